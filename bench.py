@@ -21,9 +21,13 @@ own RCCL communicator (shards.AvgPolicyExchange; `--xchg-every k` = every k slic
 time bracket the timed region; at N > 1 the line also carries every rank's own step time,
 device / PCI bus id and the exchange's cost (`ranks`).
 
-Timing: W warmup steps, then K steps with no instrumentation -> `value` / `ms_per_step`;
-then K more steps with HIP events recorded on each kernel's stream around every launch ->
-each kernel's average duration (`kernel_ms`, `ms_per_step_event_timed`).
+Timing: W warmup steps, then K steps with no instrumentation -> `value` / `ms_per_step`.
+A plain run stops there: it prints the line with what the timed pass itself counted, after
+writing the pass's outputs if `--dump-outputs DIR` asks for them (dump_outputs).  Everything
+below is measured only with `--full`: K more steps with HIP events recorded on each kernel's
+stream around every launch -> each kernel's average duration (`kernel_ms`,
+`ms_per_step_event_timed`) and the rooflines, the exact exploitability beside the CPU band, the
+engine groups (`--groups`) and the CPU baselines.
 
 Roofline (`rooflines()`): SURVEY 8(d)'s HBM framing of the kernel on the learner's critical
 path -- the chain on the stream with the longest busy span per step (`critical_stream`):
@@ -866,11 +870,76 @@ def rooflines(config, cfg, k_ms, k_launches, k_step_ms, br_upd, ar_upd, ar_max, 
     return roofline, {k: v for k, v in roofs.items() if k != roof_key}, whole_step, streams
 
 
+DUMP_ROWS = 16_384            # memory rows per table in --dump-outputs (of all replicas together)
+DUMP_STATS = ("hands", "rollouts", "rl_total", "sl_total", "rl_size", "sl_size", "last_rl", "last_sl",
+              "br_updates", "ar_updates", "iteration", "target_syncs", "actions", "reward", "epsilon",
+              "temp", "lr_br", "exploitability")
+
+
+def dump_outputs(eng, path: str, prefix: str = "") -> dict:
+    """--dump-outputs: what the timed steps left with their caller, as `path`/<name>.npy (float32;
+    the counters float64).  Per engine (a group: per replica, `r<k>_` before the name):
+    * weights: the [2 agents][AR, BR, target][NP] nets the learner trained;
+    * stats: nfsp_engine_get_stats' fields (DUMP_STATS, flattened in that order);
+    * lane_counts: the RL / SL records of every lane's hand in the last rollout;
+    * rl_<column>_a<agent> / sl_<column>_a<agent>: a fixed sample (RandomState(0), sorted, the same
+      rows of every column) of the rows of M_RL / M_SL written so far, and the rows' indices
+      (`rl_rows_a<agent>`): the memories are 100s of MB, the sample DUMP_ROWS rows per table.
+    The engine's seeds are fixed, so two runs with the same arguments write the same inputs'
+    outputs.  Returns {name: shape}."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    engines = getattr(eng, "replicas", None) or [eng]
+    rows = max(DUMP_ROWS // len(engines), 1)
+    written = {}
+
+    def save(name, a, dtype=np.float32):
+        a = np.ascontiguousarray(np.asarray(a), dtype=dtype)
+        np.save(os.path.join(path, prefix + name + ".npy"), a)
+        written[prefix + name] = list(a.shape)
+
+    def sample(n_valid, k):
+        n_valid = int(n_valid)
+        if n_valid <= k:
+            return np.arange(n_valid, dtype=np.int64)
+        return np.sort(np.random.RandomState(0).choice(n_valid, size=k, replace=False)).astype(np.int64)
+
+    for r, e in enumerate(engines):
+        tag = f"r{r}_" if len(engines) > 1 else ""
+        st = e.stats()
+        save(tag + "weights", np.stack([np.stack([e.get_weights(a, n) for n in (0, 1, 2)]) for a in (0, 1)]))
+        flat = []
+        for k in DUMP_STATS:
+            flat += [float(v) for v in np.asarray(st[k], dtype=np.float64).reshape(-1)]
+        save(tag + "stats", flat, np.float64)
+        save(tag + "lane_counts", e.lane_counts())
+        for a in (0, 1):
+            mem = e.memories(a)
+            for tbl, cols, n_valid in (("rl", ("s", "a", "r", "s2", "t"), min(mem["log_cap"], st["rl_total"][a])),
+                                       ("sl", ("s", "a"), min(mem["sl_s"].shape[0], st["sl_size"][a]))):
+                idx = sample(n_valid, rows)
+                save(f"{tag}{tbl}_rows_a{a}", idx, np.float64)
+                ti = torch.as_tensor(idx, device=mem[f"{tbl}_s"].device)
+                for c in cols:
+                    save(f"{tag}{tbl}_{c}_a{a}", mem[f"{tbl}_{c}"][ti].cpu().numpy())
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the event-timed second pass (kernel_ms, rooflines), the exact "
+                         "exploitability against the CPU band, the engine groups (--groups) and the CPU "
+                         "baselines (--no-cpu: without them).  A plain run only sets up, warms up, times "
+                         "the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what they computed (nets, counters, the last "
+                         "rollout's lane counts, a fixed sample of the memories' rows) as DIR/<name>.npy")
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS),
                     help="default: c3 at N = 1, c4 at N > 1")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
@@ -998,33 +1067,17 @@ def main():
         xcheck["after_timed_pass"] = check_ar_nets(dist, pkg.shards.ar_nets_digest(eng), "after the timed pass")
     xcalls = check_exchange_calls(x1 - x0, args.steps, cfg.get("slices", 1), args.xchg_every) \
         if avg is not None else None
-    # per-kernel durations: K more steps with HIP events around every launch (kernel_ms,
-    # roofline); their wall time is reported beside `value`, never as it
-    eng.set_timing(True)
-    eng.timings()
-    elapsed_ev = timed_steps(step, args.steps, 0, dist, torch.cuda.synchronize, device=dev)
-    timings = eng.timings()
-    eng.set_timing(False)
-    s2 = eng.stats()
-
+    dumped = None
+    if args.dump_outputs:                   # what the timed pass left, before anything else steps
+        dumped = dump_outputs(eng, args.dump_outputs, "" if world == 1 else f"rank{rank}_")
     hands_rank = args.steps * cfg["n_lanes"]
     value = job_value(hands_rank, world, elapsed)
-    br_upd = sum(s2["br_updates"]) - sum(s1["br_updates"])      # the instrumented pass's work
-    ar_upd = sum(s2["ar_updates"]) - sum(s1["ar_updates"])
-    rl_ins = sum(s1["rl_total"]) - sum(s0["rl_total"])          # the timed pass's inserts
+    br_upd = sum(s1["br_updates"]) - sum(s0["br_updates"])      # the timed pass's work
+    ar_upd = sum(s1["ar_updates"]) - sum(s0["ar_updates"])
+    rl_ins = sum(s1["rl_total"]) - sum(s0["rl_total"])
     sl_ins = sum(s1["sl_total"]) - sum(s0["sl_total"])
-    k_ms = {k: v[0] / max(v[1], 1) for k, v in timings.items()}
-    k_step_ms = {k: v[0] / args.steps for k, v in timings.items()}       # per engine step
-    k_launches = {k: v[1] for k, v in timings.items()}
     t_rl, t_sl = rl_ins / hands_rank, sl_ins / hands_rank
-    # the issue framing is per chain workgroup: the AR launch lasts as long as its longest
-    # chain, a BR launch runs up to 2R segments side by side
-    reps1, reps2 = s1.get("replicas", [s1]), s2.get("replicas", [s2])
-    ar_max = max(b["ar_updates"][a] - x["ar_updates"][a] for x, b in zip(reps1, reps2) for a in (0, 1))
-    roofline, roofs_other, whole_step, streams = rooflines(
-        args.config, cfg, k_ms, k_launches, k_step_ms, br_upd, ar_upd, ar_max, t_rl, t_sl,
-        hands_rank / elapsed, ms_per_step=elapsed / args.steps * 1e3)
-    rollout_path_ms = k_step_ms["k_rollout"] + k_step_ms["k_scan"] + k_step_ms["k_commit"]
+    # a plain run's line: the headline and what the timed pass itself counted
     out = {
         "metric": "Kuhn self-play hands/sec" if cfg.get("game") == "kuhn" else "Leduc self-play hands/sec",
         "value": value,
@@ -1033,7 +1086,6 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3,
-        "ms_per_step_event_timed": elapsed_ev / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -1041,64 +1093,99 @@ def main():
         "data": "synthetic: Philox self-play deals/draws, Glorot-uniform random-init nets",
         "config": {"workload": cfg["label"], "lanes_per_gpu": cfg["n_lanes"], "learner_replicas_per_gpu": R,
                    "rl_capacity": cfg["rl_capacity"], "sl_capacity": cfg["sl_capacity"],
-                   "inserts_per_update": 128, "batch": 128, "parallelism": (f"dp{world}: shards + AR-gradient all-reduce every "
-                                   f"{args.xchg_every} slice(s) ({avg.transport})"
-                                   if avg is not None else
-                                   f"replicas x{world} GPUs x {R} learner replicas per GPU (on-device AR average per step)"
-                                   if R > 1 else f"replicas x{world}")},
-        "roofline": roofline,
-        "roofline_other": roofs_other,
-        "whole_step_hbm_per_gpu": whole_step,
-        "kernel_ms": k_ms,
-        "kernel_ms_per_step": k_step_ms,
-        "kernel_ms_source": "HIP events around every launch, second pass of K steps",
-        "stream_ms_per_step": streams,
+                   "inserts_per_update": 128, "batch": 128, "parallelism": (
+                       f"dp{world}: shards + AR-gradient all-reduce every {args.xchg_every} slice(s) ({avg.transport})"
+                       if avg is not None else
+                       f"replicas x{world} GPUs x {R} learner replicas per GPU (on-device AR average per step)"
+                       if R > 1 else f"replicas x{world}")},
         "slices": cfg.get("slices", 1),
         "slice_lag": cfg.get("slice_lag", 1),
-        "rollout_only_hands_per_s": cfg["n_lanes"] / (rollout_path_ms * 1e-3) * world,
         "per_step": {"br_updates": br_upd / args.steps, "ar_updates": ar_upd / args.steps,
-                     "ar_updates_max_chain": ar_max / args.steps,
                      "rl_inserts_per_hand": t_rl, "sl_inserts_per_hand": t_sl},
-        "exploitability_proxy": sum(s2["exploitability"]),
+        "exploitability_proxy": sum(s1["exploitability"]),
+        "full": args.full,
     }
-    xchg_ms = k_ms.get("ar_exchange") if avg is not None and k_launches.get("ar_exchange") else None
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if avg is not None:
         out["ar_allreduce"] = {**xcalls, "calls": avg.calls, "bytes_per_call": avg.bytes_per_call,
                                "ar_nets_check": xcheck or None,
                                "backend": args.dist_backend, "transport": avg.transport, "fallback": avg.fallback,
-                               "every_slices": args.xchg_every, "gain": args.xchg_gain,
-                               "ms_per_call_event_timed": xchg_ms,
-                               "ms_per_call_is": "HIP events on the AR stream around delta + all-reduce + "
-                                                 "apply (includes waiting for the slowest rank's AR chain)"}
+                               "every_slices": args.xchg_every, "gain": args.xchg_gain}
+    mine = dict(device_identity(), ms_per_step=tl["local_s"] / args.steps * 1e3,
+                exchange_ms_per_call=None, exchanges=(x1 - x0))
+    s2 = s1
+    if args.full:
+        # per-kernel durations: K more steps with HIP events around every launch (kernel_ms,
+        # roofline); their wall time is reported beside `value`, never as it
+        eng.set_timing(True)
+        eng.timings()
+        elapsed_ev = timed_steps(step, args.steps, 0, dist, torch.cuda.synchronize, device=dev)
+        timings = eng.timings()
+        eng.set_timing(False)
+        s2 = eng.stats()
+        br_upd = sum(s2["br_updates"]) - sum(s1["br_updates"])      # the instrumented pass's work
+        ar_upd = sum(s2["ar_updates"]) - sum(s1["ar_updates"])
+        k_ms = {k: v[0] / max(v[1], 1) for k, v in timings.items()}
+        k_step_ms = {k: v[0] / args.steps for k, v in timings.items()}       # per engine step
+        k_launches = {k: v[1] for k, v in timings.items()}
+        # the issue framing is per chain workgroup: the AR launch lasts as long as its longest
+        # chain, a BR launch runs up to 2R segments side by side
+        reps1, reps2 = s1.get("replicas", [s1]), s2.get("replicas", [s2])
+        ar_max = max(b["ar_updates"][a] - x["ar_updates"][a] for x, b in zip(reps1, reps2) for a in (0, 1))
+        roofline, roofs_other, whole_step, streams = rooflines(
+            args.config, cfg, k_ms, k_launches, k_step_ms, br_upd, ar_upd, ar_max, t_rl, t_sl,
+            hands_rank / elapsed, ms_per_step=elapsed / args.steps * 1e3)
+        rollout_path_ms = k_step_ms["k_rollout"] + k_step_ms["k_scan"] + k_step_ms["k_commit"]
+        out.update({
+            "ms_per_step_event_timed": elapsed_ev / args.steps * 1e3,
+            "roofline": roofline,
+            "roofline_other": roofs_other,
+            "whole_step_hbm_per_gpu": whole_step,
+            "kernel_ms": k_ms,
+            "kernel_ms_per_step": k_step_ms,
+            "kernel_ms_source": "HIP events around every launch, second pass of K steps",
+            "stream_ms_per_step": streams,
+            "rollout_only_hands_per_s": cfg["n_lanes"] / (rollout_path_ms * 1e-3) * world,
+            "per_step": {"br_updates": br_upd / args.steps, "ar_updates": ar_upd / args.steps,
+                         "ar_updates_max_chain": ar_max / args.steps,
+                         "rl_inserts_per_hand": t_rl, "sl_inserts_per_hand": t_sl},
+            "exploitability_proxy": sum(s2["exploitability"]),
+        })
+        xchg_ms = k_ms.get("ar_exchange") if avg is not None and k_launches.get("ar_exchange") else None
+        mine.update(ms_per_step_event_timed=elapsed_ev / args.steps * 1e3, exchange_ms_per_call=xchg_ms)
+        if avg is not None:
+            out["ar_allreduce"].update({
+                "ms_per_call_event_timed": xchg_ms,
+                "ms_per_call_is": "HIP events on the AR stream around delta + all-reduce + "
+                                  "apply (includes waiting for the slowest rank's AR chain)"})
     if dist is not None:
         import socket
-        out["ranks"] = rank_report(dist, args.dist_backend, dict(
-            device_identity(), host=socket.gethostname(), ms_per_step=tl["local_s"] / args.steps * 1e3,
-            ms_per_step_event_timed=elapsed_ev / args.steps * 1e3,
-            exchange_ms_per_call=xchg_ms, exchanges=(x1 - x0)))
+        out["ranks"] = rank_report(dist, args.dist_backend, dict(mine, host=socket.gethostname()))
         if xcheck:
             out["ranks"]["ar_nets_identical"] = True      # else check_ar_nets exited 2
-    # exact exploitability of the AR nets after the timed steps (outside the timed region)
-    ex = {m: eng.exploitability(m) for m in (0, 1)}
-    out["exploitability_exact"] = {
-        "softmax_mixed": ex[0]["exploitability"], "argmax_as_executed": ex[1]["exploitability"],
-        "hands_trained_per_gpu": int(s2["hands"]), "unit": "chips (BR_0 + BR_1)"}
-    if cfg.get("game", "leduc") == "leduc" and cfg["rl_capacity"] == 200_000:
-        # the CPU reference's seed band at the same hands (one seed of the engine here): at N > 1
-        # with the exchange on, the total hands of the job (the AR net learned from all of them)
-        exchanged = avg is not None and world > 1
-        chk = learning_check(ex[0]["exploitability"], int(s2["hands"]), world, exchanged)
-        out["exploitability_exact"]["vs_cpu_band"] = chk
-        if exchanged:
-            out["ar_allreduce"]["learning_at_total_hands"] = chk
-    if world == 1 and args.config == "c3" and args.groups:
+    if args.full:
+        # exact exploitability of the AR nets after the timed steps (outside the timed region)
+        ex = {m: eng.exploitability(m) for m in (0, 1)}
+        out["exploitability_exact"] = {
+            "softmax_mixed": ex[0]["exploitability"], "argmax_as_executed": ex[1]["exploitability"],
+            "hands_trained_per_gpu": int(s2["hands"]), "unit": "chips (BR_0 + BR_1)"}
+        if cfg.get("game", "leduc") == "leduc" and cfg["rl_capacity"] == 200_000:
+            # the CPU reference's seed band at the same hands (one seed of the engine here): at N > 1
+            # with the exchange on, the total hands of the job (the AR net learned from all of them)
+            exchanged = avg is not None and world > 1
+            chk = learning_check(ex[0]["exploitability"], int(s2["hands"]), world, exchanged)
+            out["exploitability_exact"]["vs_cpu_band"] = chk
+            if exchanged:
+                out["ar_allreduce"]["learning_at_total_hands"] = chk
+    if args.full and world == 1 and args.config == "c3" and args.groups:
         # several learners on the one GPU (engine groups): new measured configs, not the headline
         eng.close()
         del eng
         torch.cuda.empty_cache()
         out["groups"] = {name: measure_group(pkg, name, max(args.steps, 10), args.warmup)
                          for name in args.groups.split(",")}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.config, args.cpu_cores)
         out["cpu_baseline_numpy"] = cpu_baseline_numpy(min(args.cpu_seconds, 5.0), args.config, args.cpu_cores)
         out["cpu_baseline_rollout"] = cpu_baseline_rollout(min(args.cpu_seconds, 4.0), args.config, args.cpu_cores)

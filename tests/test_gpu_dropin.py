@@ -130,8 +130,8 @@ def test_dropin_main_train_matches_oracle(pkg):
 # A driver with main.py's module-level imports and main() (main.py:1-18,127-146), written
 # for this test (the reference checkout is not on the GPU box): `reference_main.run`
 # resolves its imports to the drop-in and the stand-ins, runs it as __main__ in its own
-# directory, and it trains on the GPU classes.  tests/test_reference_main.py runs the
-# reference's own main.py through the same launcher on CPU.
+# directory, and it trains on the GPU classes.  tests/test_reference_main.py checks the
+# launcher's stand-ins and command line on CPU.
 _DRIVER = '''
 import random
 import tensorflow as tf

@@ -10,6 +10,6 @@ for v in noxchg xchg; do
   extra=""
   [ $v = xchg ] && extra="--ar-allreduce on --xchg-gain 1"
   timeout -k 10 300 rocprofv3 --kernel-trace --hip-runtime-trace --stats --output-format csv -d "$O" -o $v -- \
-    python3 "$R/bench.py" --config c4 --no-cpu --groups '' --steps 2 --warmup 1 $extra > "$O/$v.json" 2> "$O/$v.err" || { tail -20 "$O/$v.err"; exit 1; }
+    python3 "$R/bench.py" --full --config c4 --no-cpu --groups '' --steps 2 --warmup 1 $extra > "$O/$v.json" 2> "$O/$v.err" || { tail -20 "$O/$v.err"; exit 1; }
 done
 ls "$O"
