@@ -496,6 +496,54 @@ int nfsp_group_check(nfsp_group* g);
 int nfsp_group_set_trace(nfsp_group* g, int on);
 int nfsp_group_trace(nfsp_group* g, int32_t* out, int64_t cap, int64_t* n);
 
+/* ---- checkpoint and resume (the reference has none: main.py:21-75 trains in one
+ * process and keeps nothing) ----
+ * A state blob is one contiguous host buffer, and that buffer is the file: a little-endian
+ * header (magic, format version, sizes, section table, 128-bit digest of the payload) and the
+ * payload -- cfg and game, the schedules, EngineDev, the six nets, the live M_RL records in
+ * insert order and the M_SL rows.  Session settings are not stored (timing, the loss log, the
+ * update limit, a group's schedule and trace, the exchange transport and cadence: re-issue
+ * nfsp_engine_set_exchange after a load).  A run continued from a loaded blob is bit-identical
+ * to the uninterrupted one.
+ *   Save is legal at a step boundary only (else NFSP_EINVAL): no rollout awaiting its
+ * nfsp_engine_update, every slice of the step played, no exchange pending, and with an exchange
+ * configured its learner-call count a multiple of `every`.  It synchronises the engine's streams.
+ *   Load checks everything on the host before it writes anything (magic, version, sizes, section
+ * bounds, the digest; then n_lanes, hidden, both capacities, batch, inserts_per_update,
+ * target_every, epochs, fit_batch, quirks, eta, lr_*, gamma, epsilon, seed and game against the
+ * engine: NFSP_EINVAL, the engine untouched).  slices, slice_lag and sched may differ: the
+ * payload does not depend on them.  After the copy the device state's digest is recomputed in
+ * place (csrc/state.hip k_state_digest) and compared with the header's: NFSP_EHIP on a mismatch.
+ * A replica of a group is saved and loaded with its group. */
+typedef struct nfsp_state_info {
+  int32_t version, kind;                /* format version (1); 1 = an engine's blob, 2 = a group's */
+  int32_t replicas, n_sections;
+  int32_t slices, slice_lag;            /* the saving engine's cfg.slices / slice_lag / sched */
+  uint32_t sched, group_flags;
+  int64_t total_bytes, payload_offset, payload_bytes;
+  uint64_t digest[2];                   /* of the payload */
+} nfsp_state_info;
+/* bytes a save would write now (synchronises) */
+int nfsp_engine_state_bytes(nfsp_engine* e, int64_t* out);
+int nfsp_engine_save_state(nfsp_engine* e, void* host_buf, int64_t cap, int64_t* written);
+int nfsp_engine_load_state(nfsp_engine* e, const void* host_buf, int64_t n);
+/* The digest a save at this point would put in its header, computed on the device state where
+ * it lies: equal for two engines iff they hold the same training state, whatever their
+ * slicing.  Step boundaries only; synchronises.  A group replica's handle is accepted. */
+int nfsp_engine_state_digest(nfsp_engine* e, uint64_t out[2]);
+/* The same, also reporting the digest kernels' time (HIP events around them) and the bytes
+ * they read -- how profiles/ckpt/digest_c3.json was measured. */
+int nfsp_engine_state_digest_timed(nfsp_engine* e, uint64_t out[2], double* ms, int64_t* bytes);
+int nfsp_group_state_bytes(nfsp_group* g, int64_t* out);
+int nfsp_group_save_state(nfsp_group* g, void* host_buf, int64_t cap, int64_t* written);
+int nfsp_group_load_state(nfsp_group* g, const void* host_buf, int64_t n);
+/* Host only, no device: parse a blob, check its bounds and its digest; info may be NULL. */
+int nfsp_state_check(const void* buf, int64_t n, nfsp_state_info* info);
+/* Host only: replica's (0 for an engine's blob) cfg, with the saver's slicing, and game. */
+int nfsp_state_cfg(const void* buf, int64_t n, int replica, nfsp_engine_cfg* cfg, int32_t* game);
+/* Host only: the digest of n bytes (whole 8-byte words) taken as a payload. */
+int nfsp_state_digest(const void* payload, int64_t n, uint64_t out[2]);
+
 /* ---- evaluation ----
  * Exact exploitability of two average-policy nets (packed weights, device pointers; e.g.
  * nfsp_engine_weights(e, a, 0, ..)) in this Leduc variant as main.train plays it

@@ -297,6 +297,7 @@ struct nfsp_engine {
   int64_t update_limit = 0;    // test hook (nfsp_engine_set_update_limit): chains stop after this many
   std::vector<hipEvent_t> pool;
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> marks;
+  uint64_t* digest_buf = nullptr;    // k_state_digest's per-workgroup partials (state.hip), on first use
 };
 
 namespace nfsp {
@@ -322,6 +323,20 @@ int group_snap_part_launch(nfsp_engine* const* eng, int R, const void* d_tab, in
                            int r0 = 0);
 // the cross-shard exchange of the AR nets, enqueued on `s` (the AR chain stream)
 int exchange_enqueue(nfsp_engine* e, hipStream_t s);
+// what state.hip saves and restores of an engine group (learner.hip owns nfsp_group)
+struct GroupState {
+  nfsp_ctx* ctx;
+  int R;
+  unsigned flags;
+  nfsp_engine* const* eng;     // [R]
+  float* w0;                   // [3 nets][2 agents][NP], device
+  unsigned* w0_valid;
+  int64_t* calls;
+  int xchg_every;
+  hipStream_t streams[6];      // the group's learner streams (nullptr: not created)
+  int n_streams;
+};
+int group_state(nfsp_group* g, GroupState* out);
 
 // RAII bracket: records start/stop events around launches on `stream` when timing is on
 struct KTimer {

@@ -1190,6 +1190,27 @@ extern "C" int nfsp_group_create(nfsp_ctx* ctx, const nfsp_engine_cfg* cfg, int 
   return NFSP_OK;
 }
 
+namespace nfsp {
+namespace eng {
+int group_state(nfsp_group* g, GroupState* out) {
+  NFSP_REQUIRE(g && out, "null argument");
+  *out = GroupState{};
+  out->ctx = g->ctx;
+  out->R = g->R;
+  out->flags = g->flags;
+  out->eng = g->eng.data();
+  out->w0 = g->w0;
+  out->w0_valid = &g->w0_valid;
+  out->calls = &g->calls;
+  out->xchg_every = g->xchg_every;
+  out->streams[out->n_streams++] = g->s_ar;
+  out->streams[out->n_streams++] = g->s_br;
+  for (hipStream_t st : g->s_brp) out->streams[out->n_streams++] = st;
+  return NFSP_OK;
+}
+}  // namespace eng
+}  // namespace nfsp
+
 extern "C" int nfsp_group_engine(nfsp_group* g, int r, nfsp_engine** out) {
   NFSP_REQUIRE(g && out && r >= 0 && r < g->R, "bad argument");
   *out = g->eng[r];

@@ -19,7 +19,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import native
+from . import checkpoint, native
 
 NP = 30 * 64 + 64 + 64 * 3 + 3
 NET_AR, NET_BR, NET_TARGET = 0, 1, 2
@@ -244,6 +244,49 @@ class SelfPlayEngine:
         mode 0 = softmax mixed strategies, 1 = the argmax the env executes."""
         return exploitability(self.ctx, self._wptr(0, NET_AR), self._wptr(1, NET_AR), mode)
 
+    # -- checkpoints (checkpoint.py, DESIGN.md §10) ----------------------------------
+    def save(self, path):
+        """Save the engine at a step boundary (nfsp_engine_save_state); returns the bytes written."""
+        return checkpoint.save(self, path)
+
+    def load(self, path):
+        """Load a checkpoint into this engine (nfsp_engine_load_state): the continued run is
+        bit-identical to the uninterrupted one.  Re-issue ``set_exchange`` afterwards."""
+        checkpoint.load(self, path)
+
+    def state_digest(self) -> tuple:
+        """(D0, D1) a save would put in its header now, computed on the device state in place
+        (nfsp_engine_state_digest): equal iff the training state is, whatever the slicing."""
+        d = (native.U64 * 2)()
+        native.check(self.L.nfsp_engine_state_digest(self.h, d), "nfsp_engine_state_digest")
+        return int(d[0]), int(d[1])
+
+    def state_digest_timed(self) -> tuple:
+        """((D0, D1), the digest kernels' ms, the bytes they read) -- nfsp_engine_state_digest_timed."""
+        d, ms, nb = (native.U64 * 2)(), native.F64(), native.I64()
+        native.check(self.L.nfsp_engine_state_digest_timed(self.h, d, C.byref(ms), C.byref(nb)),
+                     "nfsp_engine_state_digest_timed")
+        return (int(d[0]), int(d[1])), ms.value, nb.value
+
+    @classmethod
+    def from_checkpoint(cls, path, ctx: native.Context | None = None, init_seed: int = 0, **overrides):
+        """An engine built from the file's cfg and game, then loaded from it.  ``overrides``:
+        slices, slice_lag and sched only (the state does not depend on them).  The initial nets
+        (``init_seed``) are overwritten by the load."""
+        data = np.fromfile(path, dtype=np.uint8)
+        info = checkpoint.check(data)
+        if info.kind != checkpoint.KIND_ENGINE:
+            raise native.NativeError("from_checkpoint: the file holds an engine group (EngineGroup.from_checkpoint)")
+        cfg, game = checkpoint.stored_cfg(data)
+        kw = checkpoint.apply_overrides(cfg, overrides)
+        eng = cls(ctx if ctx is not None else native.Context(1, game=game), init_seed=init_seed, **kw)
+        try:
+            checkpoint.load_bytes(eng, data)
+        except Exception:
+            eng.close()
+            raise
+        return eng
+
     def close(self):
         if getattr(self, "h", None) and getattr(self, "_owner", None) is None:
             self.L.nfsp_engine_destroy(self.h)
@@ -372,6 +415,38 @@ class EngineGroup:
         w0 = [e._wptr(0, NET_AR) for e in self.replicas]
         w1 = [e._wptr(1, NET_AR) for e in self.replicas]
         return exploitability_batch(self.ctx, w0, w1, mode)
+
+    # -- checkpoints (checkpoint.py) ----------------------------------
+    def save(self, path):
+        """Save the group at a step boundary (nfsp_group_save_state): every replica, and the
+        exchange's W0 with its "already broadcast" flags; returns the bytes written."""
+        return checkpoint.save(self, path)
+
+    def load(self, path):
+        checkpoint.load(self, path)
+
+    def state_digest(self) -> list:
+        """Every replica's ``SelfPlayEngine.state_digest()``."""
+        return [e.state_digest() for e in self.replicas]
+
+    @classmethod
+    def from_checkpoint(cls, path, ctx: native.Context | None = None, init_seed: int = 0, **overrides):
+        """A group built from the file's replica count, flags, cfg and game, then loaded from it
+        (``overrides``: slices, slice_lag and sched only)."""
+        data = np.fromfile(path, dtype=np.uint8)
+        info = checkpoint.check(data)
+        if info.kind != checkpoint.KIND_GROUP:
+            raise native.NativeError("from_checkpoint: the file holds a single engine (SelfPlayEngine.from_checkpoint)")
+        cfg, game = checkpoint.stored_cfg(data, 0)
+        kw = checkpoint.apply_overrides(cfg, overrides)
+        grp = cls(info.replicas, ctx if ctx is not None else native.Context(1, game=game), init_seed=init_seed,
+                  avg_ar=bool(info.group_flags & native.GROUP_AVG_AR), **kw)
+        try:
+            checkpoint.load_bytes(grp, data)
+        except Exception:
+            grp.close()
+            raise
+        return grp
 
     def close(self):
         if getattr(self, "h", None):

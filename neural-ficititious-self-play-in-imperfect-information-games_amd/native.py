@@ -72,6 +72,14 @@ class EngineStats(C.Structure):
         return out
 
 
+class StateInfo(C.Structure):
+    """``nfsp_state_info``: what nfsp_state_check reads from a state blob's header"""
+    _fields_ = [("version", C.c_int32), ("kind", C.c_int32), ("replicas", C.c_int32),
+                ("n_sections", C.c_int32), ("slices", C.c_int32), ("slice_lag", C.c_int32),
+                ("sched", C.c_uint32), ("group_flags", C.c_uint32), ("total_bytes", I64),
+                ("payload_offset", I64), ("payload_bytes", I64), ("digest", U64 * 2)]
+
+
 PP = C.POINTER(P)
 # name -> (restype, argtypes); must list every symbol include/nfsp.h declares
 SIGNATURES = {
@@ -140,6 +148,17 @@ SIGNATURES = {
     "nfsp_rccl_unique_id": (I32, [P]),
     "nfsp_rccl_comm_create": (I32, [P, I32, I32, I32, C.POINTER(P)]),
     "nfsp_rccl_comm_destroy": (I32, [P]),
+    "nfsp_engine_state_bytes": (I32, [P, C.POINTER(I64)]),
+    "nfsp_engine_save_state": (I32, [P, P, I64, C.POINTER(I64)]),
+    "nfsp_engine_load_state": (I32, [P, P, I64]),
+    "nfsp_engine_state_digest": (I32, [P, C.POINTER(U64)]),
+    "nfsp_engine_state_digest_timed": (I32, [P, C.POINTER(U64), C.POINTER(F64), C.POINTER(I64)]),
+    "nfsp_group_state_bytes": (I32, [P, C.POINTER(I64)]),
+    "nfsp_group_save_state": (I32, [P, P, I64, C.POINTER(I64)]),
+    "nfsp_group_load_state": (I32, [P, P, I64]),
+    "nfsp_state_check": (I32, [P, I64, C.POINTER(StateInfo)]),
+    "nfsp_state_cfg": (I32, [P, I64, I32, C.POINTER(EngineCfg), C.POINTER(C.c_int32)]),
+    "nfsp_state_digest": (I32, [P, I64, C.POINTER(U64)]),
 }
 # int (*nfsp_exchange_fn)(void* user, float* dev_sum, int64_t n)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, P, P, I64)
