@@ -436,6 +436,33 @@ typedef struct nfsp_group nfsp_group;
 #define NFSP_GROUP_AVG_AR 1u
 int nfsp_group_create(nfsp_ctx* ctx, const nfsp_engine_cfg* cfg, int replicas, unsigned flags,
                       nfsp_group** out);
+/* Heterogeneous groups: a hyperparameter sweep in one launch.  Replica r is an
+ * independent main.train with cfgs[r] exactly as given (its seed is NOT offset by r),
+ * bit-identical to a standalone engine created with cfgs[r] and stepped as often.
+ *   May differ between replicas: seed, eta, lr_br, lr_ar, gamma, epsilon, target_every, and
+ * quirks outside NFSP_EXT_LINEAR_Q | NFSP_EXT_MSE_Q.  Each reaches the shared launches through
+ * the replica's own rows of their device tables (the rollout's and the prep kernels' arguments,
+ * the BR targets' jobs, the schedules), never through a launch-wide argument.
+ *   Must be equal: n_lanes, hidden, rl_capacity, sl_capacity, batch, inserts_per_update, epochs,
+ * fit_batch, slices, slice_lag, sched -- the shapes of the shared launches and of the buffers
+ * behind them -- and the quirk bits NFSP_EXT_LINEAR_Q and NFSP_EXT_MSE_Q, which select the BR
+ * chain kernel of a shared launch.  A difference is NFSP_EINVAL; nfsp_last_error names the field
+ * and the replica.  Two replicas with identical cfgs, seed included, are legal.
+ *   A group is uniform when every replica's cfg equals replica 0's apart from the seed
+ * (nfsp_group_create(cfg, R) = nfsp_group_create_v with cfgs[r] = *cfg, seed + r); otherwise
+ * it is heterogeneous, and has no exchange: NFSP_GROUP_AVG_AR here, nfsp_group_set_exchange with
+ * every > 0 and nfsp_group_average_ar are NFSP_EINVAL (an average of nets trained under
+ * different hyperparameters is not a sweep).  With sched.br_persist, a group whose replicas
+ * differ in gamma, lr_br or quirks keeps the BR rounds (k_br_persist takes one of each per
+ * launch). */
+int nfsp_group_create_v(nfsp_ctx* ctx, const nfsp_engine_cfg* cfgs /*[replicas]*/, int replicas,
+                        unsigned flags, nfsp_group** out);
+/* Host only, no device: would nfsp_group_create_v accept these?  NFSP_EINVAL, with
+ * nfsp_last_error naming the first offending field and replica (also a cfg that
+ * nfsp_engine_create would refuse, and NFSP_GROUP_AVG_AR in flags on a heterogeneous list). */
+int nfsp_group_cfgs_check(const nfsp_engine_cfg* cfgs /*[replicas]*/, int replicas, unsigned flags);
+/* Replica's cfg as the group runs it. */
+int nfsp_group_replica_cfg(nfsp_group* g, int replica, nfsp_engine_cfg* out);
 int nfsp_group_destroy(nfsp_group* g);
 int nfsp_group_engine(nfsp_group* g, int replica, nfsp_engine** out);
 int nfsp_group_step(nfsp_group* g);
@@ -514,7 +541,9 @@ int nfsp_group_trace(nfsp_group* g, int32_t* out, int64_t cap, int64_t* n);
  * engine: NFSP_EINVAL, the engine untouched).  slices, slice_lag and sched may differ: the
  * payload does not depend on them.  After the copy the device state's digest is recomputed in
  * place (csrc/state.hip k_state_digest) and compared with the header's: NFSP_EHIP on a mismatch.
- * A replica of a group is saved and loaded with its group. */
+ * A replica of a group is saved and loaded with its group: the blob holds every replica's cfg
+ * (nfsp_state_cfg), replica r's is checked against replica r's engine, and the message of a
+ * mismatch names the replica. */
 typedef struct nfsp_state_info {
   int32_t version, kind;                /* format version (1); 1 = an engine's blob, 2 = a group's */
   int32_t replicas, n_sections;

@@ -550,10 +550,9 @@ extern "C" int nfsp_engine_destroy(nfsp_engine* e) {
 
 namespace nfsp {
 namespace eng {
-// own_streams: the engine's own AR / BR chain streams (nfsp_engine_update); a replica of an
-// engine group has none (the group launches its chains)
-int engine_create(nfsp_ctx* ctx, const nfsp_engine_cfg* cfg, bool own_streams, nfsp_engine** out) {
-  NFSP_REQUIRE(ctx && cfg && out, "null argument");
+// what any engine's cfg must satisfy (host only: nfsp_group_cfgs_check runs it without a device)
+int engine_cfg_check(const nfsp_engine_cfg* cfg) {
+  NFSP_REQUIRE(cfg, "null argument");
   NFSP_REQUIRE(cfg->hidden == nn::H, "only hidden == 64 is built");
   NFSP_REQUIRE(cfg->n_lanes > 0 && cfg->n_lanes < (1 << 24), "n_lanes must be in [1, 2^24)");
   NFSP_REQUIRE(cfg->slices >= 1 && cfg->n_lanes % cfg->slices == 0,
@@ -578,6 +577,15 @@ int engine_create(nfsp_ctx* ctx, const nfsp_engine_cfg* cfg, bool own_streams, n
   NFSP_REQUIRE((4 * (int64_t)(cfg->n_lanes / cfg->slices) / cfg->inserts_per_update + 2) * cfg->epochs *
                        (cfg->batch / CHAIN_MB) * (int64_t)sizeof(StepRec) < (1ll << 31),
                "one slice's step records exceed 2 GiB: use more slices (or more inserts per update)");
+  return NFSP_OK;
+}
+
+// own_streams: the engine's own AR / BR chain streams (nfsp_engine_update); a replica of an
+// engine group has none (the group launches its chains)
+int engine_create(nfsp_ctx* ctx, const nfsp_engine_cfg* cfg, bool own_streams, nfsp_engine** out) {
+  NFSP_REQUIRE(ctx && cfg && out, "null argument");
+  const int ck = engine_cfg_check(cfg);
+  if (ck != NFSP_OK) return ck;
   *out = nullptr;
   nfsp_engine* e = new nfsp_engine();
   e->ctx = ctx;

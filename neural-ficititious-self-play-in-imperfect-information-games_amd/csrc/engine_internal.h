@@ -304,6 +304,7 @@ namespace nfsp {
 namespace eng {
 
 hipEvent_t take_event(nfsp_engine* e);
+int engine_cfg_check(const nfsp_engine_cfg* cfg);   // nfsp_engine_create's cfg rules, host only
 int engine_create(nfsp_ctx* ctx, const nfsp_engine_cfg* cfg, bool own_streams, nfsp_engine** out);
 int rollout_launch(nfsp_engine* e);   // nfsp_rollout's launches
 // the same with the acting nets / epsilon given (cfg.slice_lag 2: a snapshot)

@@ -281,14 +281,33 @@ struct TargetJob {
   const float* tw;     // target net
   int64_t u0, n;
   int64_t it0;         // the agent's iteration count before the learner call
+  // the replica's own cfg.gamma / lr_br / quirks: the replicas of a group may differ in them
+  // (nfsp_group_create_v), so they travel with the job, not with the launch
+  double gamma, lr0;
+  unsigned quirks;
 };
 
-// blockIdx.x = update within the segment; blockIdx.y = job (of `jobs`, else `one`)
+// a workgroup-uniform field of a job that arrived in VGPRs, in SGPRs (as brp_uniform's below)
+__device__ __forceinline__ unsigned tj_uniform(unsigned x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ double tj_uniform(double x) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// blockIdx.x = update within the segment; blockIdx.y = job (of `jobs`, else `one`).  gamma, lr0
+// and quirks are the job's own (one engine: its cfg's; a group: each replica's).
 __global__ void __launch_bounds__(256) k_br_targets(const TargetJob* __restrict__ jobs, TargetJob one,
-                                                    int B, int E, double gamma, unsigned quirks,
-                                                    double lr0) {
+                                                    int B, int E) {
   const TargetJob J = jobs ? jobs[blockIdx.y] : one;
   const int64_t bx = blockIdx.x;
+  // The compiler folds the two sources of J into one selected address and loads the job through
+  // it with vector loads, the by-value `one` (kernel-argument memory) included.  The three values
+  // that were launch-wide arguments steer branches and selects of the whole workgroup (br_act,
+  // the ROW0 / TERMINAL quirks) and the f64 TD and lr arithmetic: made scalar again.
+  const double gamma = tj_uniform(J.gamma), lr0 = tj_uniform(J.lr0);
+  const unsigned quirks = tj_uniform(J.quirks);
 #include "br_targets_body.inc"
 }
 
@@ -788,6 +807,9 @@ TargetJob br_target_job(const nfsp_engine* e, const LearnPlan& L, int a, const S
   t.u0 = sg.u;
   t.n = sg.v - sg.u;
   t.it0 = L.it0[a];
+  t.gamma = e->cfg.gamma;
+  t.lr0 = e->cfg.lr_br;
+  t.quirks = e->cfg.quirks;
   return t;
 }
 
@@ -930,8 +952,7 @@ static int update_impl(nfsp_engine* e, bool pipelined, int par, bool snap_after)
         {
           KTimer kt2(e, KT_TARGETS, sa);
           k_br_targets<<<(unsigned)(sg.v - sg.u), 256, 0, sa>>>(nullptr, br_target_job(e, L, a, sg),
-                                                                  cfg.batch, cfg.epochs, cfg.gamma,
-                                                                  cfg.quirks, cfg.lr_br);
+                                                                  cfg.batch, cfg.epochs);
         }
         NFSP_LAUNCHED("k_br_targets");
         ChainArgs C{};
@@ -1042,6 +1063,10 @@ struct nfsp_group {
   nfsp_ctx* ctx = nullptr;
   int R = 0;
   unsigned flags = 0;
+  // nfsp_group_create_v: some replica's cfg differs from replica 0's in more than the seed (no
+  // exchange then); br_uniform: gamma, lr_br and quirks are the same everywhere (k_br_persist's
+  // launch-wide BrPersistArgs carry one of each)
+  bool hetero = false, br_uniform = true;
   std::vector<nfsp_engine*> eng;
   hipStream_t s_ar = nullptr, s_br = nullptr;
   // further BR streams: a sliced group's BR jobs run in up to GROUP_BR_STREAMS partitions,
@@ -1112,12 +1137,97 @@ extern "C" int nfsp_group_destroy(nfsp_group* g) {
   return NFSP_OK;
 }
 
+namespace {
+// The fields the replicas of a group must share: the shapes of the shared launches (lanes,
+// slices, batch, epochs and the learner buffers sized from them), the memories' sizes, the
+// schedule flags, and the two quirk bits that select the BR chain kernel of a shared launch
+// (k_chain3<1 / 2 / 3>).  The first one in which b differs from a, or nullptr.
+constexpr uint32_t GROUP_UNIFORM_QUIRKS = NFSP_EXT_LINEAR_Q | NFSP_EXT_MSE_Q;
+const char* group_uniform_diff(const nfsp_engine_cfg& a, const nfsp_engine_cfg& b) {
+  if (a.n_lanes != b.n_lanes) return "n_lanes";
+  if (a.hidden != b.hidden) return "hidden";
+  if (a.rl_capacity != b.rl_capacity) return "rl_capacity";
+  if (a.sl_capacity != b.sl_capacity) return "sl_capacity";
+  if (a.batch != b.batch) return "batch";
+  if (a.inserts_per_update != b.inserts_per_update) return "inserts_per_update";
+  if (a.epochs != b.epochs) return "epochs";
+  if (a.fit_batch != b.fit_batch) return "fit_batch";
+  if (a.slices != b.slices) return "slices";
+  if (a.slice_lag != b.slice_lag) return "slice_lag";
+  if (a.sched != b.sched) return "sched";
+  if ((a.quirks ^ b.quirks) & GROUP_UNIFORM_QUIRKS) return "quirks (NFSP_EXT_LINEAR_Q | NFSP_EXT_MSE_Q)";
+  return nullptr;
+}
+// The fields that may differ, the seed apart (bit patterns: -0.0 and 0.0 are different cfgs, as
+// in a state blob's comparison): the first one in which b differs from a, or nullptr.
+const char* group_free_diff(const nfsp_engine_cfg& a, const nfsp_engine_cfg& b) {
+  if (memcmp(&a.eta, &b.eta, sizeof(float))) return "eta";
+  if (memcmp(&a.lr_br, &b.lr_br, sizeof(float))) return "lr_br";
+  if (memcmp(&a.lr_ar, &b.lr_ar, sizeof(float))) return "lr_ar";
+  if (memcmp(&a.gamma, &b.gamma, sizeof(double))) return "gamma";
+  if (memcmp(&a.epsilon, &b.epsilon, sizeof(double))) return "epsilon";
+  if (a.target_every != b.target_every) return "target_every";
+  if (a.quirks != b.quirks) return "quirks";
+  return nullptr;
+}
+bool group_br_same(const nfsp_engine_cfg& a, const nfsp_engine_cfg& b) {
+  return !memcmp(&a.gamma, &b.gamma, sizeof(double)) && !memcmp(&a.lr_br, &b.lr_br, sizeof(float)) &&
+         a.quirks == b.quirks;
+}
+
+// nfsp_group_cfgs_check's rules; hetero / br_uniform (may be null): see nfsp_group
+int group_cfgs_scan(const nfsp_engine_cfg* cfgs, int replicas, unsigned flags, bool* hetero, bool* br_uniform) {
+  NFSP_REQUIRE(cfgs, "null argument");
+  NFSP_REQUIRE(replicas >= 1 && replicas <= NFSP_GROUP_MAX_REPLICAS, "replicas must be in [1, 256]");
+  NFSP_REQUIRE((flags & ~NFSP_GROUP_AVG_AR) == 0, "unknown group flags");
+  bool het = false, bru = true;
+  for (int r = 0; r < replicas; ++r) {
+    if (const char* f = group_uniform_diff(cfgs[0], cfgs[r]))
+      return nfsp::fail(NFSP_EINVAL, std::string("group cfgs: ") + f + " of replica " + std::to_string(r) +
+                                         " differs from replica 0's (the replicas of a group share it)");
+    if (nfsp::eng::engine_cfg_check(&cfgs[r]) != NFSP_OK)
+      return nfsp::fail(NFSP_EINVAL, "group cfgs: replica " + std::to_string(r) + ": " + nfsp_last_error());
+    const char* d = group_free_diff(cfgs[0], cfgs[r]);
+    if (d && (flags & NFSP_GROUP_AVG_AR))
+      return nfsp::fail(NFSP_EINVAL, std::string("group cfgs: NFSP_GROUP_AVG_AR on a heterogeneous group (") + d +
+                                         " of replica " + std::to_string(r) +
+                                         " differs from replica 0's): nets trained under different "
+                                         "hyperparameters are not averaged");
+    het = het || d != nullptr;
+    bru = bru && group_br_same(cfgs[0], cfgs[r]);
+  }
+  if (hetero) *hetero = het;
+  if (br_uniform) *br_uniform = bru;
+  return NFSP_OK;
+}
+}  // namespace
+
+extern "C" int nfsp_group_cfgs_check(const nfsp_engine_cfg* cfgs, int replicas, unsigned flags) {
+  return group_cfgs_scan(cfgs, replicas, flags, nullptr, nullptr);
+}
+
 extern "C" int nfsp_group_create(nfsp_ctx* ctx, const nfsp_engine_cfg* cfg, int replicas, unsigned flags,
                                  nfsp_group** out) {
   NFSP_REQUIRE(ctx && cfg && out, "null argument");
   NFSP_REQUIRE(replicas >= 1 && replicas <= NFSP_GROUP_MAX_REPLICAS, "replicas must be in [1, 256]");
-  NFSP_REQUIRE((flags & ~NFSP_GROUP_AVG_AR) == 0, "unknown group flags");
-  NFSP_REQUIRE(cfg->slices >= 1, "slices must be >= 1");
+  std::vector<nfsp_engine_cfg> cfgs((size_t)replicas, *cfg);
+  for (int r = 0; r < replicas; ++r) cfgs[r].seed = cfg->seed + (uint64_t)r;
+  return nfsp_group_create_v(ctx, cfgs.data(), replicas, flags, out);
+}
+
+extern "C" int nfsp_group_replica_cfg(nfsp_group* g, int replica, nfsp_engine_cfg* out) {
+  NFSP_REQUIRE(g && out && replica >= 0 && replica < g->R, "bad argument");
+  *out = g->eng[replica]->cfg;
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_group_create_v(nfsp_ctx* ctx, const nfsp_engine_cfg* cfgs, int replicas, unsigned flags,
+                                   nfsp_group** out) {
+  NFSP_REQUIRE(ctx && cfgs && out, "null argument");
+  bool hetero = false, br_uniform = true;
+  int ck = group_cfgs_scan(cfgs, replicas, flags, &hetero, &br_uniform);
+  if (ck != NFSP_OK) return ck;
+  const nfsp_engine_cfg* cfg = &cfgs[0];   // the fields every replica shares
   *out = nullptr;
   // up to 4R chain workgroups run at once (2R AR + a BR round's 2R): past one per CU they
   // share CUs, each with an equal share of the LDS
@@ -1128,6 +1238,8 @@ extern "C" int nfsp_group_create(nfsp_ctx* ctx, const nfsp_engine_cfg* cfg, int 
   g->ctx = ctx;
   g->R = replicas;
   g->flags = flags;
+  g->hetero = hetero;
+  g->br_uniform = br_uniform;
   if (flags & NFSP_GROUP_AVG_AR) {     // the per-step AR exchange
     g->xchg_nets = NFSP_XCHG_AR;
     g->xchg_every = cfg->slices;
@@ -1136,10 +1248,8 @@ extern "C" int nfsp_group_create(nfsp_ctx* ctx, const nfsp_engine_cfg* cfg, int 
   g->chain_lds = chain_lds_shared((4 * replicas + cus - 1) / (cus > 0 ? cus : 1));
   nfsp_group_default_sched(&g->sched);
   for (int r = 0; r < replicas; ++r) {
-    nfsp_engine_cfg c = *cfg;
-    c.seed = cfg->seed + (uint64_t)r;
     nfsp_engine* e = nullptr;
-    const int rc = nfsp::eng::engine_create(ctx, &c, false, &e);
+    const int rc = nfsp::eng::engine_create(ctx, &cfgs[r], false, &e);
     if (rc != NFSP_OK) {
       nfsp_group_destroy(g);
       return rc;
@@ -1232,6 +1342,8 @@ static int group_xchg_launch(nfsp_group* g, hipStream_t s) {
 
 extern "C" int nfsp_group_average_ar(nfsp_group* g) {
   NFSP_REQUIRE(g, "null argument");
+  NFSP_REQUIRE(!g->hetero,
+               "nfsp_group_average_ar: the replicas' cfgs differ (a heterogeneous group has no exchange)");
   return group_xchg_launch(g, g->ctx->stream);
 }
 
@@ -1239,6 +1351,8 @@ extern "C" int nfsp_group_set_exchange(nfsp_group* g, unsigned nets, int every, 
   NFSP_REQUIRE(g, "null argument");
   NFSP_REQUIRE((nets & ~(NFSP_XCHG_AR | NFSP_XCHG_BR)) == 0, "nets: NFSP_XCHG_AR | NFSP_XCHG_BR");
   NFSP_REQUIRE(every >= 0 && (every == 0 || nets), "every >= 0 (and nets when on)");
+  NFSP_REQUIRE(every == 0 || !g->hetero,
+               "nfsp_group_set_exchange: the replicas' cfgs differ (a heterogeneous group has no exchange)");
   // a net this call turns on starts like the rank path's (AvgPolicyExchange broadcasts rank 0's
   // nets, then nfsp_engine_set_exchange takes them as W0): its next exchange copies replica 0's
   // net everywhere instead of applying deltas against a W0 from before the exchange was off
@@ -1285,6 +1399,10 @@ static int group_update(nfsp_group* g, bool pipelined = false, int par = 0, bool
   hipStream_t s = g->ctx->stream;
   const int R = g->R;
   nfsp_engine* e0 = g->eng[0];
+  // replica 0's cfg stands for the fields every replica shares (batch, epochs, the LINEAR_Q /
+  // MSE_Q quirk bits; group_uniform_diff).  What may differ -- target_every, lr_*, gamma, epsilon,
+  // eta, the other quirks, the seed -- is read from each replica's own cfg: by plan_update (the
+  // segments and schedules, PrepArgs) and br_target_job (the targets' gamma, lr0, quirks)
   const nfsp_engine_cfg& cfg = e0->cfg;
   for (int r = 0; r < R; ++r) NFSP_REQUIRE(g->eng[r]->pending_update, "group replica without a rollout");
   // the trigger plans need every replica's insert counts: one gather, one readback
@@ -1345,9 +1463,10 @@ static int group_update(nfsp_group* g, bool pipelined = false, int par = 0, bool
   const bool shared_cus = g->chain_lds < CHAIN_LDS;
   // The persistent BR kernel (sched.br_persist) instead of the rounds: one launch, one stream,
   // the reference's BR net (k_chain3<1>), no loss log, its 2R chains and BRP_HELPERS helpers a
-  // CU each beside the 2R AR chains (R <= 32, no CU sharing)
+  // CU each beside the 2R AR chains (R <= 32, no CU sharing), and one gamma, lr_br and quirks for
+  // the launch (BrPersistArgs): replicas that differ in them keep the rounds
   const bool persist = g->sched.br_persist && !loss_log && !(cfg.quirks & NFSP_EXT_LINEAR_Q) && R <= 32 &&
-                       !shared_cus;
+                       !shared_cus && g->br_uniform;
   int nbs = g->sched.br_streams > 0 ? g->sched.br_streams : (e0->slices > 1 ? 2 : 1);
   nbs = nbs > GROUP_BR_STREAMS ? GROUP_BR_STREAMS : nbs;
   nbs = nbs > R ? R : nbs;
@@ -1594,8 +1713,8 @@ static int group_update(nfsp_group* g, bool pipelined = false, int par = 0, bool
     if (nt > 0) {
       {
         KTimer kt2(e0, KT_TARGETS, st);
-        k_br_targets<<<dim3((unsigned)rd.rn, (unsigned)nt), 256, 0, st>>>(
-            d_tg + rd.t0, TargetJob{}, cfg.batch, cfg.epochs, cfg.gamma, cfg.quirks, cfg.lr_br);
+        k_br_targets<<<dim3((unsigned)rd.rn, (unsigned)nt), 256, 0, st>>>(d_tg + rd.t0, TargetJob{}, cfg.batch,
+                                                                          cfg.epochs);
       }
       NFSP_LAUNCHED("k_br_targets");
     }

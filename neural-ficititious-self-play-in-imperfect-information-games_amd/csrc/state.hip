@@ -511,8 +511,9 @@ void header_finish(BlobHeader* h, const std::vector<BlobSection>& sec, unsigned 
   memcpy(buf + sizeof(*h), sec.data(), sizeof(BlobSection) * sec.size());
 }
 
-// what a blob's engine payload must share with the engine it is loaded into
-int compat_check(const nfsp_engine* e, const HostRec& hr) {
+// what a blob's engine payload must share with the engine it is loaded into (replica >= 0: a
+// group's replica, named in the message -- its replicas' cfgs may differ from each other)
+int compat_check(const nfsp_engine* e, const HostRec& hr, int replica = -1) {
   const nfsp_engine_cfg &a = e->cfg, &b = hr.cfg;
   const char* f = nullptr;
   if (a.n_lanes != b.n_lanes) f = "n_lanes";
@@ -529,6 +530,9 @@ int compat_check(const nfsp_engine* e, const HostRec& hr) {
   else if (memcmp(&a.gamma, &b.gamma, 8) || memcmp(&a.epsilon, &b.epsilon, 8)) f = "gamma / epsilon";
   else if (a.seed != b.seed) f = "seed";
   else if (e->ctx->game != hr.game) f = "game";
+  if (f && replica >= 0)
+    return nfsp::fail(NFSP_EINVAL, std::string("state blob: replica ") + std::to_string(replica) + ": " + f +
+                                       " differs from the group's replica " + std::to_string(replica));
   if (f) return nfsp::fail(NFSP_EINVAL, std::string("state blob: ") + f + " differs from the engine's");
   return NFSP_OK;
 }
@@ -806,7 +810,7 @@ extern "C" int nfsp_group_load_state(nfsp_group* g, const void* host_buf, int64_
   for (int r = 0; r < G.R; ++r) {
     HostRec hr;
     memcpy(&hr, v.at(v.engine_sec(r)), sizeof(hr));
-    if ((rc = compat_check(G.eng[r], hr)) != NFSP_OK) return rc;
+    if ((rc = compat_check(G.eng[r], hr, r)) != NFSP_OK) return rc;
     NFSP_REQUIRE(!G.eng[r]->pending_update, "nfsp_group_load_state: not at a step boundary");
   }
   if ((rc = group_sync(G)) != NFSP_OK) return rc;

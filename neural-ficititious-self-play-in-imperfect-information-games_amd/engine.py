@@ -309,26 +309,54 @@ class EngineGroup:
     after every slice, shards.AvgPolicyExchange's).  ``slice_lag=2``: every replica's slice j
     acts with the nets slice j - 2 left (a pipelined engine's arithmetic; executed pipelined --
     slice j + 1's rollout, plan and prep overlap slice j's chains -- unless the BR nets are
-    exchanged or ``set_sched(serial=1)``)."""
+    exchanged or ``set_sched(serial=1)``).
 
-    def __init__(self, replicas: int, ctx: native.Context | None = None, init_seed: int = 0,
-                 game: int = native.GAME_LEDUC, avg_ar: bool = False, **cfg):
+    ``cfgs=[dict, ...]`` instead of ``replicas`` and cfg keywords: a heterogeneous group
+    (``nfsp_group_create_v``), one sweep point per replica.  Each dict goes through ``make_cfg``
+    and replica r runs it exactly as given (its seed is not offset) -- bit-identical to
+    ``SelfPlayEngine(init_seed=init_seeds[r], **cfgs[r])``.  The replicas may differ in seed,
+    eta, lr_br, lr_ar, gamma, epsilon, target_every and the quirks outside
+    EXT_LINEAR_Q | EXT_MSE_Q; such a group has no exchange.  ``init_seeds[r]`` seeds replica r's
+    initial nets (default ``init_seed + r``); equal entries give paired initial nets.
+    ``self.cfgs``: every replica's cfg as the group runs it (``nfsp_group_replica_cfg``)."""
+
+    def __init__(self, replicas: int | None = None, ctx: native.Context | None = None, init_seed: int = 0,
+                 game: int = native.GAME_LEDUC, avg_ar: bool = False, cfgs=None, init_seeds=None, **cfg):
+        if cfgs is not None and (replicas is not None or cfg):
+            raise TypeError("EngineGroup: cfgs excludes replicas and cfg keywords (put them in each dict)")
+        if cfgs is None and replicas is None:
+            raise TypeError("EngineGroup: replicas or cfgs")
         self.ctx = ctx if ctx is not None else native.Context(1, game=game)
         self.L = self.ctx.L
-        self.cfg = make_cfg(self.L, **cfg)
+        flags = native.GROUP_AVG_AR if avg_ar else 0
         h = native.P()
-        native.check(self.L.nfsp_group_create(self.ctx.h, C.byref(self.cfg), int(replicas),
-                                              native.GROUP_AVG_AR if avg_ar else 0, C.byref(h)),
-                     "nfsp_group_create")
+        if cfgs is not None:
+            made = [make_cfg(self.L, **dict(c)) for c in cfgs]
+            self.R = len(made)
+            arr = (native.EngineCfg * max(self.R, 1))(*made)
+            self.cfg = made[0] if made else make_cfg(self.L)
+            native.check(self.L.nfsp_group_create_v(self.ctx.h, arr, self.R, flags, C.byref(h)),
+                         "nfsp_group_create_v")
+        else:
+            self.R = int(replicas)
+            self.cfg = make_cfg(self.L, **cfg)
+            native.check(self.L.nfsp_group_create(self.ctx.h, C.byref(self.cfg), self.R, flags, C.byref(h)),
+                         "nfsp_group_create")
         self.h = h
-        self.R = int(replicas)
+        self.cfgs = []
         self.replicas = []
+        if init_seeds is None:
+            init_seeds = [init_seed + r for r in range(self.R)]
+        if len(init_seeds) != self.R:
+            self.close()
+            raise ValueError(f"EngineGroup: {len(init_seeds)} init_seeds for {self.R} replicas")
         for r in range(self.R):
             e = native.P()
             native.check(self.L.nfsp_group_engine(self.h, r, C.byref(e)), "nfsp_group_engine")
-            c = native.EngineCfg.from_buffer_copy(self.cfg)
-            c.seed = self.cfg.seed + r
-            self.replicas.append(SelfPlayEngine(self.ctx, init_seed=init_seed + r, _borrow=(self, e, c)))
+            c = native.EngineCfg()
+            native.check(self.L.nfsp_group_replica_cfg(self.h, r, C.byref(c)), "nfsp_group_replica_cfg")
+            self.cfgs.append(c)
+            self.replicas.append(SelfPlayEngine(self.ctx, init_seed=int(init_seeds[r]), _borrow=(self, e, c)))
 
     def step(self):
         native.check(self.L.nfsp_group_step(self.h), "nfsp_group_step")
@@ -431,16 +459,17 @@ class EngineGroup:
 
     @classmethod
     def from_checkpoint(cls, path, ctx: native.Context | None = None, init_seed: int = 0, **overrides):
-        """A group built from the file's replica count, flags, cfg and game, then loaded from it
-        (``overrides``: slices, slice_lag and sched only)."""
+        """A group built from the file's replica count, flags, every replica's own cfg and the
+        game, then loaded from it (``overrides``: slices, slice_lag and sched only, applied to
+        every replica)."""
         data = np.fromfile(path, dtype=np.uint8)
         info = checkpoint.check(data)
         if info.kind != checkpoint.KIND_GROUP:
             raise native.NativeError("from_checkpoint: the file holds a single engine (SelfPlayEngine.from_checkpoint)")
-        cfg, game = checkpoint.stored_cfg(data, 0)
-        kw = checkpoint.apply_overrides(cfg, overrides)
-        grp = cls(info.replicas, ctx if ctx is not None else native.Context(1, game=game), init_seed=init_seed,
-                  avg_ar=bool(info.group_flags & native.GROUP_AVG_AR), **kw)
+        game = checkpoint.stored_cfg(data, 0)[1]
+        kws = [checkpoint.apply_overrides(checkpoint.stored_cfg(data, r)[0], overrides) for r in range(info.replicas)]
+        grp = cls(ctx=ctx if ctx is not None else native.Context(1, game=game), init_seed=init_seed,
+                  avg_ar=bool(info.group_flags & native.GROUP_AVG_AR), cfgs=kws)
         try:
             checkpoint.load_bytes(grp, data)
         except Exception:

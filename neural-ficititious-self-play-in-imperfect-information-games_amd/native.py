@@ -128,6 +128,9 @@ SIGNATURES = {
     "nfsp_engine_set_update_limit": (I32, [P, I64]),
     "nfsp_engine_snapshot": (I32, [P, I32, PP, P]),
     "nfsp_group_create": (I32, [P, C.POINTER(EngineCfg), I32, U32, C.POINTER(P)]),
+    "nfsp_group_create_v": (I32, [P, C.POINTER(EngineCfg), I32, U32, C.POINTER(P)]),
+    "nfsp_group_cfgs_check": (I32, [C.POINTER(EngineCfg), I32, U32]),
+    "nfsp_group_replica_cfg": (I32, [P, I32, C.POINTER(EngineCfg)]),
     "nfsp_group_destroy": (I32, [P]),
     "nfsp_group_engine": (I32, [P, I32, C.POINTER(P)]),
     "nfsp_group_step": (I32, [P]),
