@@ -71,7 +71,8 @@ __device__ inline floatx4 lds4v(const void* p) { return *(lds_vfloatx4*)p; }
 //   PK_SM  AR softmax: y = e / S and d = y T_M - m for outputs 0 / 1
 //   PK_L2  layer 2: the two sample halves' partial outputs (24 fma -> 12)
 //   PK_O   outputs 0 / 1 of the 4-wave partial sums (8 add -> 4)
-// Kept: BR PK_W, AR PK_W | PK_SM (AR 0.788 -> 0.761 us per SGD step in the microbenchmark).
+// Kept: AR PK_W | PK_SM (AR 0.788 -> 0.761 us per SGD step in the microbenchmark); BR PK_W until
+// the X^T reads moved (NFSP_CH_BR below): with them the packed update breaks the hazard rule.
 // Not kept, because their results were not reproducible:
 //  * PK_L2 in the AR chain (whose Z1 MFMAs are scheduled freely, see the fences in the
 //    step): the weights differed on every run (4e-3 .. 9e-3 from the f32 reference chain
@@ -91,7 +92,7 @@ constexpr unsigned PK_L2 = 1, PK_O = 2, PK_W = 4, PK_SM = 8;
 #define NFSP_PK_AR (PK_W | PK_SM)
 #endif
 #ifndef NFSP_PK_BR
-#define NFSP_PK_BR (PK_W)
+#define NFSP_PK_BR 0
 #endif
 template <int RELU>
 constexpr unsigned chain_pk() { return RELU == 0 ? (NFSP_PK_AR) : (NFSP_PK_BR); }
@@ -106,6 +107,43 @@ constexpr unsigned chain_pk() { return RELU == 0 ? (NFSP_PK_AR) : (NFSP_PK_BR); 
 #ifndef NFSP_CHAIN_G0ROW
 #define NFSP_CHAIN_G0ROW 0
 #endif
+// Where a step's LDS reads sit (chain3_body.inc).  One wave per SIMD issues in order and LDS
+// returns a wave's reads in order, so a read parks the serial chain when its s_waitcnt is reached
+// early, and it delays every read queued behind it.  None of these switches changes an operation
+// or its order: the microbenchmark's weight hashes (tools/bench_chain.hip, 400 updates, 1 and 2
+// blocks, both nets) are the same with every combination measured.
+//   CH_OWN  the lane's row-owned W2 / b2 values are carried in two registers instead of being
+//           read back from LDS every step (the stores stay: other rows and the epilogue read them)
+//   CH_XT2  the X^T reads (ds_read_b64_tr_b16) at the head of the layer-2 arithmetic, after the
+//           Z1^T MFMAs, instead of after the barrier (BR: ahead of the partial sums the loss
+//           waits on) / after the loss (AR: ahead of the dW1 MFMAs).  The ring slot was
+//           published by the previous step's barrier, and ~45 VALU instructions cover the reads
+//   CH_TG2  the targets' read there as well, instead of between the Z1 MFMAs before the barrier
+//   CH_TG   the targets' read at the step top with the fa reads
+//   CH_XT   the X^T reads beside the Z1 MFMAs, between the partial stores and the barrier
+//   CH_XTF  AR with CH_XT: that window fenced with sched_barrier, as the BR chain has it
+//   CH_W2   the W2 / b2 reads of layer 2 and the backward in front of the W split instead of
+//           after it (CH_W2F: pinned there by a sched_barrier)
+// Kept (us per SGD step, 2,000 updates, run-to-run spread 0.001; DESIGN Appendix A.0b has every
+// combination measured -- the parts do not add up, the compiler's schedule moves with each):
+//  * AR CH_OWN | CH_XT2: 0.757 -> 0.738;
+//  * BR CH_OWN | CH_XT2 | CH_TG with the scalar W1 update (NFSP_PK_BR 0): 0.720 -> 0.714.  With
+//    the X^T fragments live from layer 2 to dW1, the register allocator rotates W1 through the
+//    registers of the dz split and the dW1 accumulators, so the packed W1 update wrote MFMA
+//    registers 7-30 wait states after issue -- the packed-f32 rule of tools/mfma_hazards.py.
+//    (CH_OWN | CH_XT2 | CH_TG2 with PK_W measured 0.707, and is not shipped for that reason;
+//    with the dW1 MFMAs' registers held live past the update it is clean and 0.721.)
+// Per chain, as NFSP_PK_*; -DNFSP_CH_AR=<mask> / -DNFSP_CH_BR=<mask> for A/B builds.
+constexpr unsigned CH_OWN = 1, CH_XT = 2, CH_XTF = 4, CH_TG = 8, CH_W2 = 16, CH_XT2 = 32, CH_TG2 = 64,
+                   CH_W2F = 128;
+#ifndef NFSP_CH_AR
+#define NFSP_CH_AR (CH_OWN | CH_XT2)
+#endif
+#ifndef NFSP_CH_BR
+#define NFSP_CH_BR (CH_OWN | CH_XT2 | CH_TG)
+#endif
+template <int RELU>
+constexpr unsigned chain_ch() { return RELU == 0 ? (NFSP_CH_AR) : (NFSP_CH_BR); }
 
 __device__ inline float dpp_f(float x, int ctrl) {
   switch (ctrl) {   // the control word must be an immediate

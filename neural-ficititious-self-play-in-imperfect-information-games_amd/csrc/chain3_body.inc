@@ -85,6 +85,14 @@
   // (tot_rows) instead of the 32-sample total replicated in every lane (tot32: one permlane32 and
   // a copy more); rows g and g ^ 1 hold the same 16 samples, so row 3's total is 2 gb2[0]
   const float own1_sc = g == 3 ? (NFSP_CHAIN_G0ROW ? 0.5f : 0.25f) : 1.0f;
+  // CH_OWN: the lane's two owned values stay in registers across the steps (ov1, ov2: what
+  // publish() and the b2s stores below put into the own1 / own2 slots).  Each lane is the
+  // only writer of the value it holds (the lanes that share a b2 slot compute bit-identical
+  // totals, see `ls`), so the register is what the read-back returned; LDS keeps its copy for
+  // the other rows' reads next step and for the epilogue
+  constexpr unsigned CH = chain_ch<RELU>();
+  float ov1 = g == 3 ? b2_0 : g == 0 ? W2_0 : g == 1 ? W2_2 : W2_1;
+  float ov2 = g < 2 ? b2_1 : b2_2;
 #ifdef NFSP_CHAIN_STAMPS
   unsigned long long st_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last = 0;
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_last)::"memory");
@@ -104,14 +112,20 @@
     const StepRec& R = sm.ring[slot];
     const bf16x8 fa0 = __builtin_bit_cast(bf16x8, R.fa[g][c ^ fsw]);
     const bf16x8 fa1 = __builtin_bit_cast(bf16x8, R.fa[g][(16 + c) ^ fsw]);
-    // X^T, read where each chain measured fastest (tools/chain_ab.sh; results identical):
-    // BR right after the barrier, AR after the loss (round 3: after the dm reads).  Beside the fa reads both were
-    // slower (BR 0.831 -> 0.90 us, bimodal), as was carrying them from the previous step.
+    // X^T, read where each chain measured fastest (results identical): at the head of the
+    // layer-2 arithmetic (CH_XT2, chain3.h).  Without the switches: BR right after the barrier, AR
+    // after the loss (round 3: after the dm reads).  Beside the fa reads both were slower in
+    // round 3 (BR 0.831 -> 0.90 us, bimodal), as was carrying them from the previous step.
     bf16x8 ba0, ba1;
     const char* const rtr = reinterpret_cast<const char*>(&R.fa[0][0]) + tr_off;
+    float4 tg;
+    if constexpr (CH & CH_TG) tg = R.tg[ls];
     // ---- layer 1, both orientations
     bf16x8 whi, wmid, wlo;
-    split3(wr, whi, wmid, wlo, SK);
+    // CH_W2: the reads below come before the W split.  They need no barrier: w2t[w] / b2s[w] are
+    // this wave's own rows, last written by its own-stores at the end of the previous step (or
+    // the prologue), and LDS executes a wave's operations in order
+    if constexpr (!(CH & CH_W2)) split3(wr, whi, wmid, wlo, SK);
     float W2h[4][3];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -122,12 +136,24 @@
     const float W2_0 = w2c[0], W2_1 = w2c[1], W2_2 = w2c[2];
     const floatx4 b2v = lds4(&sm.b2s[w][0]);
     const float b2_0 = b2v[0], b2_1 = b2v[1], b2_2 = b2v[2];
+    if constexpr (CH & CH_W2) {
+      if constexpr (CH & CH_W2F) __builtin_amdgcn_sched_barrier(0);   // pins the reads above the split
+      split3(wr, whi, wmid, wlo, SK);
+    }
     // Z1^T first (layer 2 waits on it); Z1 (needed only by the backward) is issued after
     // layer 2, so its matrix-core time overlaps the barrier wait
     const floatx4 zh0 = mfma3t(whi, wmid, wlo, fa0);     // Z1^T: hidden 16w+4g+r, sample c
     const floatx4 zh1 = mfma3t(whi, wmid, wlo, fa1);     //                      sample 16+c
     __builtin_amdgcn_sched_barrier(0);
     CHAIN_STAMP(0);
+    // CH_XT2 / CH_TG2: ring slot `slot` was published by the previous step's barrier, so X^T and
+    // the targets are readable before this step's; here the layer-2 arithmetic covers the reads,
+    // and the partial sums are the first reads in the LDS queue after the barrier
+    if constexpr (CH & CH_XT2) {
+      ba0 = tr_pair(rtr, rtr + 256);
+      ba1 = tr_pair(rtr + 8, rtr + 264);
+    }
+    if constexpr (CH & CH_TG2) tg = R.tg[ls];
     // ---- layer 2 partial over the slice, from Z1^T
     float p0[3], p1[3];
     if constexpr (PK & PK_L2) {     // the two sample halves as pairs
@@ -172,19 +198,24 @@
       pr[g & 1] = __uint_as_float(r01[0]) + __uint_as_float(r01[1]);
       pr[2] = sum_x16(q[2]);
     }
-    // BR: the Z1 MFMAs and the targets' read fenced between the partial stores and the barrier
-    // (they overlap the barrier wait).  AR: left to the scheduler, which measured faster (AR
-    // 0.810 -> 0.787 us per SGD step; the BR chain unfenced 0.751 -> 0.786; tools/chain_ab.sh,
-    // results identical)
-    if (RELU) __builtin_amdgcn_sched_barrier(0);
+    // BR: the Z1 MFMAs (and, without CH_TG / CH_TG2, the targets' read) fenced between the
+    // partial stores and the barrier (they overlap the barrier wait).  AR: left to the scheduler,
+    // which measured faster (AR 0.810 -> 0.787 us per SGD step; the BR chain unfenced 0.751 ->
+    // 0.786; tools/chain_ab.sh, results identical)
+    constexpr bool fenced = RELU || (CH & CH_XTF);
+    if (fenced) __builtin_amdgcn_sched_barrier(0);
+    if constexpr (CH & CH_XT) {
+      ba0 = tr_pair(rtr, rtr + 256);
+      ba1 = tr_pair(rtr + 8, rtr + 264);
+    }
     const floatx4 zs0 = mfma3(fa0, whi, wmid, wlo);      // Z1: sample 4g+r, hidden 16w+c
     const floatx4 zs1 = mfma3(fa1, whi, wmid, wlo);      //     sample 16+4g+r
-    const float4 tg = R.tg[ls];                          // read before the barrier pins it early
-    if (RELU) __builtin_amdgcn_sched_barrier(0);         // ... and the Z1 MFMAs issue before it
+    if constexpr (!(CH & (CH_TG | CH_TG2))) tg = R.tg[ls];   // read before the barrier pins it early
+    if (fenced) __builtin_amdgcn_sched_barrier(0);       // ... and the Z1 MFMAs issue before it
     CHAIN_STAMP(1);
     __syncthreads();
     CHAIN_STAMP(2);
-    if (RELU) {
+    if (RELU && !(CH & (CH_XT | CH_XT2))) {
       ba0 = tr_pair(rtr, rtr + 256);
       ba1 = tr_pair(rtr + 8, rtr + 264);
     }
@@ -297,7 +328,7 @@
     const float U = tot32_pair(d1, d2);
     CHAIN_STAMP(3);
     // ---- backward in the sample-major layout: samples 16 mt + 4g + r, hidden 16w + c
-    if (!RELU) {
+    if (!RELU && !(CH & (CH_XT | CH_XT2))) {
       ba0 = tr_pair(rtr, rtr + 256);
       ba1 = tr_pair(rtr + 8, rtr + 264);
     }
@@ -334,9 +365,11 @@
     CHAIN_STAMP(4);
     const float lr = lr_step;
     {
-      const float v1 = *own1, v2 = *own2;
-      *own1 = v1 - (lr * own1_sc) * V;
-      *own2 = v2 - lr * U;
+      const float v1 = (CH & CH_OWN) ? ov1 : *own1, v2 = (CH & CH_OWN) ? ov2 : *own2;
+      ov1 = v1 - (lr * own1_sc) * V;
+      ov2 = v2 - lr * U;
+      *own1 = ov1;
+      *own2 = ov2;
     }
     if constexpr (PK & PK_W) {      // W1 -= lr dW1, two rows per instruction
       const floatx2 nl = {-lr, -lr};
