@@ -1,4 +1,5 @@
-// Internals shared by engine.hip (rollout, insert, lifecycle) and learner.hip.
+// Internals shared by engine.hip (rollout, insert, lifecycle), learner.hip (the learner), group.hip
+// (engine groups) and state.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -324,7 +325,7 @@ int group_snap_part_launch(nfsp_engine* const* eng, int R, const void* d_tab, in
                            int r0 = 0);
 // the cross-shard exchange of the AR nets, enqueued on `s` (the AR chain stream)
 int exchange_enqueue(nfsp_engine* e, hipStream_t s);
-// what state.hip saves and restores of an engine group (learner.hip owns nfsp_group)
+// what state.hip saves and restores of an engine group (group.hip owns nfsp_group)
 struct GroupState {
   nfsp_ctx* ctx;
   int R;

@@ -1,5 +1,9 @@
 // The engine's learner (nfsp_engine_update): update_strategy at the reference cadence
 // for the RL/SL inserts of the last rollout.  Reference: agent/agent.py:192-273.
+// This file: the learner's kernels (the BR instantiation of k_chain3 among them: this is the
+// BR chain's translation unit, built with the chain flags), their host launchers
+// (learner_internal.h), and the one-engine learner call.  The engine group's host code, which
+// launches the same kernels through the launchers, is group.hip.
 //
 // An update's inputs (sampled rows, fit permutations, reservoir contents at that moment,
 // DQN targets) do not depend on the weights being trained, except the targets on the
@@ -22,8 +26,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "engine_internal.h"
-#include "chain3.h"
+#include "learner_internal.h"
 
 using nfsp::u32x4;
 namespace nn = nfsp::nn;
@@ -31,28 +34,6 @@ using namespace nfsp::eng;
 using namespace nfsp::chain;
 
 namespace {
-
-struct AgentPlan {
-  int64_t P0;          // agent's RL inserts before the last rollout
-  int64_t m_first;     // first trigger index (trigger m at RL stream position m * c)
-  int64_t U;           // triggers in the last rollout
-  int64_t m_br0;       // first trigger with a BR update (position > batch)
-  int64_t U_br;
-  int64_t n_sl;        // SL records of the last rollout
-  int64_t sl_total0;   // SL inserts before the last rollout
-};
-
-struct PrepArgs {
-  Memories M;
-  LearnBufs LB;
-  EngineDev* st;
-  AgentPlan A[2];
-  int64_t c, rl_cap;
-  int B, E;
-  uint32_t k0, k1, tag;
-  float lr_ar;
-  uint32_t quirks;
-};
 
 // ---------------------------------------------------------------------------
 // BR prep: rows of update u of agent a (agent/agent.py:217 sample_batch)
@@ -271,22 +252,6 @@ __global__ void __launch_bounds__(256) k_res_apply(PrepArgs P0, const PrepArgs* 
 // ---------------------------------------------------------------------------
 // DQN targets of one BR segment (agent/agent.py:219-241), one update per workgroup
 // ---------------------------------------------------------------------------
-// One (engine, agent) segment: the agent's learner buffers (update u of the learner call at
-// index u), the target net, and the segment's update range [u0, u0 + n).
-struct TargetJob {
-  const BrRow* rows;   // [umax][B]
-  const uint8_t* perm; // [umax][E][B]
-  double* expl;        // [umax]
-  StepRec* rec;        // [umax][E][B / 32]
-  const float* tw;     // target net
-  int64_t u0, n;
-  int64_t it0;         // the agent's iteration count before the learner call
-  // the replica's own cfg.gamma / lr_br / quirks: the replicas of a group may differ in them
-  // (nfsp_group_create_v), so they travel with the job, not with the launch
-  double gamma, lr0;
-  unsigned quirks;
-};
-
 // a workgroup-uniform field of a job that arrived in VGPRs, in SGPRs (as brp_uniform's below)
 __device__ __forceinline__ unsigned tj_uniform(unsigned x) { return __builtin_amdgcn_readfirstlane(x); }
 __device__ __forceinline__ double tj_uniform(double x) {
@@ -342,28 +307,8 @@ __device__ __forceinline__ void br_targets_item(const TargetJob J, int64_t bx, i
 // The words that end the loops (a bail, the next item) are read through readfirstlane, so the
 // loops' exits are scalar branches, and a job's fields are made scalar (brp_uniform).
 // ---------------------------------------------------------------------------
-struct BrPersistArgs {
-  ChainArgs C;                  // B, E (the chains' jobs come from seg_job)
-  const ChainJob* seg_job;      // [nseg] chain job of each segment (u0, u1: the segment; sync_to)
-  const TargetJob* seg_tgt;     // [nseg] its targets job
-  const int32_t* seg_chunk0;    // [nseg] its first chunk counter
-  const int32_t* job_seg0;      // [njobs + 1] chain workgroup j's segments: [job_seg0[j], job_seg0[j + 1])
-  uint32_t* slots;              // [nitems] work items (segment << 16 | update in it); BRP_EMPTY until queued
-  uint32_t* ctr;                // [0] helpers' claims, [1] queue reservations
-  uint32_t* chunk_done;         // finished items per chunk
-  int32_t* err;                 // pinned host: [0] a wait expired, [1] chain bails, [2] helper bails
-  int njobs, nitems, chunk;
-  int spin;                     // bound of every wait (s_sleep 8 rounds)
-  double gamma, lr0;
-  unsigned quirks;
-};
 constexpr uint32_t BRP_EMPTY = 0xFFFFFFFFu, BRP_DONE = 0xFFFFFFFEu;
-constexpr int BRP_SPIN = 1 << 18;           // x s_sleep 8 (~56 ms): far past any legitimate wait
-constexpr int BRP_CHUNK = 16;               // updates per chain piece (readiness is checked per piece)
-constexpr int BRP_HELPERS = 48;             // helper workgroups (c4_emul_r8, timeline tool, with
-                                            // the scalar jobs: 96 / 144 / 192 helpers 193.1 /
-                                            // 189.5 / 188.1 ms, the AR chains slowing 155 -> 166;
-                                            // the rounds 179.6)
+static_assert(BRP_EMPTY == nfsp::plan::SLOT_EMPTY, "the host fills the queue (group_plan.h)");
 constexpr int BRP_STATIC_LDS = 16 * 1024;   // bound on the kernel's static LDS (the targets buffers)
 
 #ifdef NFSP_BRP_STAMPS
@@ -512,41 +457,6 @@ __global__ void __launch_bounds__(256) k_br_persist(BrPersistArgs P) {
   }
 }
 
-// launch with a CU per workgroup: dynamic LDS up to what the CU has left beside the kernel's
-// static LDS (the helpers' targets buffers), as the one-engine chains reserve theirs
-int launch_br_persist(const BrPersistArgs& P, int helpers, hipStream_t s) {
-  static std::atomic<uint64_t> mask{0};
-  static std::atomic<int> dyn{0};
-  int dev = 0;
-  NFSP_HIP(hipGetDevice(&dev));
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(mask.load(std::memory_order_acquire) & bit)) {
-    hipFuncAttributes fa{};
-    NFSP_HIP(hipFuncGetAttributes(&fa, (const void*)k_br_persist));
-    if ((int)fa.sharedSizeBytes > BRP_STATIC_LDS) return nfsp::fail(NFSP_EINVAL, "k_br_persist: static LDS");
-    const int d = CHAIN_LDS - BRP_STATIC_LDS;
-    if (d < (int)sizeof(Chain3Smem)) return nfsp::fail(NFSP_EINVAL, "k_br_persist: LDS");
-    NFSP_HIP(hipFuncSetAttribute((const void*)k_br_persist, hipFuncAttributeMaxDynamicSharedMemorySize, d));
-    dyn.store(d, std::memory_order_release);
-    mask.fetch_or(bit, std::memory_order_acq_rel);
-  }
-  k_br_persist<<<P.njobs + helpers, 256, dyn.load(std::memory_order_acquire), s>>>(P);
-  NFSP_LAUNCHED("k_br_persist");
-  return NFSP_OK;
-}
-
-// schedule state after the learner (host-computed values + device-side counters)
-struct FinalArgs {
-  EngineDev* st;
-  const double* br_expl;
-  int64_t umax;
-  int64_t n_rl[2], n_sl[2], U_br[2];
-  int64_t iteration[2], tcount[2], syncs[2];
-  double eps[2], temp[2];
-  float lr[2];
-  int64_t sl_cap;
-};
-
 // mode bits: 1 = the insert counters (both agents; they must be current before the next
 // rollout's commit), 2 << a = agent a's learner results and schedules (after its BR chain)
 template <int TABLE>   // TABLE: engine groups, block = replica of `tab`
@@ -603,6 +513,16 @@ __global__ void __launch_bounds__(256) k_group_xchg(float* const* __restrict__ w
   for (int r = 0; r < R; ++r) war[2 * r + a][q] = nw;
 }
 
+// engine groups: the replicas' EngineDev, gathered for one readback
+__global__ void k_gather_st(EngineDev* const* __restrict__ src, EngineDev* __restrict__ dst, int R) {
+  constexpr int W = (int)(sizeof(EngineDev) / 8);
+  static_assert(sizeof(EngineDev) % 8 == 0, "EngineDev words");
+  for (int i = threadIdx.x; i < R * W; i += blockDim.x) {
+    const int r = i / W, k = i - r * W;
+    reinterpret_cast<uint64_t*>(dst + r)[k] = reinterpret_cast<const uint64_t*>(src[r])[k];
+  }
+}
+
 }  // namespace
 
 #ifdef NFSP_CHAIN_STAMPS
@@ -614,30 +534,12 @@ extern "C" int nfsp_debug_chain_stamps(unsigned long long* out) {
 }
 #endif
 
-namespace {
-
 // ---------------------------------------------------------------------------
-// host side: one learner call = plan (from the rollout's insert counts) + prep launches +
-// chain launches + finalize.  nfsp_engine_update runs them for one engine, the group for
-// R engines with their chains in shared launches.
+// host side (learner_internal.h): the plan of one engine's learner call, its jobs, the launchers
 // ---------------------------------------------------------------------------
-struct Segment {
-  int64_t u, v;        // BR updates [u, v) of the learner call
-  bool sync;           // ends with a target sync
-};
+namespace nfsp {
+namespace eng {
 
-struct LearnPlan {
-  PrepArgs P;
-  int64_t maxU = 0, maxUbr = 0, maxSL = 0;
-  std::vector<Segment> seg[2];
-  int64_t it0[2];
-  FinalArgs F;
-  nfsp_engine::Sched hs;     // the schedules after this call (commit_plan publishes them)
-};
-
-// The learner call's plan from the rollout's insert counts and the host's schedule mirror.
-// Leaves the engine untouched: commit_plan(e, L) adopts it once every plan of the call (a
-// group's replicas) has succeeded, so a failed plan changes no replica's schedules.
 int plan_update(const nfsp_engine* e, const EngineDev& h, LearnPlan& L) {
   const nfsp_engine_cfg& cfg = e->cfg;
   PrepArgs& P = L.P;
@@ -741,45 +643,8 @@ void commit_plan(nfsp_engine* e, const LearnPlan& L) {
   e->pending_update = false;
 }
 
-int launch_br_prep(nfsp_engine* e, const LearnPlan& L, hipStream_t s) {
-  if (L.maxUbr > 0) {
-    k_br_prep<0><<<dim3((unsigned)L.maxUbr, 2), 128, 0, s>>>(L.P, nullptr);
-    NFSP_LAUNCHED("k_br_prep");
-  }
-  if (e->log_loss)                     // NaN = no fit recorded
-    for (int a = 0; a < 2; ++a)
-      NFSP_HIP(hipMemsetAsync(e->LB.br_loss + a * e->LB.umax * e->cfg.epochs, 0xFF,
-                              sizeof(float) * L.P.A[a].U_br * e->cfg.epochs, s));
-  return NFSP_OK;
-}
+static int64_t recs_per_update(const nfsp_engine* e) { return (int64_t)e->cfg.epochs * (e->cfg.batch / CHAIN_MB); }
 
-int launch_ar_prep(nfsp_engine* e, const LearnPlan& L, hipStream_t s) {
-  if (L.maxSL > 0) {
-    k_ar_slots<0><<<dim3(nfsp_blocks(L.maxSL, 256), 2), 256, 0, s>>>(L.P, nullptr);
-    NFSP_LAUNCHED("k_ar_slots");
-  }
-  if (L.maxU > 0) {
-    k_ar_prep<0><<<dim3((unsigned)L.maxU, 2), 128, 0, s>>>(L.P, nullptr);
-    NFSP_LAUNCHED("k_ar_prep");
-  }
-  if (e->log_loss)                     // NaN = no fit recorded (inactive AR update)
-    for (int a = 0; a < 2; ++a)
-      NFSP_HIP(hipMemsetAsync(e->LB.ar_loss + a * e->LB.umax * e->cfg.epochs, 0xFF,
-                              sizeof(float) * L.P.A[a].U * e->cfg.epochs, s));
-  return NFSP_OK;
-}
-
-int launch_res_apply(const LearnPlan& L, hipStream_t s) {
-  if (L.maxSL > 0) {
-    k_res_apply<0><<<dim3(nfsp_blocks(L.maxSL, 256), 2), 256, 0, s>>>(L.P, nullptr);
-    NFSP_LAUNCHED("k_res_apply");
-  }
-  return NFSP_OK;
-}
-
-int64_t recs_per_update(const nfsp_engine* e) { return (int64_t)e->cfg.epochs * (e->cfg.batch / CHAIN_MB); }
-
-// the AR chain of agent a over the whole learner call
 ChainJob ar_job(const nfsp_engine* e, const LearnPlan& L, int a) {
   const int64_t um = e->LB.umax;
   ChainJob j{};
@@ -795,7 +660,6 @@ ChainJob ar_job(const nfsp_engine* e, const LearnPlan& L, int a) {
   return j;
 }
 
-// BR segment g of agent a: its targets and its chain
 TargetJob br_target_job(const nfsp_engine* e, const LearnPlan& L, int a, const Segment& sg) {
   const int64_t um = e->LB.umax, B = e->cfg.batch, E = e->cfg.epochs;
   TargetJob t{};
@@ -827,6 +691,69 @@ ChainJob br_chain_job(const nfsp_engine* e, int a, const Segment& sg) {
   return j;
 }
 
+// ---- launchers.  The device code object lists the template kernels in the order of their first
+// use below -- the <0> prep kernels, the BR chain, k_finalize<0>, then the <1> forms -- so the
+// definitions keep that order.
+
+// the first n0 / n1 updates' epoch losses of the two agents <- NaN (no fit recorded)
+static int clear_loss_log(const nfsp_engine* e, float* loss, int64_t n0, int64_t n1, hipStream_t s) {
+  const int64_t n[2] = {n0, n1};
+  for (int a = 0; a < 2; ++a)
+    NFSP_HIP(hipMemsetAsync(loss + a * e->LB.umax * e->cfg.epochs, 0xFF, sizeof(float) * n[a] * e->cfg.epochs, s));
+  return NFSP_OK;
+}
+
+// launch_prep / launch_prep_table.  TABLE 0: one engine (R 1), its PrepArgs by value; 1: the
+// same prep kernels, every replica in one launch (blockIdx.z = its entry of `tab`)
+template <int TABLE>
+static int launch_prep_t(nfsp_engine* const* eng, const LearnPlan* L, int R, const PrepArgs* tab, hipEvent_t fork_br,
+                         hipEvent_t fork, hipStream_t s) {
+  const PrepArgs one = TABLE ? PrepArgs{} : L[0].P;
+  int64_t maxU = 0, maxUbr = 0, maxSL = 0;
+  for (int r = 0; r < R; ++r) {
+    maxU = L[r].maxU > maxU ? L[r].maxU : maxU;
+    maxUbr = L[r].maxUbr > maxUbr ? L[r].maxUbr : maxUbr;
+    maxSL = L[r].maxSL > maxSL ? L[r].maxSL : maxSL;
+  }
+  const bool loss_log = eng[0]->log_loss;   // a group: on in all replicas or none
+  int rc;
+  if (maxUbr > 0) {
+    k_br_prep<TABLE><<<dim3((unsigned)maxUbr, 2, R), 128, 0, s>>>(one, tab);
+    NFSP_LAUNCHED("k_br_prep");
+  }
+  if (loss_log)
+    for (int r = 0; r < R; ++r)
+      if ((rc = clear_loss_log(eng[r], eng[r]->LB.br_loss, L[r].P.A[0].U_br, L[r].P.A[1].U_br, s)) != NFSP_OK) return rc;
+  NFSP_HIP(hipEventRecord(fork_br, s));
+  if (maxSL > 0) {
+    k_ar_slots<TABLE><<<dim3(nfsp_blocks(maxSL, 256), 2, R), 256, 0, s>>>(one, tab);
+    NFSP_LAUNCHED("k_ar_slots");
+  }
+  if (maxU > 0) {
+    k_ar_prep<TABLE><<<dim3((unsigned)maxU, 2, R), 128, 0, s>>>(one, tab);
+    NFSP_LAUNCHED("k_ar_prep");
+  }
+  if (loss_log)                          // (an inactive AR update records no fit either)
+    for (int r = 0; r < R; ++r)
+      if ((rc = clear_loss_log(eng[r], eng[r]->LB.ar_loss, L[r].P.A[0].U, L[r].P.A[1].U, s)) != NFSP_OK) return rc;
+  NFSP_HIP(hipEventRecord(fork, s));
+  if (maxSL > 0) {
+    k_res_apply<TABLE><<<dim3(nfsp_blocks(maxSL, 256), 2, R), 256, 0, s>>>(one, tab);
+    NFSP_LAUNCHED("k_res_apply");
+  }
+  return NFSP_OK;
+}
+
+int launch_prep(nfsp_engine* e, const LearnPlan& L, hipEvent_t fork_br, hipEvent_t fork, hipStream_t s) {
+  return launch_prep_t<0>(&e, &L, 1, nullptr, fork_br, fork, s);
+}
+
+int launch_br_targets(const TargetJob* jobs, const TargetJob& one, int64_t n, int njobs, int B, int E, hipStream_t s) {
+  k_br_targets<<<dim3((unsigned)n, (unsigned)njobs), 256, 0, s>>>(jobs, one, B, E);
+  NFSP_LAUNCHED("k_br_targets");
+  return NFSP_OK;
+}
+
 int launch_br_chain(const ChainArgs& C, int blocks, unsigned quirks, bool loss_log, hipStream_t s) {
   if (quirks & NFSP_EXT_LINEAR_Q)
     return launch_chain_br_linear(C, blocks, loss_log, (quirks & NFSP_EXT_MSE_Q) != 0, s);
@@ -834,7 +761,69 @@ int launch_br_chain(const ChainArgs& C, int blocks, unsigned quirks, bool loss_l
   return launch_chain<1>(C, blocks, loss_log, s, attr);
 }
 
-}  // namespace
+int launch_br_persist(const BrPersistArgs& P, int helpers, hipStream_t s) {
+  static std::atomic<uint64_t> mask{0};
+  static std::atomic<int> dyn{0};
+  int dev = 0;
+  NFSP_HIP(hipGetDevice(&dev));
+  const uint64_t bit = 1ull << (dev & 63);
+  if (!(mask.load(std::memory_order_acquire) & bit)) {
+    hipFuncAttributes fa{};
+    NFSP_HIP(hipFuncGetAttributes(&fa, (const void*)k_br_persist));
+    if ((int)fa.sharedSizeBytes > BRP_STATIC_LDS) return nfsp::fail(NFSP_EINVAL, "k_br_persist: static LDS");
+    const int d = CHAIN_LDS - BRP_STATIC_LDS;
+    if (d < (int)sizeof(Chain3Smem)) return nfsp::fail(NFSP_EINVAL, "k_br_persist: LDS");
+    NFSP_HIP(hipFuncSetAttribute((const void*)k_br_persist, hipFuncAttributeMaxDynamicSharedMemorySize, d));
+    dyn.store(d, std::memory_order_release);
+    mask.fetch_or(bit, std::memory_order_acq_rel);
+  }
+  k_br_persist<<<P.njobs + helpers, 256, dyn.load(std::memory_order_acquire), s>>>(P);
+  NFSP_LAUNCHED("k_br_persist");
+  return NFSP_OK;
+}
+
+template <int TABLE>
+static int launch_finalize_t(const FinalArgs& F, const FinalArgs* tab, int n, int mode, hipStream_t s) {
+  k_finalize<TABLE><<<n, 64, 0, s>>>(F, tab, mode);
+  NFSP_LAUNCHED("k_finalize");
+  return NFSP_OK;
+}
+
+int launch_finalize(const FinalArgs& F, int mode, hipStream_t s) { return launch_finalize_t<0>(F, nullptr, 1, mode, s); }
+
+int launch_prep_table(nfsp_engine* const* eng, const LearnPlan* L, int R, const PrepArgs* tab, hipEvent_t fork_br,
+                      hipEvent_t fork, hipStream_t s) {
+  return launch_prep_t<1>(eng, L, R, tab, fork_br, fork, s);
+}
+
+int launch_finalize_table(const FinalArgs* tab, int n, int mode, hipStream_t s) {
+  return launch_finalize_t<1>(FinalArgs{}, tab, n, mode, s);
+}
+
+int launch_gather_st(EngineDev* const* src, EngineDev* dst, int R, hipStream_t s) {
+  k_gather_st<<<1, 256, 0, s>>>(src, dst, R);
+  NFSP_LAUNCHED("k_gather_st");
+  return NFSP_OK;
+}
+
+int launch_group_xchg(float* const* wtab, float* w0, int R, unsigned nets, unsigned bcast, float scale, hipStream_t s) {
+  k_group_xchg<<<nfsp_blocks(3 * 2 * nn::NP, 256), 256, 0, s>>>(wtab, w0, R, nets, bcast, scale);
+  NFSP_LAUNCHED("k_group_xchg");
+  return NFSP_OK;
+}
+
+int join_into(nfsp_engine* e, hipStream_t dst, std::initializer_list<hipStream_t> streams) {
+  for (hipStream_t st : streams) {
+    hipEvent_t j = take_event(e);
+    NFSP_HIP(hipEventRecord(j, st));
+    NFSP_HIP(hipStreamWaitEvent(dst, j, 0));
+    e->pool.push_back(j);      // reusable once the wait is enqueued
+  }
+  return NFSP_OK;
+}
+
+}  // namespace eng
+}  // namespace nfsp
 
 // The exchange a pipelined learner call left pending (nfsp_engine_set_exchange), enqueued on
 // the AR stream behind that call's AR chain, then the AR snapshot it feeds and its event.
@@ -879,23 +868,15 @@ static int update_impl(nfsp_engine* e, bool pipelined, int par, bool snap_after)
   const bool xchg = e->xchg_every > 0 && (++e->xchg_calls) % e->xchg_every == 0;
   if (pipelined && snap_after)         // the rollout two slices on acts with this epsilon
     for (int a = 0; a < 2; ++a) e->snap_eps[par][a] = e->hs.epsilon[a];
-  // ---- parallel prep on the ctx stream, in the order the chains need it: the BR rows
-  // first (agent 0's BR segments are the learner's critical path), the BR streams fork;
-  // then the AR records, the AR stream forks; the final reservoir last (only the next
-  // rollout reads it, and it must follow k_ar_prep, which reads the reservoir as it was)
+  // ---- parallel prep on the ctx stream (launch_prep): the BR streams fork behind the BR rows
+  // (agent 0's BR segments are the learner's critical path), the AR stream behind the AR records
   hipEvent_t fork_br = take_event(e), fork = take_event(e);
   {
     KTimer kprep(e, KT_PREP);
-    if ((rc = launch_br_prep(e, L, s)) != NFSP_OK) return rc;
-    NFSP_HIP(hipEventRecord(fork_br, s));
-    if ((rc = launch_ar_prep(e, L, s)) != NFSP_OK) return rc;
-    NFSP_HIP(hipEventRecord(fork, s));
-    if ((rc = launch_res_apply(L, s)) != NFSP_OK) return rc;
+    if ((rc = launch_prep(e, L, fork_br, fork, s)) != NFSP_OK) return rc;
   }
-  if (pipelined) {                     // the counters, before the next rollout's commit
-    k_finalize<0><<<1, 64, 0, s>>>(L.F, nullptr, 1);
-    NFSP_LAUNCHED("k_finalize");
-  }
+  // the counters, before the next rollout's commit
+  if (pipelined && (rc = launch_finalize(L.F, 1, s)) != NFSP_OK) return rc;
   float* snap = e->snap + (size_t)par * 6 * nn::NP;
   // diagnostic (cfg.sched NFSP_SCHED_LEARNER_SERIAL): BR work waits for the AR chains, to time
   // them alone
@@ -912,9 +893,7 @@ static int update_impl(nfsp_engine* e, bool pipelined, int par, bool snap_after)
     if (pipelined && (r = flush_exchange(e)) != NFSP_OK) return r;
     NFSP_HIP(hipStreamWaitEvent(e->s_ar, fork, 0));
     if (L.maxU > 0) {
-      ChainArgs C{};
-      C.B = cfg.batch;
-      C.E = cfg.epochs;
+      ChainArgs C = chain_args(cfg);
       for (int a = 0; a < 2; ++a) {
         C.job[a] = ar_job(e, L, a);
         if (snap_after && !xchg) C.job[a].snap_to = snap + (a * 3 + 0) * nn::NP;   // written by the chain
@@ -951,23 +930,18 @@ static int update_impl(nfsp_engine* e, bool pipelined, int par, bool snap_after)
         const Segment& sg = L.seg[a][gi];
         {
           KTimer kt2(e, KT_TARGETS, sa);
-          k_br_targets<<<(unsigned)(sg.v - sg.u), 256, 0, sa>>>(nullptr, br_target_job(e, L, a, sg),
-                                                                  cfg.batch, cfg.epochs);
+          r = launch_br_targets(nullptr, br_target_job(e, L, a, sg), sg.v - sg.u, 1, cfg.batch, cfg.epochs, sa);
         }
-        NFSP_LAUNCHED("k_br_targets");
-        ChainArgs C{};
-        C.B = cfg.batch;
-        C.E = cfg.epochs;
+        if (r != NFSP_OK) return r;
+        ChainArgs C = chain_args(cfg);
         C.job[0] = br_chain_job(e, a, sg);
         if (snap_after && gi + 1 == L.seg[a].size())            // the last segment writes the snapshot
           C.job[0].snap_to = snap + (a * 3 + 1) * nn::NP;
         KTimer kc(e, KT_CHAIN_BR, sa);
         if ((r = launch_br_chain(C, 1, cfg.quirks, e->log_loss, sa)) != NFSP_OK) return r;
       }
-      if (pipelined) {                   // this agent's learner results, after its chain
-        k_finalize<0><<<1, 64, 0, sa>>>(L.F, nullptr, 2 << a);
-        NFSP_LAUNCHED("k_finalize");
-      }
+      // this agent's learner results, after its chain
+      if (pipelined && (r = launch_finalize(L.F, 2 << a, sa)) != NFSP_OK) return r;
       if (snap_after) {
         if (L.seg[a].empty())             // no BR chain this call: copy the net as it is
           NFSP_HIP(hipMemcpyAsync(snap + (a * 3 + 1) * nn::NP, e->w + (a * 3 + 1) * nn::NP,
@@ -994,26 +968,8 @@ static int update_impl(nfsp_engine* e, bool pipelined, int par, bool snap_after)
   if (ar_done != fork) e->pool.push_back(ar_done);
   if (pipelined) return NFSP_OK;
   // ---- join and publish the schedules
-  for (hipStream_t st : {e->s_ar, e->s_br[0], e->s_br[1]}) {
-    hipEvent_t j = take_event(e);
-    NFSP_HIP(hipEventRecord(j, st));
-    NFSP_HIP(hipStreamWaitEvent(s, j, 0));
-    e->pool.push_back(j);      // reusable once the wait is enqueued
-  }
-  k_finalize<0><<<1, 64, 0, s>>>(L.F, nullptr, 7);
-  NFSP_LAUNCHED("k_finalize");
-  return NFSP_OK;
-}
-
-// the side streams' work so far, joined into the ctx stream
-static int join_streams(nfsp_engine* e) {
-  for (hipStream_t st : {e->s_ar, e->s_br[0], e->s_br[1]}) {
-    hipEvent_t j = take_event(e);
-    NFSP_HIP(hipEventRecord(j, st));
-    NFSP_HIP(hipStreamWaitEvent(e->ctx->stream, j, 0));
-    e->pool.push_back(j);
-  }
-  return NFSP_OK;
+  if ((rc = join_into(e, s, {e->s_ar, e->s_br[0], e->s_br[1]})) != NFSP_OK) return rc;
+  return launch_finalize(L.F, 7, s);
 }
 
 extern "C" int nfsp_engine_update(nfsp_engine* e) {
@@ -1049,736 +1005,10 @@ int step_pipelined(nfsp_engine* e) {
     if ((rc = update_impl(e, true, par, j + 2 < K)) != NFSP_OK) return rc;
   }
   if ((rc = flush_exchange(e)) != NFSP_OK) return rc;    // the last slice's
-  return join_streams(e);
+  return join_into(e, s, {e->s_ar, e->s_br[0], e->s_br[1]});   // the side streams' work so far
 }
 }  // namespace eng
 }  // namespace nfsp
-
-// ---------------------------------------------------------------------------
-// Engine groups (nfsp_group_*): R replicas stepped together, their chains in shared launches
-// ---------------------------------------------------------------------------
-constexpr int GROUP_BR_STREAMS = 4;   // at most; nfsp_group_sched.br_streams (group_update)
-
-struct nfsp_group {
-  nfsp_ctx* ctx = nullptr;
-  int R = 0;
-  unsigned flags = 0;
-  // nfsp_group_create_v: some replica's cfg differs from replica 0's in more than the seed (no
-  // exchange then); br_uniform: gamma, lr_br and quirks are the same everywhere (k_br_persist's
-  // launch-wide BrPersistArgs carry one of each)
-  bool hetero = false, br_uniform = true;
-  std::vector<nfsp_engine*> eng;
-  hipStream_t s_ar = nullptr, s_br = nullptr;
-  // further BR streams: a sliced group's BR jobs run in up to GROUP_BR_STREAMS partitions,
-  // each its own rounds on its own stream (partition 0 on s_br); created on first use, so a
-  // group with one partition holds no extra stream (and no extra hardware queue)
-  hipStream_t s_brp[GROUP_BR_STREAMS - 1] = {};
-  void* d_roll = nullptr;        // the replicas' rollout arguments (static device table)
-  // per learner call: job / prep / final tables, host (pinned) staging -> device, one copy;
-  // two sets by slice parity (a pipelined step's slice j + 1 fills its set while slice j's
-  // chains still read theirs)
-  char* h_tab[2] = {nullptr, nullptr};
-  char* d_tab[2] = {nullptr, nullptr};
-  size_t tab_cap[2] = {0, 0};
-  hipEvent_t snap_ev[2][2] = {};  // pipelined step: [parity][AR, BR stream] snapshot copies done
-  // the replicas' EngineDev, gathered on device and read back in one copy
-  EngineDev** d_stp = nullptr;   // [R] -> each replica's state
-  EngineDev* d_st = nullptr;     // [R]
-  EngineDev* h_st = nullptr;     // [R] pinned
-  float** d_war = nullptr;       // [3 nets][R][2] weight pointers (k_group_xchg)
-  float* w0 = nullptr;           // [3][2][NP] the exchanged nets after the last exchange
-  unsigned w0_valid = 0;         // nets (NFSP_XCHG_*) broadcast from replica 0 already
-  unsigned xchg_nets = 0;        // nfsp_group_set_exchange
-  int xchg_every = 0;
-  float xchg_scale = 1.f;
-  int64_t calls = 0;             // learner calls (slices) so far
-  int64_t rounds = 0;            // BR rounds of the last learner call (stats)
-  nfsp_group_sched sched{};      // nfsp_group_set_sched (from nfsp_group_default_sched)
-  int32_t* h_err = nullptr;      // k_br_persist's bail flags (pinned host, mapped): group_check_err
-  int chain_lds = 0;             // LDS per chain workgroup: 4R chains on the device's CUs
-  bool trace_on = false;         // nfsp_group_set_trace: per call [R][2][AR, BR] update counts
-  std::vector<int32_t> trace;
-};
-
-namespace {
-__global__ void k_gather_st(EngineDev* const* __restrict__ src, EngineDev* __restrict__ dst, int R) {
-  constexpr int W = (int)(sizeof(EngineDev) / 8);
-  static_assert(sizeof(EngineDev) % 8 == 0, "EngineDev words");
-  for (int i = threadIdx.x; i < R * W; i += blockDim.x) {
-    const int r = i / W, k = i - r * W;
-    reinterpret_cast<uint64_t*>(dst + r)[k] = reinterpret_cast<const uint64_t*>(src[r])[k];
-  }
-}
-}  // namespace
-
-extern "C" int nfsp_group_destroy(nfsp_group* g) {
-  if (!g) return NFSP_OK;
-  if (g->ctx) (void)hipStreamSynchronize(g->ctx->stream);
-  for (hipStream_t st : {g->s_ar, g->s_br})
-    if (st) (void)hipStreamSynchronize(st);
-  for (hipStream_t st : g->s_brp)
-    if (st) (void)hipStreamSynchronize(st);
-  for (nfsp_engine* e : g->eng) nfsp_engine_destroy(e);
-  for (int p = 0; p < 2; ++p) {
-    if (g->h_tab[p]) (void)hipHostFree(g->h_tab[p]);
-    if (g->d_tab[p]) (void)hipFree(g->d_tab[p]);
-    for (hipEvent_t ev : g->snap_ev[p])
-      if (ev) (void)hipEventDestroy(ev);
-  }
-  if (g->h_st) (void)hipHostFree(g->h_st);
-  if (g->h_err) (void)hipHostFree(g->h_err);
-  for (void* p : {(void*)g->d_war, (void*)g->w0, g->d_roll, (void*)g->d_stp, (void*)g->d_st})
-    if (p) (void)hipFree(p);
-  for (hipStream_t st : {g->s_ar, g->s_br})
-    if (st) (void)hipStreamDestroy(st);
-  for (hipStream_t st : g->s_brp)
-    if (st) (void)hipStreamDestroy(st);
-  delete g;
-  return NFSP_OK;
-}
-
-namespace {
-// The fields the replicas of a group must share: the shapes of the shared launches (lanes,
-// slices, batch, epochs and the learner buffers sized from them), the memories' sizes, the
-// schedule flags, and the two quirk bits that select the BR chain kernel of a shared launch
-// (k_chain3<1 / 2 / 3>).  The first one in which b differs from a, or nullptr.
-constexpr uint32_t GROUP_UNIFORM_QUIRKS = NFSP_EXT_LINEAR_Q | NFSP_EXT_MSE_Q;
-const char* group_uniform_diff(const nfsp_engine_cfg& a, const nfsp_engine_cfg& b) {
-  if (a.n_lanes != b.n_lanes) return "n_lanes";
-  if (a.hidden != b.hidden) return "hidden";
-  if (a.rl_capacity != b.rl_capacity) return "rl_capacity";
-  if (a.sl_capacity != b.sl_capacity) return "sl_capacity";
-  if (a.batch != b.batch) return "batch";
-  if (a.inserts_per_update != b.inserts_per_update) return "inserts_per_update";
-  if (a.epochs != b.epochs) return "epochs";
-  if (a.fit_batch != b.fit_batch) return "fit_batch";
-  if (a.slices != b.slices) return "slices";
-  if (a.slice_lag != b.slice_lag) return "slice_lag";
-  if (a.sched != b.sched) return "sched";
-  if ((a.quirks ^ b.quirks) & GROUP_UNIFORM_QUIRKS) return "quirks (NFSP_EXT_LINEAR_Q | NFSP_EXT_MSE_Q)";
-  return nullptr;
-}
-// The fields that may differ, the seed apart (bit patterns: -0.0 and 0.0 are different cfgs, as
-// in a state blob's comparison): the first one in which b differs from a, or nullptr.
-const char* group_free_diff(const nfsp_engine_cfg& a, const nfsp_engine_cfg& b) {
-  if (memcmp(&a.eta, &b.eta, sizeof(float))) return "eta";
-  if (memcmp(&a.lr_br, &b.lr_br, sizeof(float))) return "lr_br";
-  if (memcmp(&a.lr_ar, &b.lr_ar, sizeof(float))) return "lr_ar";
-  if (memcmp(&a.gamma, &b.gamma, sizeof(double))) return "gamma";
-  if (memcmp(&a.epsilon, &b.epsilon, sizeof(double))) return "epsilon";
-  if (a.target_every != b.target_every) return "target_every";
-  if (a.quirks != b.quirks) return "quirks";
-  return nullptr;
-}
-bool group_br_same(const nfsp_engine_cfg& a, const nfsp_engine_cfg& b) {
-  return !memcmp(&a.gamma, &b.gamma, sizeof(double)) && !memcmp(&a.lr_br, &b.lr_br, sizeof(float)) &&
-         a.quirks == b.quirks;
-}
-
-// nfsp_group_cfgs_check's rules; hetero / br_uniform (may be null): see nfsp_group
-int group_cfgs_scan(const nfsp_engine_cfg* cfgs, int replicas, unsigned flags, bool* hetero, bool* br_uniform) {
-  NFSP_REQUIRE(cfgs, "null argument");
-  NFSP_REQUIRE(replicas >= 1 && replicas <= NFSP_GROUP_MAX_REPLICAS, "replicas must be in [1, 256]");
-  NFSP_REQUIRE((flags & ~NFSP_GROUP_AVG_AR) == 0, "unknown group flags");
-  bool het = false, bru = true;
-  for (int r = 0; r < replicas; ++r) {
-    if (const char* f = group_uniform_diff(cfgs[0], cfgs[r]))
-      return nfsp::fail(NFSP_EINVAL, std::string("group cfgs: ") + f + " of replica " + std::to_string(r) +
-                                         " differs from replica 0's (the replicas of a group share it)");
-    if (nfsp::eng::engine_cfg_check(&cfgs[r]) != NFSP_OK)
-      return nfsp::fail(NFSP_EINVAL, "group cfgs: replica " + std::to_string(r) + ": " + nfsp_last_error());
-    const char* d = group_free_diff(cfgs[0], cfgs[r]);
-    if (d && (flags & NFSP_GROUP_AVG_AR))
-      return nfsp::fail(NFSP_EINVAL, std::string("group cfgs: NFSP_GROUP_AVG_AR on a heterogeneous group (") + d +
-                                         " of replica " + std::to_string(r) +
-                                         " differs from replica 0's): nets trained under different "
-                                         "hyperparameters are not averaged");
-    het = het || d != nullptr;
-    bru = bru && group_br_same(cfgs[0], cfgs[r]);
-  }
-  if (hetero) *hetero = het;
-  if (br_uniform) *br_uniform = bru;
-  return NFSP_OK;
-}
-}  // namespace
-
-extern "C" int nfsp_group_cfgs_check(const nfsp_engine_cfg* cfgs, int replicas, unsigned flags) {
-  return group_cfgs_scan(cfgs, replicas, flags, nullptr, nullptr);
-}
-
-extern "C" int nfsp_group_create(nfsp_ctx* ctx, const nfsp_engine_cfg* cfg, int replicas, unsigned flags,
-                                 nfsp_group** out) {
-  NFSP_REQUIRE(ctx && cfg && out, "null argument");
-  NFSP_REQUIRE(replicas >= 1 && replicas <= NFSP_GROUP_MAX_REPLICAS, "replicas must be in [1, 256]");
-  std::vector<nfsp_engine_cfg> cfgs((size_t)replicas, *cfg);
-  for (int r = 0; r < replicas; ++r) cfgs[r].seed = cfg->seed + (uint64_t)r;
-  return nfsp_group_create_v(ctx, cfgs.data(), replicas, flags, out);
-}
-
-extern "C" int nfsp_group_replica_cfg(nfsp_group* g, int replica, nfsp_engine_cfg* out) {
-  NFSP_REQUIRE(g && out && replica >= 0 && replica < g->R, "bad argument");
-  *out = g->eng[replica]->cfg;
-  return NFSP_OK;
-}
-
-extern "C" int nfsp_group_create_v(nfsp_ctx* ctx, const nfsp_engine_cfg* cfgs, int replicas, unsigned flags,
-                                   nfsp_group** out) {
-  NFSP_REQUIRE(ctx && cfgs && out, "null argument");
-  bool hetero = false, br_uniform = true;
-  int ck = group_cfgs_scan(cfgs, replicas, flags, &hetero, &br_uniform);
-  if (ck != NFSP_OK) return ck;
-  const nfsp_engine_cfg* cfg = &cfgs[0];   // the fields every replica shares
-  *out = nullptr;
-  // up to 4R chain workgroups run at once (2R AR + a BR round's 2R): past one per CU they
-  // share CUs, each with an equal share of the LDS
-  int dev = 0, cus = 0;
-  NFSP_HIP(hipGetDevice(&dev));
-  NFSP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  nfsp_group* g = new nfsp_group();
-  g->ctx = ctx;
-  g->R = replicas;
-  g->flags = flags;
-  g->hetero = hetero;
-  g->br_uniform = br_uniform;
-  if (flags & NFSP_GROUP_AVG_AR) {     // the per-step AR exchange
-    g->xchg_nets = NFSP_XCHG_AR;
-    g->xchg_every = cfg->slices;
-    g->xchg_scale = 1.0f / (float)replicas;
-  }
-  g->chain_lds = chain_lds_shared((4 * replicas + cus - 1) / (cus > 0 ? cus : 1));
-  nfsp_group_default_sched(&g->sched);
-  for (int r = 0; r < replicas; ++r) {
-    nfsp_engine* e = nullptr;
-    const int rc = nfsp::eng::engine_create(ctx, &cfgs[r], false, &e);
-    if (rc != NFSP_OK) {
-      nfsp_group_destroy(g);
-      return rc;
-    }
-    g->eng.push_back(e);
-  }
-  for (hipStream_t* st : {&g->s_ar, &g->s_br}) {
-    const hipError_t sr = hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-    if (sr != hipSuccess) {
-      nfsp_group_destroy(g);
-      return nfsp::hip_fail(sr, "nfsp_group_create: hipStreamCreate");
-    }
-  }
-  for (auto& pe : g->snap_ev)
-    for (hipEvent_t& ev : pe) {
-      const hipError_t er = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-      if (er != hipSuccess) {
-        nfsp_group_destroy(g);
-        return nfsp::hip_fail(er, "nfsp_group_create: hipEventCreate");
-      }
-    }
-  int rc = nfsp::eng::group_rollout_table(g->eng.data(), replicas, &g->d_roll);
-  if (rc != NFSP_OK) {
-    nfsp_group_destroy(g);
-    return rc;
-  }
-  std::vector<float*> war(3 * 2 * replicas);
-  std::vector<EngineDev*> stp(replicas);
-  for (int r = 0; r < replicas; ++r) {
-    for (int n = 0; n < 3; ++n)
-      for (int a = 0; a < 2; ++a) war[((size_t)n * replicas + r) * 2 + a] = g->eng[r]->w + (a * 3 + n) * nn::NP;
-    stp[r] = g->eng[r]->st;
-  }
-  hipError_t r = hipMalloc((void**)&g->d_war, sizeof(float*) * war.size());
-  if (r == hipSuccess) r = hipMalloc((void**)&g->w0, sizeof(float) * 3 * 2 * nn::NP);
-  if (r == hipSuccess) r = hipMemcpy(g->d_war, war.data(), sizeof(float*) * war.size(), hipMemcpyHostToDevice);
-  if (r == hipSuccess) r = hipMalloc((void**)&g->d_stp, sizeof(EngineDev*) * replicas);
-  if (r == hipSuccess) r = hipMalloc((void**)&g->d_st, sizeof(EngineDev) * replicas);
-  if (r == hipSuccess) r = hipHostMalloc((void**)&g->h_st, sizeof(EngineDev) * replicas, hipHostMallocDefault);
-  if (r == hipSuccess) r = hipHostMalloc((void**)&g->h_err, sizeof(int32_t) * 4, hipHostMallocMapped | hipHostMallocCoherent);
-  if (r == hipSuccess) memset(g->h_err, 0, sizeof(int32_t) * 4);
-  if (r == hipSuccess) r = hipMemcpy(g->d_stp, stp.data(), sizeof(EngineDev*) * replicas, hipMemcpyHostToDevice);
-  if (r != hipSuccess) {
-    nfsp_group_destroy(g);
-    return nfsp::hip_fail(r, "nfsp_group_create");
-  }
-  *out = g;
-  return NFSP_OK;
-}
-
-namespace nfsp {
-namespace eng {
-int group_state(nfsp_group* g, GroupState* out) {
-  NFSP_REQUIRE(g && out, "null argument");
-  *out = GroupState{};
-  out->ctx = g->ctx;
-  out->R = g->R;
-  out->flags = g->flags;
-  out->eng = g->eng.data();
-  out->w0 = g->w0;
-  out->w0_valid = &g->w0_valid;
-  out->calls = &g->calls;
-  out->xchg_every = g->xchg_every;
-  out->streams[out->n_streams++] = g->s_ar;
-  out->streams[out->n_streams++] = g->s_br;
-  for (hipStream_t st : g->s_brp) out->streams[out->n_streams++] = st;
-  return NFSP_OK;
-}
-}  // namespace eng
-}  // namespace nfsp
-
-extern "C" int nfsp_group_engine(nfsp_group* g, int r, nfsp_engine** out) {
-  NFSP_REQUIRE(g && out && r >= 0 && r < g->R, "bad argument");
-  *out = g->eng[r];
-  return NFSP_OK;
-}
-
-// the group's exchange (k_group_xchg) on stream `s`
-static int group_xchg_launch(nfsp_group* g, hipStream_t s) {
-  const unsigned nets = g->xchg_nets ? g->xchg_nets : NFSP_XCHG_AR;
-  // nets not broadcast yet take replica 0's (a BR net with its target net)
-  unsigned bc = nets & ~g->w0_valid;
-  if (bc & NFSP_XCHG_BR) bc |= 4u;
-  const float scale = g->xchg_nets ? g->xchg_scale : 1.0f / (float)g->R;
-  k_group_xchg<<<nfsp_blocks(3 * 2 * nn::NP, 256), 256, 0, s>>>(g->d_war, g->w0, g->R, nets, bc, scale);
-  NFSP_LAUNCHED("k_group_xchg");
-  g->w0_valid |= nets;
-  return NFSP_OK;
-}
-
-extern "C" int nfsp_group_average_ar(nfsp_group* g) {
-  NFSP_REQUIRE(g, "null argument");
-  NFSP_REQUIRE(!g->hetero,
-               "nfsp_group_average_ar: the replicas' cfgs differ (a heterogeneous group has no exchange)");
-  return group_xchg_launch(g, g->ctx->stream);
-}
-
-extern "C" int nfsp_group_set_exchange(nfsp_group* g, unsigned nets, int every, float scale) {
-  NFSP_REQUIRE(g, "null argument");
-  NFSP_REQUIRE((nets & ~(NFSP_XCHG_AR | NFSP_XCHG_BR)) == 0, "nets: NFSP_XCHG_AR | NFSP_XCHG_BR");
-  NFSP_REQUIRE(every >= 0 && (every == 0 || nets), "every >= 0 (and nets when on)");
-  NFSP_REQUIRE(every == 0 || !g->hetero,
-               "nfsp_group_set_exchange: the replicas' cfgs differ (a heterogeneous group has no exchange)");
-  // a net this call turns on starts like the rank path's (AvgPolicyExchange broadcasts rank 0's
-  // nets, then nfsp_engine_set_exchange takes them as W0): its next exchange copies replica 0's
-  // net everywhere instead of applying deltas against a W0 from before the exchange was off
-  const unsigned on = every ? nets : 0;
-  g->w0_valid &= ~(on & ~g->xchg_nets);
-  g->xchg_nets = on;
-  g->xchg_every = every;
-  g->xchg_scale = scale;
-  g->calls = 0;
-  return NFSP_OK;
-}
-
-// bump-allocate n items of T in the host / device table pair (8-byte aligned offsets)
-struct TabCursor {
-  size_t off = 0;
-  template <class T>
-  size_t take(size_t n) {
-    const size_t o = (off + 15) & ~(size_t)15;
-    off = o + sizeof(T) * n;
-    return o;
-  }
-};
-
-// One learner call of every replica for their pending rollouts.  par: the learner-buffer and
-// table set (slice parity; 0 unless pipelined).  pipelined (nfsp_group_step at slice_lag 2):
-// nothing joins the ctx stream -- the counters are published on it after the prep, the BR
-// results on the BR stream after the last round; the exchange (when due) follows the AR chains
-// on the AR stream; with snap_after each learner stream then copies its nets into snapshot
-// `par` and records snap_ev[par] for the rollout two slices on.
-// k_br_persist's bounded waits: a hand-off that never came ended that kernel with a bail flag
-// set (pinned host memory).  Checked once the kernel has completed: after a learner call's
-// readback sync (the ctx stream has then waited for every earlier slice's BR stream) and by
-// nfsp_group_check (which synchronises first).
-static int group_check_err(nfsp_group* g) {
-  volatile int32_t* h = g->h_err;
-  if (!h || !h[0]) return NFSP_OK;
-  const int cb = h[1], hb = h[2];
-  h[0] = h[1] = h[2] = 0;
-  return nfsp::fail(NFSP_EHIP, "k_br_persist: a bounded wait expired (work-queue hand-off): chain bails " +
-                                   std::to_string(cb) + ", helper bails " + std::to_string(hb));
-}
-
-static int group_update(nfsp_group* g, bool pipelined = false, int par = 0, bool snap_after = false) {
-  hipStream_t s = g->ctx->stream;
-  const int R = g->R;
-  nfsp_engine* e0 = g->eng[0];
-  // replica 0's cfg stands for the fields every replica shares (batch, epochs, the LINEAR_Q /
-  // MSE_Q quirk bits; group_uniform_diff).  What may differ -- target_every, lr_*, gamma, epsilon,
-  // eta, the other quirks, the seed -- is read from each replica's own cfg: by plan_update (the
-  // segments and schedules, PrepArgs) and br_target_job (the targets' gamma, lr0, quirks)
-  const nfsp_engine_cfg& cfg = e0->cfg;
-  for (int r = 0; r < R; ++r) NFSP_REQUIRE(g->eng[r]->pending_update, "group replica without a rollout");
-  // the trigger plans need every replica's insert counts: one gather, one readback
-  k_gather_st<<<1, 256, 0, s>>>(g->d_stp, g->d_st, R);
-  NFSP_LAUNCHED("k_gather_st");
-  NFSP_HIP(hipMemcpyAsync(g->h_st, g->d_st, sizeof(EngineDev) * R, hipMemcpyDeviceToHost, s));
-  NFSP_HIP(hipStreamSynchronize(s));
-  int rc;
-  if ((rc = group_check_err(g)) != NFSP_OK) return rc;
-  KTimer kt(e0, KT_LEARNER);
-  std::vector<LearnPlan> L(R);
-  int64_t maxU = 0, maxUbr = 0, maxSL = 0;
-  const bool loss_log = e0->log_loss;
-  for (int r = 0; r < R; ++r) {
-    nfsp_engine* e = g->eng[r];
-    NFSP_REQUIRE(e->log_loss == loss_log, "the loss log must be on in all replicas of a group or none");
-    e->LB = e->LBs[par];
-    if ((rc = plan_update(e, g->h_st[r], L[r])) != NFSP_OK) return rc;
-    maxU = L[r].maxU > maxU ? L[r].maxU : maxU;
-    maxUbr = L[r].maxUbr > maxUbr ? L[r].maxUbr : maxUbr;
-    maxSL = L[r].maxSL > maxSL ? L[r].maxSL : maxSL;
-  }
-  // every plan succeeded: the rollouts are consumed and the schedules advance (a failed
-  // plan leaves every replica as it was -- pending, schedules untouched -- so they stay in step)
-  for (int r = 0; r < R; ++r) commit_plan(g->eng[r], L[r]);
-  if (g->trace_on)
-    for (int r = 0; r < R; ++r)
-      for (int a = 0; a < 2; ++a) {
-        g->trace.push_back((int32_t)L[r].P.A[a].U);
-        g->trace.push_back((int32_t)L[r].P.A[a].U_br);
-      }
-  // ---- tables: prep / final args per replica; the AR chains (2R workgroups, one launch);
-  // per BR round k the targets and the chain of every (replica, agent) with a k-th segment
-  std::vector<ChainJob> ar_jobs;
-  for (int r = 0; r < R; ++r)
-    for (int a = 0; a < 2; ++a)
-      if (L[r].P.A[a].U > 0) ar_jobs.push_back(ar_job(g->eng[r], L[r], a));
-  // BR rounds: round k = one k_br_targets launch (the targets of the segments that start in
-  // it, whole segments) + one chain launch (every (replica, agent) with BR work left: the next
-  // piece of its current segment, at most `cap` updates; a target sync ends the last piece of
-  // its segment).  cap 0: one round per segment index, every job's k-th segment in round k.
-  // A round lasts as long as its longest piece, so with whole segments the round structure
-  // waits for the longest segment of every round: a sliced group's BR stream ran 1.9 ms per
-  // slice against 1.2 ms for its busiest job (tools/group_timeline.py).  Pieces of a segment
-  // resume from the weights in memory: the same SGD steps, bit for bit.
-  const int64_t cap = g->sched.br_cap >= 0 ? g->sched.br_cap : (e0->slices > 1 ? 40 : 0);
-  const bool pace_br = g->sched.br_pace != 0;
-  // Partitions: replicas [pr0[p], pr0[p + 1]) are partition p, whose BR jobs run their own
-  // rounds on their own stream, followed (pipelined) by the partition's BR results and BR
-  // snapshot on that stream.  A round then waits only for the longest piece among its
-  // partition's jobs, and one partition's targets overlap the others' chains.  Partitions
-  // 1.. go on into the next slice without waiting for the others; partition 0 runs on s_br,
-  // which joins every partition at the end of the call (below), so its next-slice rounds wait
-  // for the slowest partition: the overlap is asymmetric.  Each job's pieces and targets are
-  // the same as with one partition, so are its SGD steps.  Sliced groups only (their rounds
-  // are short: the targets between them were ~10% of c4_emul_r8's BR stream); groups whose
-  // chains share CUs keep one stream.
-  const bool shared_cus = g->chain_lds < CHAIN_LDS;
-  // The persistent BR kernel (sched.br_persist) instead of the rounds: one launch, one stream,
-  // the reference's BR net (k_chain3<1>), no loss log, its 2R chains and BRP_HELPERS helpers a
-  // CU each beside the 2R AR chains (R <= 32, no CU sharing), and one gamma, lr_br and quirks for
-  // the launch (BrPersistArgs): replicas that differ in them keep the rounds
-  const bool persist = g->sched.br_persist && !loss_log && !(cfg.quirks & NFSP_EXT_LINEAR_Q) && R <= 32 &&
-                       !shared_cus && g->br_uniform;
-  int nbs = g->sched.br_streams > 0 ? g->sched.br_streams : (e0->slices > 1 ? 2 : 1);
-  nbs = nbs > GROUP_BR_STREAMS ? GROUP_BR_STREAMS : nbs;
-  nbs = nbs > R ? R : nbs;
-  if (shared_cus || persist) nbs = 1;
-  struct BrCursor {
-    int r, a;
-    size_t s;        // current segment
-    int64_t pos;     // next update of it
-  };
-  struct BrRound {
-    int p;                   // partition (stream)
-    size_t b0, b1, t0, t1;   // its chain jobs / target jobs in br_jobs / tg_jobs
-    int64_t rn;              // the longest segment starting in it (targets grid)
-  };
-  std::vector<ChainJob> br_jobs;
-  std::vector<TargetJob> tg_jobs;
-  std::vector<BrRound> rounds_v;
-  int pr0[GROUP_BR_STREAMS + 1];
-  for (int p = 0; p <= nbs; ++p) pr0[p] = p * R / nbs;
-  int64_t max_rounds = 0;
-  for (int p = 0; p < (persist ? 0 : nbs); ++p) {
-    std::vector<BrCursor> bc;
-    for (int r = pr0[p]; r < pr0[p + 1]; ++r)
-      for (int a = 0; a < 2; ++a)
-        if (!L[r].seg[a].empty()) bc.push_back({r, a, 0, L[r].seg[a][0].u});
-    // Paced pieces (capped groups): the partition's busiest job (most BR updates in this call)
-    // splits each of its segments into equal pieces of at most `cap`, and in every round the
-    // other jobs take at most the busiest job's piece of that round, so no round outlasts the
-    // busiest job's own piece and its last piece of a segment is not a short one.  (Plain caps:
-    // a 150-update segment ran as 40 + 40 + 40 + 30, and every job's round took 40.)
-    std::vector<int64_t> pace;                 // the busiest job's piece per round
-    if (cap > 0 && pace_br) {
-      int64_t most = -1;
-      const std::vector<Segment>* bs = nullptr;
-      for (const BrCursor& c : bc) {
-        int64_t n = 0;
-        for (const Segment& sg : L[c.r].seg[c.a]) n += sg.v - sg.u;
-        if (n > most) most = n, bs = &L[c.r].seg[c.a];
-      }
-      if (bs)
-        for (const Segment& sg : *bs) {
-          const int64_t len = sg.v - sg.u, np = (len + cap - 1) / cap;
-          for (int64_t k = 0; k < np; ++k) pace.push_back(len / np + (k < len % np ? 1 : 0));
-        }
-    }
-    int64_t nr = 0;
-    for (;;) {
-      const size_t b0 = br_jobs.size(), t0 = tg_jobs.size();
-      int64_t rn = 0;
-      const int64_t pk = (size_t)nr < pace.size() ? pace[(size_t)nr] : cap;
-      for (BrCursor& c : bc) {
-        const std::vector<Segment>& segs = L[c.r].seg[c.a];
-        if (c.s >= segs.size()) continue;
-        const Segment& sg = segs[c.s];
-        if (c.pos == sg.u) {
-          tg_jobs.push_back(br_target_job(g->eng[c.r], L[c.r], c.a, sg));
-          rn = sg.v - sg.u > rn ? sg.v - sg.u : rn;
-        }
-        const int64_t end = pk > 0 && c.pos + pk < sg.v ? c.pos + pk : sg.v;
-        br_jobs.push_back(br_chain_job(g->eng[c.r], c.a, Segment{c.pos, end, sg.sync && end == sg.v}));
-        c.pos = end;
-        if (end == sg.v && ++c.s < segs.size()) c.pos = segs[c.s].u;
-      }
-      if (br_jobs.size() == b0) break;
-      rounds_v.push_back({p, b0, br_jobs.size(), t0, tg_jobs.size(), rn});
-      ++nr;
-    }
-    max_rounds = nr > max_rounds ? nr : max_rounds;
-  }
-  // k_br_persist's tables: each segment's chain and targets jobs, its chunk counters, and the
-  // work queue holding the first segments' items, chunk by chunk across the jobs
-  std::vector<ChainJob> p_job;
-  std::vector<TargetJob> p_tgt;
-  std::vector<int32_t> p_chunk0, p_jseg0;
-  std::vector<uint32_t> p_slots;
-  int32_t p_nchunks = 0;
-  uint32_t p_npre = 0;
-  if (persist) {
-    for (int r = 0; r < R; ++r)
-      for (int a = 0; a < 2; ++a) {
-        if (L[r].seg[a].empty()) continue;
-        p_jseg0.push_back((int32_t)p_job.size());
-        for (const Segment& sg : L[r].seg[a]) {
-          NFSP_REQUIRE(sg.v - sg.u < 65536, "a BR segment of >= 65536 updates");
-          p_job.push_back(br_chain_job(g->eng[r], a, sg));
-          p_tgt.push_back(br_target_job(g->eng[r], L[r], a, sg));
-          p_chunk0.push_back(p_nchunks);
-          p_nchunks += (int32_t)((sg.v - sg.u + BRP_CHUNK - 1) / BRP_CHUNK);
-        }
-      }
-    NFSP_REQUIRE(p_job.size() < 65536, "too many BR segments in one learner call");
-    const int njobs = (int)p_jseg0.size();
-    p_jseg0.push_back((int32_t)p_job.size());
-    int64_t nitems = 0, maxn = 0;
-    for (const TargetJob& t : p_tgt) nitems += t.n;
-    for (int j = 0; j < njobs; ++j) maxn = p_tgt[p_jseg0[j]].n > maxn ? p_tgt[p_jseg0[j]].n : maxn;
-    p_slots.assign((size_t)nitems, BRP_EMPTY);
-    for (int64_t c0 = 0; c0 < maxn; c0 += BRP_CHUNK)
-      for (int j = 0; j < njobs; ++j) {
-        const int sgi = p_jseg0[j];
-        const int64_t n = p_tgt[sgi].n, c1 = c0 + BRP_CHUNK < n ? c0 + BRP_CHUNK : n;
-        for (int64_t i = c0; i < c1; ++i) p_slots[p_npre++] = ((uint32_t)sgi << 16) | (uint32_t)i;
-      }
-    max_rounds = njobs > 0 ? 1 : 0;
-  }
-  g->rounds = max_rounds;
-  TabCursor cur;
-  const size_t o_prep = cur.take<PrepArgs>(R), o_fin = cur.take<FinalArgs>(R);
-  const size_t o_ar = cur.take<ChainJob>(ar_jobs.size()), o_br = cur.take<ChainJob>(br_jobs.size());
-  const size_t o_tg = cur.take<TargetJob>(tg_jobs.size());
-  const size_t o_pj = cur.take<ChainJob>(p_job.size()), o_pt = cur.take<TargetJob>(p_tgt.size());
-  const size_t o_pc = cur.take<int32_t>(p_chunk0.size()), o_ps = cur.take<int32_t>(p_jseg0.size());
-  const size_t o_pq = cur.take<uint32_t>(p_slots.size()), o_pn = cur.take<uint32_t>(2);
-  const size_t o_pd = cur.take<uint32_t>((size_t)p_nchunks);
-  const size_t need = cur.off;
-  // Every earlier use of set `par` has completed: serially, the call starts with the readback's
-  // sync; pipelined, the ctx stream waited for slice j - 2's snapshot events (after its chains)
-  // before this slice's rollout.  A grown set is freed and reallocated: the device free
-  // synchronises the device.
-  char*& h_tab = g->h_tab[par];
-  char*& d_tab = g->d_tab[par];
-  if (need > g->tab_cap[par]) {
-    if (h_tab) NFSP_HIP(hipHostFree(h_tab));
-    if (d_tab) NFSP_HIP(hipFree(d_tab));
-    h_tab = nullptr;
-    d_tab = nullptr;
-    g->tab_cap[par] = 0;
-    const size_t cap = need * 2;
-    NFSP_HIP(hipHostMalloc((void**)&h_tab, cap, hipHostMallocDefault));
-    NFSP_HIP(hipMalloc((void**)&d_tab, cap));
-    g->tab_cap[par] = cap;
-  }
-  for (int r = 0; r < R; ++r) {
-    memcpy(h_tab + o_prep + sizeof(PrepArgs) * r, &L[r].P, sizeof(PrepArgs));
-    memcpy(h_tab + o_fin + sizeof(FinalArgs) * r, &L[r].F, sizeof(FinalArgs));
-  }
-  memcpy(h_tab + o_ar, ar_jobs.data(), sizeof(ChainJob) * ar_jobs.size());
-  memcpy(h_tab + o_br, br_jobs.data(), sizeof(ChainJob) * br_jobs.size());
-  memcpy(h_tab + o_tg, tg_jobs.data(), sizeof(TargetJob) * tg_jobs.size());
-  if (persist) {
-    memcpy(h_tab + o_pj, p_job.data(), sizeof(ChainJob) * p_job.size());
-    memcpy(h_tab + o_pt, p_tgt.data(), sizeof(TargetJob) * p_tgt.size());
-    memcpy(h_tab + o_pc, p_chunk0.data(), sizeof(int32_t) * p_chunk0.size());
-    memcpy(h_tab + o_ps, p_jseg0.data(), sizeof(int32_t) * p_jseg0.size());
-    memcpy(h_tab + o_pq, p_slots.data(), sizeof(uint32_t) * p_slots.size());
-    const uint32_t ctr[2] = {0u, p_npre};
-    memcpy(h_tab + o_pn, ctr, sizeof(ctr));
-    memset(h_tab + o_pd, 0, sizeof(uint32_t) * (size_t)p_nchunks);
-  }
-  const PrepArgs* d_prep = reinterpret_cast<const PrepArgs*>(d_tab + o_prep);
-  const FinalArgs* d_fin = reinterpret_cast<const FinalArgs*>(d_tab + o_fin);
-  const ChainJob* d_ar = reinterpret_cast<const ChainJob*>(d_tab + o_ar);
-  const ChainJob* d_br = reinterpret_cast<const ChainJob*>(d_tab + o_br);
-  const TargetJob* d_tg = reinterpret_cast<const TargetJob*>(d_tab + o_tg);
-  hipEvent_t fork_br = take_event(e0), fork = take_event(e0);
-  {
-    KTimer kprep(e0, KT_PREP);
-    NFSP_HIP(hipMemcpyAsync(d_tab, h_tab, need, hipMemcpyHostToDevice, s));
-    // the same prep kernels as one engine's, every replica in one launch (blockIdx.z)
-    if (maxUbr > 0) {
-      k_br_prep<1><<<dim3((unsigned)maxUbr, 2, R), 128, 0, s>>>(PrepArgs{}, d_prep);
-      NFSP_LAUNCHED("k_br_prep");
-    }
-    if (loss_log)
-      for (int r = 0; r < R; ++r)
-        for (int a = 0; a < 2; ++a)
-          NFSP_HIP(hipMemsetAsync(g->eng[r]->LB.br_loss + a * g->eng[r]->LB.umax * cfg.epochs, 0xFF,
-                                  sizeof(float) * L[r].P.A[a].U_br * cfg.epochs, s));
-    NFSP_HIP(hipEventRecord(fork_br, s));
-    if (maxSL > 0) {
-      k_ar_slots<1><<<dim3(nfsp_blocks(maxSL, 256), 2, R), 256, 0, s>>>(PrepArgs{}, d_prep);
-      NFSP_LAUNCHED("k_ar_slots");
-    }
-    if (maxU > 0) {
-      k_ar_prep<1><<<dim3((unsigned)maxU, 2, R), 128, 0, s>>>(PrepArgs{}, d_prep);
-      NFSP_LAUNCHED("k_ar_prep");
-    }
-    if (loss_log)
-      for (int r = 0; r < R; ++r)
-        for (int a = 0; a < 2; ++a)
-          NFSP_HIP(hipMemsetAsync(g->eng[r]->LB.ar_loss + a * g->eng[r]->LB.umax * cfg.epochs, 0xFF,
-                                  sizeof(float) * L[r].P.A[a].U * cfg.epochs, s));
-    NFSP_HIP(hipEventRecord(fork, s));
-    if (maxSL > 0) {
-      k_res_apply<1><<<dim3(nfsp_blocks(maxSL, 256), 2, R), 256, 0, s>>>(PrepArgs{}, d_prep);
-      NFSP_LAUNCHED("k_res_apply");
-    }
-  }
-  if (pipelined) {                     // the counters, before the next rollout's commit
-    k_finalize<1><<<R, 64, 0, s>>>(FinalArgs{}, d_fin, 1);
-    NFSP_LAUNCHED("k_finalize");
-  }
-  // When chains share CUs (R > 64), the first round's BR targets run before the AR chains
-  // start: alone they take the chip's issue slots instead of competing with 2R resident AR
-  // chains, and the BR stream is the longer one at that size.  (No data dependency.)
-  auto launch_ar = [&](hipEvent_t after) -> int {
-    NFSP_HIP(hipStreamWaitEvent(g->s_ar, fork, 0));
-    if (after) NFSP_HIP(hipStreamWaitEvent(g->s_ar, after, 0));
-    ChainArgs C{};
-    C.jobs = d_ar;
-    C.B = cfg.batch;
-    C.E = cfg.epochs;
-    C.lds = g->chain_lds;
-    KTimer kc(e0, KT_CHAIN_AR, g->s_ar);
-    return launch_chain_ar(C, (int)ar_jobs.size(), loss_log, g->s_ar);
-  };
-  bool ar_launched = ar_jobs.empty();
-  if (!shared_cus && !ar_launched) {
-    if ((rc = launch_ar(nullptr)) != NFSP_OK) return rc;
-    ar_launched = true;
-  }
-  for (int p = 1; p < nbs; ++p)
-    if (!g->s_brp[p - 1]) NFSP_HIP(hipStreamCreateWithFlags(&g->s_brp[p - 1], hipStreamNonBlocking));
-  static_assert(GROUP_BR_STREAMS == 4, "sp below");
-  hipStream_t sp[GROUP_BR_STREAMS] = {g->s_br, g->s_brp[0], g->s_brp[1], g->s_brp[2]};
-  for (int p = 0; p < nbs; ++p) NFSP_HIP(hipStreamWaitEvent(sp[p], fork_br, 0));
-  KTimer kspan(e0, KT_BR_STREAM0, g->s_br);     // the group's BR streams, end to end (joined on s_br)
-  if (persist && p_jseg0.size() > 1) {
-    BrPersistArgs P{};
-    P.C.B = cfg.batch;
-    P.C.E = cfg.epochs;
-    P.seg_job = reinterpret_cast<const ChainJob*>(d_tab + o_pj);
-    P.seg_tgt = reinterpret_cast<const TargetJob*>(d_tab + o_pt);
-    P.seg_chunk0 = reinterpret_cast<const int32_t*>(d_tab + o_pc);
-    P.job_seg0 = reinterpret_cast<const int32_t*>(d_tab + o_ps);
-    P.slots = reinterpret_cast<uint32_t*>(d_tab + o_pq);
-    P.ctr = reinterpret_cast<uint32_t*>(d_tab + o_pn);
-    P.chunk_done = reinterpret_cast<uint32_t*>(d_tab + o_pd);
-    NFSP_HIP(hipHostGetDevicePointer((void**)&P.err, g->h_err, 0));
-    P.njobs = (int)p_jseg0.size() - 1;
-    P.nitems = (int)p_slots.size();
-    P.chunk = BRP_CHUNK;
-    P.spin = g->sched.br_persist > 1 ? g->sched.br_persist : BRP_SPIN;
-    P.gamma = cfg.gamma;
-    P.lr0 = cfg.lr_br;
-    P.quirks = cfg.quirks;
-    KTimer kc(e0, KT_CHAIN_BR, g->s_br);
-    if ((rc = launch_br_persist(P, BRP_HELPERS, g->s_br)) != NFSP_OK) return rc;
-  }
-  for (const BrRound& rd : rounds_v) {
-    hipStream_t st = sp[rd.p];
-    const int nj = (int)(rd.b1 - rd.b0);
-    const int nt = (int)(rd.t1 - rd.t0);
-    if (nt > 0) {
-      {
-        KTimer kt2(e0, KT_TARGETS, st);
-        k_br_targets<<<dim3((unsigned)rd.rn, (unsigned)nt), 256, 0, st>>>(d_tg + rd.t0, TargetJob{}, cfg.batch,
-                                                                          cfg.epochs);
-      }
-      NFSP_LAUNCHED("k_br_targets");
-    }
-    if (!ar_launched) {                      // (one partition: shared_cus)
-      hipEvent_t t0 = take_event(e0);
-      NFSP_HIP(hipEventRecord(t0, st));
-      if ((rc = launch_ar(t0)) != NFSP_OK) return rc;
-      e0->pool.push_back(t0);
-      ar_launched = true;
-    }
-    ChainArgs C{};
-    C.jobs = d_br + rd.b0;
-    C.B = cfg.batch;
-    C.E = cfg.epochs;
-    C.lds = g->chain_lds;
-    KTimer kc(e0, KT_CHAIN_BR, st);
-    if ((rc = launch_br_chain(C, nj, cfg.quirks, loss_log, st)) != NFSP_OK) return rc;
-  }
-  if (!ar_launched && (rc = launch_ar(nullptr)) != NFSP_OK) return rc;
-  // each partition's stream: (pipelined) its replicas' BR results, then (snap_after) their BR /
-  // target nets and epsilons into snapshot `par`; then the partitions are joined on s_br
-  for (int p = 0; p < nbs; ++p) {
-    const int r0 = pr0[p], rn = pr0[p + 1] - pr0[p];
-    if (pipelined && rn > 0) {
-      k_finalize<1><<<rn, 64, 0, sp[p]>>>(FinalArgs{}, d_fin + r0, 6);
-      NFSP_LAUNCHED("k_finalize");
-      if (snap_after &&
-          (rc = nfsp::eng::group_snap_part_launch(g->eng.data() + r0, rn, g->d_roll, par, 1, sp[p], r0)) != NFSP_OK)
-        return rc;
-    }
-    if (p > 0) {
-      hipEvent_t j = take_event(e0);
-      NFSP_HIP(hipEventRecord(j, sp[p]));
-      NFSP_HIP(hipStreamWaitEvent(g->s_br, j, 0));
-      e0->pool.push_back(j);
-    }
-  }
-  if (pipelined) {
-    if (snap_after) NFSP_HIP(hipEventRecord(g->snap_ev[par][1], g->s_br));
-    // AR stream: the exchange when due (after this call's AR chains; AR nets only, so no other
-    // stream touches what it writes), then the AR nets into snapshot `par`
-    NFSP_HIP(hipStreamWaitEvent(g->s_ar, fork, 0));
-    if (g->xchg_every > 0 && (++g->calls) % g->xchg_every == 0 && (rc = group_xchg_launch(g, g->s_ar)) != NFSP_OK)
-      return rc;
-    if (snap_after) {
-      if ((rc = nfsp::eng::group_snap_part_launch(g->eng.data(), R, g->d_roll, par, 0, g->s_ar)) != NFSP_OK) return rc;
-      NFSP_HIP(hipEventRecord(g->snap_ev[par][0], g->s_ar));
-    }
-    e0->pool.push_back(fork);
-    e0->pool.push_back(fork_br);
-    return NFSP_OK;
-  }
-  for (hipStream_t st : {g->s_ar, g->s_br}) {
-    hipEvent_t j = take_event(e0);
-    NFSP_HIP(hipEventRecord(j, st));
-    NFSP_HIP(hipStreamWaitEvent(s, j, 0));
-    e0->pool.push_back(j);
-  }
-  e0->pool.push_back(fork);
-  e0->pool.push_back(fork_br);
-  k_finalize<1><<<R, 64, 0, s>>>(FinalArgs{}, d_fin, 7);
-  NFSP_LAUNCHED("k_finalize");
-  return NFSP_OK;
-}
 
 extern "C" int nfsp_engine_snapshot(nfsp_engine* e, int parity, float** dev_w, double* eps) {
   NFSP_REQUIRE(e && dev_w && eps && (parity == 0 || parity == 1), "bad argument");
@@ -1801,107 +1031,6 @@ extern "C" int nfsp_engine_set_update_limit(nfsp_engine* e, int64_t max_updates)
   return NFSP_OK;
 }
 
-extern "C" int nfsp_group_set_timing(nfsp_group* g, int on) {
-  NFSP_REQUIRE(g, "null argument");
-  for (nfsp_engine* e : g->eng) e->timing = on != 0;
-  return NFSP_OK;
-}
-
-// the replicas' rollout / prep marks and the group's shared launches (kept on replica 0)
-extern "C" int nfsp_group_get_timings(nfsp_group* g, double* ms, int64_t* launches) {
-  NFSP_REQUIRE(g && ms && launches, "null argument");
-  for (int k = 0; k < KT_N; ++k) { ms[k] = 0.0; launches[k] = 0; }
-  for (nfsp_engine* e : g->eng) {
-    double m[KT_N];
-    int64_t n[KT_N];
-    const int rc = nfsp_engine_get_timings(e, m, n);
-    if (rc != NFSP_OK) return rc;
-    for (int k = 0; k < KT_N; ++k) { ms[k] += m[k]; launches[k] += n[k]; }
-  }
-  return NFSP_OK;
-}
-
-// Every slice: rollout, then its learner, then (when due) the exchange.  With slice_lag 2 the
-// slices run one after another, but slice j acts with snapshot j & 1: the nets and epsilon as
-// slice j - 2's learner (and exchange) left them, the step's start for j < 2 -- a pipelined
-// engine's arithmetic (step_pipelined).
-extern "C" int nfsp_group_step(nfsp_group* g) {
-  NFSP_REQUIRE(g, "null argument");
-  int rc;
-  if (g->xchg_nets & ~g->w0_valid)      // common nets before the first exchange
-    if ((rc = nfsp_group_average_ar(g)) != NFSP_OK) return rc;
-  const int K = g->eng[0]->slices;
-  const bool lag2 = g->eng[0]->slice_lag == 2 && K > 1;
-  // Pipelined (as step_pipelined): slice j's rollout waits only for the snapshot copies of
-  // slice j - 2, so the rollout, readback, plan and prep of slice j + 1 overlap slice j's
-  // chains.  The same arithmetic as the serial loop below.  Not with a BR exchange (it would
-  // need both learner streams joined after every exchange) or sched.serial.
-  if (lag2 && !(g->xchg_nets & NFSP_XCHG_BR) && !g->sched.serial) {
-    hipStream_t s = g->ctx->stream;
-    if ((rc = nfsp::eng::group_snap_launch(g->eng.data(), g->R, g->d_roll, -1)) != NFSP_OK) return rc;
-    for (int j = 0; j < K; ++j) {
-      const int par = j & 1;
-      if (j >= 2)
-        for (hipEvent_t ev : g->snap_ev[par]) NFSP_HIP(hipStreamWaitEvent(s, ev, 0));
-      if ((rc = nfsp::eng::group_rollout_launch(g->eng.data(), g->R, g->d_roll, par)) != NFSP_OK) return rc;
-      if ((rc = group_update(g, true, par, j + 2 < K)) != NFSP_OK) return rc;
-    }
-    for (hipStream_t st : {g->s_ar, g->s_br}) {    // the step ends with every stream joined
-      hipEvent_t jv = take_event(g->eng[0]);
-      NFSP_HIP(hipEventRecord(jv, st));
-      NFSP_HIP(hipStreamWaitEvent(s, jv, 0));
-      g->eng[0]->pool.push_back(jv);
-    }
-    return NFSP_OK;
-  }
-  if (lag2 && (rc = nfsp::eng::group_snap_launch(g->eng.data(), g->R, g->d_roll, -1)) != NFSP_OK) return rc;
-  for (int j = 0; j < K; ++j) {
-    if ((rc = nfsp::eng::group_rollout_launch(g->eng.data(), g->R, g->d_roll, lag2 ? (j & 1) : -1)) != NFSP_OK)
-      return rc;
-    if ((rc = group_update(g)) != NFSP_OK) return rc;
-    if (g->xchg_every > 0 && (++g->calls) % g->xchg_every == 0 && (rc = nfsp_group_average_ar(g)) != NFSP_OK)
-      return rc;
-    if (lag2 && j + 2 < K && (rc = nfsp::eng::group_snap_launch(g->eng.data(), g->R, g->d_roll, j & 1)) != NFSP_OK)
-      return rc;
-  }
-  return NFSP_OK;
-}
-
-namespace {
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v && *v ? atoi(v) : dflt;
-}
-}  // namespace
-
-extern "C" int nfsp_group_default_sched(nfsp_group_sched* out) {
-  NFSP_REQUIRE(out, "null argument");
-  out->br_cap = env_int("NFSP_GROUP_BR_CAP", -1);
-  out->br_pace = env_int("NFSP_GROUP_BR_PACE", 1) != 0;
-  out->br_streams = env_int("NFSP_GROUP_BR_STREAMS", -1);
-  out->serial = env_int("NFSP_GROUP_SERIAL", 0) != 0;
-  out->br_persist = env_int("NFSP_GROUP_BR_PERSIST", 0);
-  return NFSP_OK;
-}
-
-extern "C" int nfsp_group_set_sched(nfsp_group* g, const nfsp_group_sched* sc) {
-  NFSP_REQUIRE(g && sc, "null argument");
-  NFSP_REQUIRE(sc->br_cap >= -1, "br_cap must be >= -1");
-  NFSP_REQUIRE(sc->br_streams == -1 || (sc->br_streams >= 1 && sc->br_streams <= GROUP_BR_STREAMS),
-               "br_streams must be -1 or in [1, 4]");
-  NFSP_REQUIRE(sc->br_persist >= 0, "br_persist must be >= 0");
-  g->sched = *sc;
-  g->sched.br_pace = sc->br_pace != 0;
-  g->sched.serial = sc->serial != 0;
-  return NFSP_OK;
-}
-
-extern "C" int nfsp_group_get_sched(nfsp_group* g, nfsp_group_sched* out) {
-  NFSP_REQUIRE(g && out, "null argument");
-  *out = g->sched;
-  return NFSP_OK;
-}
-
 #ifdef NFSP_BRP_STAMPS
 extern "C" int nfsp_debug_brp_stamps(unsigned long long* out, int reset) {
   NFSP_HIP(hipDeviceSynchronize());
@@ -1913,34 +1042,3 @@ extern "C" int nfsp_debug_brp_stamps(unsigned long long* out, int reset) {
   return NFSP_OK;
 }
 #endif
-
-extern "C" int nfsp_group_check(nfsp_group* g) {
-  NFSP_REQUIRE(g, "null argument");
-  NFSP_HIP(hipStreamSynchronize(g->ctx->stream));
-  for (hipStream_t st : {g->s_ar, g->s_br})
-    if (st) NFSP_HIP(hipStreamSynchronize(st));
-  for (hipStream_t st : g->s_brp)
-    if (st) NFSP_HIP(hipStreamSynchronize(st));
-  return group_check_err(g);
-}
-
-extern "C" int nfsp_group_rounds(nfsp_group* g, int64_t* out) {
-  NFSP_REQUIRE(g && out, "null argument");
-  *out = g->rounds;
-  return NFSP_OK;
-}
-
-extern "C" int nfsp_group_set_trace(nfsp_group* g, int on) {
-  NFSP_REQUIRE(g, "null argument");
-  g->trace_on = on != 0;
-  g->trace.clear();
-  return NFSP_OK;
-}
-
-extern "C" int nfsp_group_trace(nfsp_group* g, int32_t* out, int64_t cap, int64_t* n) {
-  NFSP_REQUIRE(g && n && cap >= 0 && (out || cap == 0), "bad argument");
-  const int64_t m = (int64_t)g->trace.size();
-  for (int64_t i = 0; i < m && i < cap; ++i) out[i] = g->trace[i];
-  *n = m;
-  return NFSP_OK;
-}

@@ -1,0 +1,156 @@
+// What learner.hip (the learner's kernels, the one-engine learner call, the launchers) shares
+// with group.hip (the engine group's host code): the plain structs a learner call's tables are
+// built from, the plan of one engine's call, and the host launchers of learner.hip's kernels.
+#pragma once
+#include <initializer_list>
+#include <vector>
+
+#include "engine_internal.h"
+#include "chain3.h"
+#include "group_plan.h"
+
+namespace nfsp {
+namespace eng {
+
+struct AgentPlan {
+  int64_t P0;          // agent's RL inserts before the last rollout
+  int64_t m_first;     // first trigger index (trigger m at RL stream position m * c)
+  int64_t U;           // triggers in the last rollout
+  int64_t m_br0;       // first trigger with a BR update (position > batch)
+  int64_t U_br;
+  int64_t n_sl;        // SL records of the last rollout
+  int64_t sl_total0;   // SL inserts before the last rollout
+};
+
+struct PrepArgs {
+  Memories M;
+  LearnBufs LB;
+  EngineDev* st;
+  AgentPlan A[2];
+  int64_t c, rl_cap;
+  int B, E;
+  uint32_t k0, k1, tag;
+  float lr_ar;
+  uint32_t quirks;
+};
+
+// One (engine, agent) segment: the agent's learner buffers (update u of the learner call at
+// index u), the target net, and the segment's update range [u0, u0 + n).
+struct TargetJob {
+  const BrRow* rows;   // [umax][B]
+  const uint8_t* perm; // [umax][E][B]
+  double* expl;        // [umax]
+  StepRec* rec;        // [umax][E][B / 32]
+  const float* tw;     // target net
+  int64_t u0, n;
+  int64_t it0;         // the agent's iteration count before the learner call
+  // the replica's own cfg.gamma / lr_br / quirks: the replicas of a group may differ in them
+  // (nfsp_group_create_v), so they travel with the job, not with the launch
+  double gamma, lr0;
+  unsigned quirks;
+};
+
+// k_br_persist's arguments (learner.hip)
+struct BrPersistArgs {
+  chain::ChainArgs C;           // B, E (the chains' jobs come from seg_job)
+  const chain::ChainJob* seg_job;   // [nseg] chain job of each segment (u0, u1: the segment; sync_to)
+  const TargetJob* seg_tgt;     // [nseg] its targets job
+  const int32_t* seg_chunk0;    // [nseg] its first chunk counter
+  const int32_t* job_seg0;      // [njobs + 1] chain workgroup j's segments: [job_seg0[j], job_seg0[j + 1])
+  uint32_t* slots;              // [nitems] work items (segment << 16 | update in it); BRP_EMPTY until queued
+  uint32_t* ctr;                // [0] helpers' claims, [1] queue reservations
+  uint32_t* chunk_done;         // finished items per chunk
+  int32_t* err;                 // pinned host: [0] a wait expired, [1] chain bails, [2] helper bails
+  int njobs, nitems, chunk;
+  int spin;                     // bound of every wait (s_sleep 8 rounds)
+  double gamma, lr0;
+  unsigned quirks;
+};
+constexpr int BRP_SPIN = 1 << 18;           // x s_sleep 8 (~56 ms): far past any legitimate wait
+constexpr int BRP_CHUNK = 16;               // updates per chain piece (readiness is checked per piece)
+constexpr int BRP_HELPERS = 48;             // helper workgroups (c4_emul_r8, timeline tool, with
+                                            // the scalar jobs: 96 / 144 / 192 helpers 193.1 /
+                                            // 189.5 / 188.1 ms, the AR chains slowing 155 -> 166;
+                                            // the rounds 179.6)
+
+// schedule state after the learner (host-computed values + device-side counters)
+struct FinalArgs {
+  EngineDev* st;
+  const double* br_expl;
+  int64_t umax;
+  int64_t n_rl[2], n_sl[2], U_br[2];
+  int64_t iteration[2], tcount[2], syncs[2];
+  double eps[2], temp[2];
+  float lr[2];
+  int64_t sl_cap;
+};
+
+// ---------------------------------------------------------------------------
+// host side: one learner call = plan (from the rollout's insert counts) + prep launches +
+// chain launches + finalize.  nfsp_engine_update runs them for one engine, the group for
+// R engines with their chains in shared launches.
+// ---------------------------------------------------------------------------
+using Segment = plan::Segment;   // BR updates [u, v) of the learner call; sync: ends with a target sync
+
+struct LearnPlan {
+  PrepArgs P;
+  int64_t maxU = 0, maxUbr = 0, maxSL = 0;
+  std::vector<Segment> seg[2];
+  int64_t it0[2];
+  FinalArgs F;
+  nfsp_engine::Sched hs;     // the schedules after this call (commit_plan publishes them)
+};
+
+// The learner call's plan from the rollout's insert counts and the host's schedule mirror.
+// Leaves the engine untouched: commit_plan(e, L) adopts it once every plan of the call (a
+// group's replicas) has succeeded, so a failed plan changes no replica's schedules.
+int plan_update(const nfsp_engine* e, const EngineDev& h, LearnPlan& L);
+void commit_plan(nfsp_engine* e, const LearnPlan& L);
+
+// the AR chain of agent a over the whole learner call
+chain::ChainJob ar_job(const nfsp_engine* e, const LearnPlan& L, int a);
+// a BR segment of agent a: its targets and its chain
+TargetJob br_target_job(const nfsp_engine* e, const LearnPlan& L, int a, const Segment& sg);
+chain::ChainJob br_chain_job(const nfsp_engine* e, int a, const Segment& sg);
+
+// a chain launch's arguments: the cfg's batch and epochs; jobs / lds: a group's device job table
+// and LDS per workgroup (one engine: the jobs go into C.job, a CU each)
+inline chain::ChainArgs chain_args(const nfsp_engine_cfg& cfg, const chain::ChainJob* jobs = nullptr, int lds = 0) {
+  chain::ChainArgs C{};
+  C.jobs = jobs;
+  C.B = cfg.batch;
+  C.E = cfg.epochs;
+  C.lds = lds;
+  return C;
+}
+
+// The work of `streams` so far joined into `dst`: per stream an event of e's pool, recorded on
+// it, awaited by dst and returned to the pool (reusable once the wait is enqueued).
+int join_into(nfsp_engine* e, hipStream_t dst, std::initializer_list<hipStream_t> streams);
+
+// ---- launchers (learner.hip).  The one-engine form of a kernel takes its arguments by value,
+// the table form (_table: engine groups) reads entry blockIdx.z / blockIdx.x of a device table;
+// each pair is one function template in learner.hip.
+// The parallel prep of a learner call on `s`, in the order the chains need it: the BR rows
+// first (the BR segments are the learner's critical path), then fork_br is recorded for the BR
+// streams; then the AR records, fork is recorded for the AR stream; the final reservoir last
+// (only the next rollout reads it, and it must follow k_ar_prep, which reads the reservoir as
+// it was).  With the loss log on, each log is reset (NaN = no fit recorded) behind its prep.
+int launch_prep(nfsp_engine* e, const LearnPlan& L, hipEvent_t fork_br, hipEvent_t fork, hipStream_t s);
+int launch_prep_table(nfsp_engine* const* eng, const LearnPlan* L, int R, const PrepArgs* tab, hipEvent_t fork_br,
+                      hipEvent_t fork, hipStream_t s);
+// k_finalize (mode bits: see there) of one engine, or of n table entries
+int launch_finalize(const FinalArgs& F, int mode, hipStream_t s);
+int launch_finalize_table(const FinalArgs* tab, int n, int mode, hipStream_t s);
+// the targets of `njobs` segments of at most `n` updates (jobs: device table; null: `one`)
+int launch_br_targets(const TargetJob* jobs, const TargetJob& one, int64_t n, int njobs, int B, int E, hipStream_t s);
+int launch_br_chain(const chain::ChainArgs& C, int blocks, unsigned quirks, bool loss_log, hipStream_t s);
+// launch with a CU per workgroup: dynamic LDS up to what the CU has left beside the kernel's
+// static LDS (the helpers' targets buffers), as the one-engine chains reserve theirs
+int launch_br_persist(const BrPersistArgs& P, int helpers, hipStream_t s);
+// engine groups: the replicas' EngineDev gathered into one array; the exchange (k_group_xchg)
+int launch_gather_st(EngineDev* const* src, EngineDev* dst, int R, hipStream_t s);
+int launch_group_xchg(float* const* wtab, float* w0, int R, unsigned nets, unsigned bcast, float scale, hipStream_t s);
+
+}  // namespace eng
+}  // namespace nfsp

@@ -26,12 +26,6 @@ int fail(int code, const std::string&) { return code; }
 int hip_fail(hipError_t, const char*) { return NFSP_EHIP; }
 namespace eng {
 hipEvent_t take_event(nfsp_engine*) { return nullptr; }
-int engine_create(nfsp_ctx*, const nfsp_engine_cfg*, bool, nfsp_engine**) { return NFSP_EINVAL; }
-int engine_cfg_check(const nfsp_engine_cfg*) { return NFSP_EINVAL; }
-int group_rollout_table(nfsp_engine* const*, int, void**) { return NFSP_EINVAL; }
-int group_rollout_launch(nfsp_engine* const*, int, const void*, int) { return NFSP_EINVAL; }
-int group_snap_launch(nfsp_engine* const*, int, const void*, int) { return NFSP_EINVAL; }
-int group_snap_part_launch(nfsp_engine* const*, int, const void*, int, int, hipStream_t) { return NFSP_EINVAL; }
 int exchange_enqueue(nfsp_engine*, hipStream_t) { return NFSP_EINVAL; }
 int rollout_launch_with(nfsp_engine*, const float*, const double*) { return NFSP_EINVAL; }
 }
@@ -39,9 +33,6 @@ int rollout_launch_with(nfsp_engine*, const float*, const double*) { return NFSP
 namespace nfsp { namespace chain {
 int launch_chain_br_linear(const ChainArgs&, int, bool, bool, hipStream_t) { return NFSP_EINVAL; }
 } }
-extern "C" const char* nfsp_last_error(void) { return ""; }
-extern "C" int nfsp_engine_destroy(nfsp_engine*) { return NFSP_OK; }
-extern "C" int nfsp_engine_get_timings(nfsp_engine*, double*, int64_t*) { return NFSP_OK; }
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1);} } while (0)
 
