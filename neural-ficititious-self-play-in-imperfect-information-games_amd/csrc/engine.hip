@@ -2,19 +2,25 @@
 // commit of its records into the agents' memories, and the on-device learner.
 // Declarations and the semantics contract: include/nfsp.h (nfsp_engine_*).
 //
-// Data path of one nfsp_engine_step (all on the ctx stream, no host sync):
+// Data path of one nfsp_engine_step, per lane slice.  This file, on the ctx stream:
 //   k_rollout   one lane = one env: deal, eta draws, main.train's D/L/D scheduler, every
 //               Agent.play (observe -> RL record, act with the AR net or eps-greedy BR
 //               net -> env.step -> SL record).  Networks of both agents in LDS.  Records
 //               go to lane-major staging ([slot][lane], so a wave's stores coalesce).
 //   k_scan1/2   exclusive prefix over lanes of the 4 per-lane record counts -> canonical
 //               insert order (lane, then play order) independent of scheduling.
-//   k_commit    RL records -> each agent's circular M_RL log (fp32 reference layout);
+//   k_commit    RL records -> each agent's circular M_RL log (bit-packed RlRec);
 //               SL records -> the agent's pending list with their RL stream position.
-//   k_learner   4 workgroups (agent x {AR, BR}): update_strategy once per
-//               inserts_per_update RL inserts, each a sampled minibatch, the DQN targets,
-//               epochs x minibatch SGD (nn_device.h), and the reference schedules; the
-//               AR workgroup applies the reservoir inserts in stream order in between.
+// Then the learner call (engine_update.hip; kernels in learner.hip): one readback of the insert
+// counts for the host's plan of update_strategy's triggers (learn_plan.h), then
+//   prep kernels  on the ctx stream, all updates at once: k_br_prep (sampled M_RL rows, fit
+//               permutations), k_ar_slots / k_ar_prep (reservoir slots; the AR step records
+//               from M_SL as of each trigger), k_res_apply (the reservoir after the inserts)
+//   k_br_targets  per agent on its BR stream, per segment between target syncs: the DQN
+//               targets and the BR step records
+//   k_chain3    the SGD steps, one workgroup per (agent, net) with the net in registers: the
+//               BR chain after each segment's targets, both AR chains on the AR stream
+//   k_finalize  the insert counters and the reference schedules into EngineDev.
 #include <math.h>
 
 #include <cmath>
@@ -647,7 +653,6 @@ int engine_create(nfsp_ctx* ctx, const nfsp_engine_cfg* cfg, bool own_streams, n
       L.res_slot = e->LBs[0].res_slot;
     }
   }
-  e->LB = e->LBs[0];
   if (e->slice_lag == 2) {
     EALLOC(e->snap, sizeof(float) * 2 * 6 * nn::NP);
     if (!own_streams) EALLOC(e->snap_eps_dev, sizeof(double) * 4);   // a group replica
@@ -961,10 +966,11 @@ extern "C" int nfsp_engine_losses(nfsp_engine* e, double* out) {
   NFSP_REQUIRE(e->log_loss, "the loss log is off (nfsp_engine_set_loss_log)");
   NFSP_HIP(hipStreamSynchronize(e->ctx->stream));
   const int E = e->cfg.epochs;
+  const LearnBufs& LB = e->LBs[e->last_par];      // the last learner call's set
   for (int a = 0; a < 2; ++a)
     for (int n = 0; n < 2; ++n) {                 // n: 0 = AR (avg_strategy_model), 1 = BR
       const int64_t U = n ? e->last_Ubr[a] : e->last_U[a];
-      const float* src = (n ? e->LB.br_loss : e->LB.ar_loss) + (int64_t)a * e->LB.umax * E;
+      const float* src = (n ? LB.br_loss : LB.ar_loss) + (int64_t)a * LB.umax * E;
       std::vector<float> h((size_t)(U * E));
       if (U > 0) NFSP_HIP(hipMemcpy(h.data(), src, sizeof(float) * U * E, hipMemcpyDeviceToHost));
       double sum = 0.0, last = NAN;

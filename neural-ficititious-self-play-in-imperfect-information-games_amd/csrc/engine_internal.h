@@ -1,5 +1,6 @@
-// Internals shared by engine.hip (rollout, insert, lifecycle), learner.hip (the learner), group.hip
-// (engine groups) and state.hip.
+// Internals shared by engine.hip (rollout, insert, lifecycle), learner.hip (the learner's kernels
+// and launchers), engine_update.hip (one engine's learner call), group.hip (engine groups) and
+// state.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -261,8 +262,11 @@ struct nfsp_engine {
   nfsp::eng::EngineDev* st = nullptr;
   nfsp::eng::Staging S{};
   nfsp::eng::Memories M{};
-  nfsp::eng::LearnBufs LB{};        // the learner call's buffers: LBs[parity of the slice]
-  nfsp::eng::LearnBufs LBs[2]{};     // [1] only with cfg.slice_lag 2 (double-buffered slices)
+  // the learner calls' buffers, by slice parity: [1] only with cfg.slice_lag 2 (double-buffered
+  // slices).  A call's plan names its set (plan_update); last_par: the last call's, whose loss
+  // logs nfsp_engine_losses reads
+  nfsp::eng::LearnBufs LBs[2]{};
+  int last_par = 0;
   int slice_lag = 1;                 // cfg.slice_lag
   // cfg.slice_lag 2: the acting nets of the next rollouts, [parity][2 agents][3 nets][NP]
   // (target slots unused), and the epsilon each parity's rollout acts with
@@ -310,7 +314,7 @@ int engine_create(nfsp_ctx* ctx, const nfsp_engine_cfg* cfg, bool own_streams, n
 int rollout_launch(nfsp_engine* e);   // nfsp_rollout's launches
 // the same with the acting nets / epsilon given (cfg.slice_lag 2: a snapshot)
 int rollout_launch_with(nfsp_engine* e, const float* w, const double eps[2]);
-// nfsp_engine_step with cfg.slice_lag 2 (learner.hip): the slices pipelined
+// nfsp_engine_step with cfg.slice_lag 2 (engine_update.hip): the slices pipelined
 int step_pipelined(nfsp_engine* e);
 // engine groups: the replicas' rollout arguments as a device table (static), and every
 // replica's rollout through it in one launch per kernel

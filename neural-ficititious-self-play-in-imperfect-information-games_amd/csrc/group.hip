@@ -433,8 +433,7 @@ static int group_plans(GroupCall& c) {
   for (int r = 0; r < R; ++r) {
     nfsp_engine* e = g->eng[r];
     NFSP_REQUIRE(e->log_loss == c.loss_log, "the loss log must be on in all replicas of a group or none");
-    e->LB = e->LBs[c.par];
-    if ((rc = plan_update(e, g->h_st[r], c.L[r])) != NFSP_OK) return rc;
+    if ((rc = plan_update(e, c.par, g->h_st[r], c.L[r])) != NFSP_OK) return rc;
   }
   // every plan succeeded: the rollouts are consumed and the schedules advance (a failed
   // plan leaves every replica as it was -- pending, schedules untouched -- so they stay in step)
@@ -517,13 +516,14 @@ static int group_fill_tables(GroupCall& c) {
   }
   if (!c.ar_jobs.empty()) memcpy(h_tab + o_ar, c.ar_jobs.data(), sizeof(ChainJob) * c.ar_jobs.size());
   for (size_t i = 0; i < pc.size(); ++i)
-    tab_at<ChainJob>(h_tab, o_br)[i] = br_chain_job(g->eng[pc[i].r], pc[i].a, Segment{pc[i].u, pc[i].v, pc[i].sync});
+    tab_at<ChainJob>(h_tab, o_br)[i] =
+        br_chain_job(g->eng[pc[i].r], c.L[pc[i].r], pc[i].a, Segment{pc[i].u, pc[i].v, pc[i].sync});
   for (size_t i = 0; i < tg.size(); ++i)
     tab_at<TargetJob>(h_tab, o_tg)[i] = br_target_job(g->eng[tg[i].r], c.L[tg[i].r], tg[i].a, seg_of(tg[i]));
   if (c.sc.persist) {
     for (size_t i = 0; i < q.segs.size(); ++i) {
       const plan::SegRef& t = q.segs[i];
-      tab_at<ChainJob>(h_tab, o_pj)[i] = br_chain_job(g->eng[t.r], t.a, seg_of(t));
+      tab_at<ChainJob>(h_tab, o_pj)[i] = br_chain_job(g->eng[t.r], c.L[t.r], t.a, seg_of(t));
       tab_at<TargetJob>(h_tab, o_pt)[i] = br_target_job(g->eng[t.r], c.L[t.r], t.a, seg_of(t));
     }
     memcpy(h_tab + o_pc, q.chunk0.data(), sizeof(int32_t) * q.chunk0.size());

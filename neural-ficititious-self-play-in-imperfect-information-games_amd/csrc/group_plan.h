@@ -9,13 +9,11 @@
 
 #include <vector>
 
+#include "learn_plan.h"   // Segment
+
 namespace nfsp {
 namespace plan {
 
-struct Segment {
-  int64_t u, v;        // BR updates [u, v) of the learner call
-  bool sync;           // ends with a target sync
-};
 // job 2 r + a: the segments of (replica r, agent a) in order; null or empty: no BR work
 using Jobs = std::vector<const std::vector<Segment>*>;
 

@@ -1,9 +1,9 @@
 // The engine's learner (nfsp_engine_update): update_strategy at the reference cadence
 // for the RL/SL inserts of the last rollout.  Reference: agent/agent.py:192-273.
 // This file: the learner's kernels (the BR instantiation of k_chain3 among them: this is the
-// BR chain's translation unit, built with the chain flags), their host launchers
-// (learner_internal.h), and the one-engine learner call.  The engine group's host code, which
-// launches the same kernels through the launchers, is group.hip.
+// BR chain's translation unit, built with the chain flags) and their host launchers
+// (learner_internal.h).  The host code of a learner call, which launches the kernels through
+// the launchers, is engine_update.hip (one engine) and group.hip (an engine group).
 //
 // An update's inputs (sampled rows, fit permutations, reservoir contents at that moment,
 // DQN targets) do not depend on the weights being trained, except the targets on the
@@ -535,171 +535,19 @@ extern "C" int nfsp_debug_chain_stamps(unsigned long long* out) {
 #endif
 
 // ---------------------------------------------------------------------------
-// host side (learner_internal.h): the plan of one engine's learner call, its jobs, the launchers
+// host side: the launchers (learner_internal.h).  The device code object lists the template
+// kernels in the order of their first use below -- the <0> prep kernels, the BR chain,
+// k_finalize<0>, then the <1> forms -- so the definitions keep that order.
 // ---------------------------------------------------------------------------
 namespace nfsp {
 namespace eng {
 
-int plan_update(const nfsp_engine* e, const EngineDev& h, LearnPlan& L) {
-  const nfsp_engine_cfg& cfg = e->cfg;
-  PrepArgs& P = L.P;
-  P = PrepArgs{};
-  P.M = e->M;
-  P.LB = e->LB;
-  P.st = e->st;
-  P.c = cfg.inserts_per_update;
-  P.rl_cap = cfg.rl_capacity;
-  P.B = cfg.batch;
-  P.E = cfg.epochs;
-  P.k0 = (uint32_t)cfg.seed;
-  P.k1 = (uint32_t)(cfg.seed >> 32);
-  P.tag = e->learn_tag + 1;
-  P.lr_ar = cfg.lr_ar;
-  P.quirks = cfg.quirks;
-  L.maxU = L.maxUbr = L.maxSL = 0;
-  for (int a = 0; a < 2; ++a) {
-    AgentPlan& pl = P.A[a];
-    pl.P0 = h.rl_total[a];
-    const int64_t n = h.last_rl[a];
-    pl.m_first = pl.P0 / P.c + 1;
-    const int64_t m_last = (pl.P0 + n) / P.c;
-    pl.U = m_last >= pl.m_first ? m_last - pl.m_first + 1 : 0;
-    // BR update iff min(p_m, cap) > batch  <=>  m * c > batch
-    pl.m_br0 = pl.m_first > cfg.batch / P.c + 1 ? pl.m_first : cfg.batch / P.c + 1;
-    pl.U_br = m_last >= pl.m_br0 ? m_last - pl.m_br0 + 1 : 0;
-    pl.n_sl = h.last_sl[a];
-    pl.sl_total0 = h.sl_total[a];
-    NFSP_REQUIRE(pl.U <= e->LB.umax, "update plan exceeds the learner buffers");
-    L.maxU = pl.U > L.maxU ? pl.U : L.maxU;
-    L.maxUbr = pl.U_br > L.maxUbr ? pl.U_br : L.maxUbr;
-    L.maxSL = pl.n_sl > L.maxSL ? pl.n_sl : L.maxSL;
-  }
-  FinalArgs& F = L.F;
-  F = FinalArgs{};
-  F.st = e->st;
-  F.br_expl = e->LB.br_expl;
-  F.umax = e->LB.umax;
-  F.sl_cap = cfg.sl_capacity;
-  for (int a = 0; a < 2; ++a) {
-    const AgentPlan& pl = P.A[a];
-    F.n_rl[a] = h.last_rl[a];
-    F.n_sl[a] = pl.n_sl;
-    F.U_br[a] = pl.U_br;
-    // the schedules from the host's mirror (the device copy in EngineDev, written by
-    // k_finalize, may still be in flight with cfg.slice_lag 2)
-    int64_t it = e->hs.iteration[a], tc = e->hs.target_count[a], syncs = e->hs.target_syncs[a];
-    double eps = e->hs.epsilon[a];
-    L.it0[a] = it;
-    // BR segments between target syncs: [u, v) ends after the first update whose
-    // target_count % every == 0 (agent/agent.py:266-273)
-    L.seg[a].clear();
-    for (int64_t u = 0; u < pl.U_br;) {
-      int64_t v = u;
-      bool sync = false;
-      while (v < pl.U_br) {
-        const bool s_here = (tc + v) % cfg.target_every == 0;
-        ++v;
-        if (s_here) { sync = true; break; }
-      }
-      L.seg[a].push_back({u, v, sync});
-      u = v;
-    }
-    // schedules (agent/agent.py:245-253, 266-273) in the reference's double arithmetic
-    for (int64_t k = 0; k < pl.U_br; ++k) {
-      if (tc % cfg.target_every == 0) syncs++;
-      tc++;
-      it += 2;
-      eps = (cfg.quirks & NFSP_EXT_EPS_CONST) ? cfg.epsilon : eps / (double)it;
-    }
-    if (e->update_limit > 0) {         // test hook: only a prefix of the updates runs
-      std::vector<Segment> kept;
-      for (const Segment& sg : L.seg[a]) {
-        if (sg.u >= e->update_limit) break;
-        kept.push_back(sg.v <= e->update_limit ? sg : Segment{sg.u, e->update_limit, false});
-      }
-      L.seg[a] = kept;
-    }
-    F.iteration[a] = it;
-    F.tcount[a] = tc;
-    F.syncs[a] = syncs;
-    F.eps[a] = eps;
-    L.hs.iteration[a] = it;
-    L.hs.target_count[a] = tc;
-    L.hs.target_syncs[a] = syncs;
-    L.hs.epsilon[a] = eps;
-    F.temp[a] = 1.0 / (1.0 + 0.02 * sqrt((double)it));
-    F.lr[a] = (float)(cfg.lr_br / (1.0 + 0.003 * sqrt((double)it)));
-  }
-  return NFSP_OK;
-}
-
-void commit_plan(nfsp_engine* e, const LearnPlan& L) {
-  e->learn_tag = L.P.tag;
-  e->hs = L.hs;
-  for (int a = 0; a < 2; ++a) {
-    e->last_U[a] = L.P.A[a].U;
-    e->last_Ubr[a] = L.P.A[a].U_br;
-  }
-  e->pending_update = false;
-}
-
-static int64_t recs_per_update(const nfsp_engine* e) { return (int64_t)e->cfg.epochs * (e->cfg.batch / CHAIN_MB); }
-
-ChainJob ar_job(const nfsp_engine* e, const LearnPlan& L, int a) {
-  const int64_t um = e->LB.umax;
-  ChainJob j{};
-  j.w = e->w + (a * 3 + 0) * nn::NP;
-  j.sync_to = nullptr;
-  j.snap_to = nullptr;
-  j.rec = e->LB.ar_rec + a * um * recs_per_update(e);
-  j.active = e->LB.ar_active + a * um;
-  j.loss_out = e->log_loss ? e->LB.ar_loss + a * um * e->cfg.epochs : nullptr;
-  j.u0 = 0;
-  j.u1 = L.P.A[a].U;
-  if (e->update_limit > 0 && j.u1 > e->update_limit) j.u1 = e->update_limit;   // test hook
-  return j;
-}
-
-TargetJob br_target_job(const nfsp_engine* e, const LearnPlan& L, int a, const Segment& sg) {
-  const int64_t um = e->LB.umax, B = e->cfg.batch, E = e->cfg.epochs;
-  TargetJob t{};
-  t.rows = e->LB.br_rows + a * um * B;
-  t.perm = e->LB.br_perm + a * um * E * B;
-  t.expl = e->LB.br_expl + a * um;
-  t.rec = e->LB.br_rec + a * um * recs_per_update(e);
-  t.tw = e->w + (a * 3 + 2) * nn::NP;
-  t.u0 = sg.u;
-  t.n = sg.v - sg.u;
-  t.it0 = L.it0[a];
-  t.gamma = e->cfg.gamma;
-  t.lr0 = e->cfg.lr_br;
-  t.quirks = e->cfg.quirks;
-  return t;
-}
-
-ChainJob br_chain_job(const nfsp_engine* e, int a, const Segment& sg) {
-  const int64_t um = e->LB.umax;
-  ChainJob j{};
-  j.w = e->w + (a * 3 + 1) * nn::NP;
-  j.sync_to = sg.sync ? e->w + (a * 3 + 2) * nn::NP : nullptr;
-  j.snap_to = nullptr;
-  j.rec = e->LB.br_rec + a * um * recs_per_update(e);
-  j.active = nullptr;
-  j.loss_out = e->log_loss ? e->LB.br_loss + a * um * e->cfg.epochs : nullptr;
-  j.u0 = sg.u;
-  j.u1 = sg.v;
-  return j;
-}
-
-// ---- launchers.  The device code object lists the template kernels in the order of their first
-// use below -- the <0> prep kernels, the BR chain, k_finalize<0>, then the <1> forms -- so the
-// definitions keep that order.
-
-// the first n0 / n1 updates' epoch losses of the two agents <- NaN (no fit recorded)
-static int clear_loss_log(const nfsp_engine* e, float* loss, int64_t n0, int64_t n1, hipStream_t s) {
+// the first n0 / n1 updates' epoch losses of the two agents in a log of the plan's buffer set
+// <- NaN (no fit recorded)
+static int clear_loss_log(const PrepArgs& P, float* loss, int64_t n0, int64_t n1, hipStream_t s) {
   const int64_t n[2] = {n0, n1};
   for (int a = 0; a < 2; ++a)
-    NFSP_HIP(hipMemsetAsync(loss + a * e->LB.umax * e->cfg.epochs, 0xFF, sizeof(float) * n[a] * e->cfg.epochs, s));
+    NFSP_HIP(hipMemsetAsync(loss + a * P.LB.umax * P.E, 0xFF, sizeof(float) * n[a] * P.E, s));
   return NFSP_OK;
 }
 
@@ -723,7 +571,7 @@ static int launch_prep_t(nfsp_engine* const* eng, const LearnPlan* L, int R, con
   }
   if (loss_log)
     for (int r = 0; r < R; ++r)
-      if ((rc = clear_loss_log(eng[r], eng[r]->LB.br_loss, L[r].P.A[0].U_br, L[r].P.A[1].U_br, s)) != NFSP_OK) return rc;
+      if ((rc = clear_loss_log(L[r].P, L[r].P.LB.br_loss, L[r].P.A[0].U_br, L[r].P.A[1].U_br, s)) != NFSP_OK) return rc;
   NFSP_HIP(hipEventRecord(fork_br, s));
   if (maxSL > 0) {
     k_ar_slots<TABLE><<<dim3(nfsp_blocks(maxSL, 256), 2, R), 256, 0, s>>>(one, tab);
@@ -735,7 +583,7 @@ static int launch_prep_t(nfsp_engine* const* eng, const LearnPlan* L, int R, con
   }
   if (loss_log)                          // (an inactive AR update records no fit either)
     for (int r = 0; r < R; ++r)
-      if ((rc = clear_loss_log(eng[r], eng[r]->LB.ar_loss, L[r].P.A[0].U, L[r].P.A[1].U, s)) != NFSP_OK) return rc;
+      if ((rc = clear_loss_log(L[r].P, L[r].P.LB.ar_loss, L[r].P.A[0].U, L[r].P.A[1].U, s)) != NFSP_OK) return rc;
   NFSP_HIP(hipEventRecord(fork, s));
   if (maxSL > 0) {
     k_res_apply<TABLE><<<dim3(nfsp_blocks(maxSL, 256), 2, R), 256, 0, s>>>(one, tab);
@@ -812,224 +660,8 @@ int launch_group_xchg(float* const* wtab, float* w0, int R, unsigned nets, unsig
   return NFSP_OK;
 }
 
-int join_into(nfsp_engine* e, hipStream_t dst, std::initializer_list<hipStream_t> streams) {
-  for (hipStream_t st : streams) {
-    hipEvent_t j = take_event(e);
-    NFSP_HIP(hipEventRecord(j, st));
-    NFSP_HIP(hipStreamWaitEvent(dst, j, 0));
-    e->pool.push_back(j);      // reusable once the wait is enqueued
-  }
-  return NFSP_OK;
-}
-
 }  // namespace eng
 }  // namespace nfsp
-
-// The exchange a pipelined learner call left pending (nfsp_engine_set_exchange), enqueued on
-// the AR stream behind that call's AR chain, then the AR snapshot it feeds and its event.
-static int flush_exchange(nfsp_engine* e) {
-  if (!e->xchg_pending) return NFSP_OK;
-  e->xchg_pending = false;
-  int rc;
-  {
-    KTimer kx(e, KT_XCHG, e->s_ar);
-    if ((rc = exchange_enqueue(e, e->s_ar)) != NFSP_OK) return rc;
-  }
-  if (e->xchg_pend_snap) {
-    float* snap = e->snap + (size_t)e->xchg_pend_par * 6 * nn::NP;
-    for (int a = 0; a < 2; ++a)
-      NFSP_HIP(hipMemcpyAsync(snap + (a * 3 + 0) * nn::NP, e->w + (a * 3 + 0) * nn::NP,
-                              sizeof(float) * nn::NP, hipMemcpyDeviceToDevice, e->s_ar));
-    NFSP_HIP(hipEventRecord(e->snap_ev[e->xchg_pend_par][0], e->s_ar));
-  }
-  return NFSP_OK;
-}
-
-// One learner call for the pending rollout.  par: the learner-buffer set (slice parity; 0
-// unless cfg.slice_lag 2).  pipelined: leave the chains running (no join into the ctx
-// stream; each BR stream publishes its agent's results itself), and when snap_after, copy
-// the nets into snapshot `par` after the chains and record snap_ev[par] for the rollout two
-// slices on (step_pipelined).
-static int update_impl(nfsp_engine* e, bool pipelined, int par, bool snap_after) {
-  if (!e->pending_update) return NFSP_OK;
-  hipStream_t s = e->ctx->stream;
-  const nfsp_engine_cfg& cfg = e->cfg;
-  // the trigger plan needs the rollout's insert counts: one small readback
-  EngineDev h;
-  NFSP_HIP(hipMemcpyAsync(&h, e->st, sizeof(h), hipMemcpyDeviceToHost, s));
-  NFSP_HIP(hipStreamSynchronize(s));
-  KTimer kt(e, KT_LEARNER);
-  e->LB = e->LBs[par];
-  LearnPlan L;
-  int rc = plan_update(e, h, L);
-  if (rc != NFSP_OK) return rc;
-  commit_plan(e, L);
-  // the cross-shard exchange after this call's AR chain (nfsp_engine_set_exchange)
-  const bool xchg = e->xchg_every > 0 && (++e->xchg_calls) % e->xchg_every == 0;
-  if (pipelined && snap_after)         // the rollout two slices on acts with this epsilon
-    for (int a = 0; a < 2; ++a) e->snap_eps[par][a] = e->hs.epsilon[a];
-  // ---- parallel prep on the ctx stream (launch_prep): the BR streams fork behind the BR rows
-  // (agent 0's BR segments are the learner's critical path), the AR stream behind the AR records
-  hipEvent_t fork_br = take_event(e), fork = take_event(e);
-  {
-    KTimer kprep(e, KT_PREP);
-    if ((rc = launch_prep(e, L, fork_br, fork, s)) != NFSP_OK) return rc;
-  }
-  // the counters, before the next rollout's commit
-  if (pipelined && (rc = launch_finalize(L.F, 1, s)) != NFSP_OK) return rc;
-  float* snap = e->snap + (size_t)par * 6 * nn::NP;
-  // diagnostic (cfg.sched NFSP_SCHED_LEARNER_SERIAL): BR work waits for the AR chains, to time
-  // them alone
-  const bool serial_ar = (e->cfg.sched & NFSP_SCHED_LEARNER_SERIAL) != 0;
-  hipEvent_t ar_done = fork;
-  // ---- AR chains (both agents, one launch) on their own stream.  With the exchange on and
-  // the slices pipelined, this call's exchange (and the AR snapshot it feeds) is enqueued by
-  // the NEXT call, after its prep and BR chains and right before its AR chain (or at the
-  // step's end): an exchange may hold the host until the AR stream reaches it (RCCL's world-1
-  // path synchronises the stream), and this way the host has enqueued everything the other
-  // streams need before it can wait -- the AR stream's next chain needs the exchange anyway.
-  auto ar_part = [&]() -> int {
-    int r;
-    if (pipelined && (r = flush_exchange(e)) != NFSP_OK) return r;
-    NFSP_HIP(hipStreamWaitEvent(e->s_ar, fork, 0));
-    if (L.maxU > 0) {
-      ChainArgs C = chain_args(cfg);
-      for (int a = 0; a < 2; ++a) {
-        C.job[a] = ar_job(e, L, a);
-        if (snap_after && !xchg) C.job[a].snap_to = snap + (a * 3 + 0) * nn::NP;   // written by the chain
-      }
-      KTimer kc(e, KT_CHAIN_AR, e->s_ar);
-      if ((r = launch_chain_ar(C, 2, e->log_loss, e->s_ar)) != NFSP_OK) return r;
-    }
-    if (xchg) {
-      e->xchg_pending = true;
-      e->xchg_pend_par = par;
-      e->xchg_pend_snap = snap_after;
-      if (!pipelined && (r = flush_exchange(e)) != NFSP_OK) return r;
-    } else if (snap_after) {
-      if (L.maxU == 0)                 // no AR chain this call: copy the nets as they are
-        for (int a = 0; a < 2; ++a)
-          NFSP_HIP(hipMemcpyAsync(snap + (a * 3 + 0) * nn::NP, e->w + (a * 3 + 0) * nn::NP,
-                                  sizeof(float) * nn::NP, hipMemcpyDeviceToDevice, e->s_ar));
-      NFSP_HIP(hipEventRecord(e->snap_ev[par][0], e->s_ar));
-    }
-    if (serial_ar) {
-      ar_done = take_event(e);
-      NFSP_HIP(hipEventRecord(ar_done, e->s_ar));
-    }
-    return NFSP_OK;
-  };
-  // ---- BR: per agent on its own stream, segments between target syncs = targets + chain
-  auto br_part = [&]() -> int {
-    int r;
-    for (int a = 0; a < 2; ++a) {
-      hipStream_t sa = e->s_br[a];
-      NFSP_HIP(hipStreamWaitEvent(sa, serial_ar ? ar_done : fork_br, 0));
-      KTimer kspan(e, KT_BR_STREAM0 + a, sa);     // this agent's BR stream, end to end
-      for (size_t gi = 0; gi < L.seg[a].size(); ++gi) {
-        const Segment& sg = L.seg[a][gi];
-        {
-          KTimer kt2(e, KT_TARGETS, sa);
-          r = launch_br_targets(nullptr, br_target_job(e, L, a, sg), sg.v - sg.u, 1, cfg.batch, cfg.epochs, sa);
-        }
-        if (r != NFSP_OK) return r;
-        ChainArgs C = chain_args(cfg);
-        C.job[0] = br_chain_job(e, a, sg);
-        if (snap_after && gi + 1 == L.seg[a].size())            // the last segment writes the snapshot
-          C.job[0].snap_to = snap + (a * 3 + 1) * nn::NP;
-        KTimer kc(e, KT_CHAIN_BR, sa);
-        if ((r = launch_br_chain(C, 1, cfg.quirks, e->log_loss, sa)) != NFSP_OK) return r;
-      }
-      // this agent's learner results, after its chain
-      if (pipelined && (r = launch_finalize(L.F, 2 << a, sa)) != NFSP_OK) return r;
-      if (snap_after) {
-        if (L.seg[a].empty())             // no BR chain this call: copy the net as it is
-          NFSP_HIP(hipMemcpyAsync(snap + (a * 3 + 1) * nn::NP, e->w + (a * 3 + 1) * nn::NP,
-                                  sizeof(float) * nn::NP, hipMemcpyDeviceToDevice, sa));
-        NFSP_HIP(hipEventRecord(e->snap_ev[par][1 + a], sa));
-      }
-    }
-    return NFSP_OK;
-  };
-  // with the exchange on, the BR chains first (they never wait for an exchange), then the AR
-  // chain and the exchange (pipelined: the previous call's exchange, then this call's AR chain;
-  // else this call's, whose host transport synchronises the AR stream -- the BR streams are
-  // busy by then instead of waiting for the host)
-  const bool br_first = e->xchg_every > 0 && !serial_ar;
-  if (br_first) {
-    if ((rc = br_part()) != NFSP_OK) return rc;
-    if ((rc = ar_part()) != NFSP_OK) return rc;
-  } else {
-    if ((rc = ar_part()) != NFSP_OK) return rc;
-    if ((rc = br_part()) != NFSP_OK) return rc;
-  }
-  e->pool.push_back(fork);
-  e->pool.push_back(fork_br);
-  if (ar_done != fork) e->pool.push_back(ar_done);
-  if (pipelined) return NFSP_OK;
-  // ---- join and publish the schedules
-  if ((rc = join_into(e, s, {e->s_ar, e->s_br[0], e->s_br[1]})) != NFSP_OK) return rc;
-  return launch_finalize(L.F, 7, s);
-}
-
-extern "C" int nfsp_engine_update(nfsp_engine* e) {
-  NFSP_REQUIRE(e, "null argument");
-  NFSP_REQUIRE(e->s_ar, "a replica of an engine group is stepped by nfsp_group_step");
-  return update_impl(e, false, 0, false);
-}
-
-namespace nfsp {
-namespace eng {
-// nfsp_engine_step with cfg.slice_lag 2.  Slice j's rollout acts with snapshot j & 1: the
-// nets as of the step's start for j < 2, else as the chains of slice j - 2 left them (copied
-// on each chain stream right after its chain, so slice j - 1's chains may already run).  The
-// ctx stream waits only for those copies, never for the running chains: rollout, readback,
-// plan and prep of slice j overlap slice j - 1's chains, which the chain streams follow
-// without a gap.  The step ends with every stream joined (stats, weights and the next step
-// see all of it).
-int step_pipelined(nfsp_engine* e) {
-  hipStream_t s = e->ctx->stream;
-  const int K = e->slices;
-  for (int p = 0; p < 2; ++p) {
-    NFSP_HIP(hipMemcpyAsync(e->snap + (size_t)p * 6 * nn::NP, e->w, sizeof(float) * 6 * nn::NP,
-                            hipMemcpyDeviceToDevice, s));
-    for (int a = 0; a < 2; ++a) e->snap_eps[p][a] = e->hs.epsilon[a];
-  }
-  int rc;
-  for (int j = 0; j < K; ++j) {
-    const int par = j & 1;
-    if (j >= 2)
-      for (hipEvent_t ev : e->snap_ev[par]) NFSP_HIP(hipStreamWaitEvent(s, ev, 0));
-    if ((rc = rollout_launch_with(e, e->snap + (size_t)par * 6 * nn::NP, e->snap_eps[par])) != NFSP_OK)
-      return rc;
-    if ((rc = update_impl(e, true, par, j + 2 < K)) != NFSP_OK) return rc;
-  }
-  if ((rc = flush_exchange(e)) != NFSP_OK) return rc;    // the last slice's
-  return join_into(e, s, {e->s_ar, e->s_br[0], e->s_br[1]});   // the side streams' work so far
-}
-}  // namespace eng
-}  // namespace nfsp
-
-extern "C" int nfsp_engine_snapshot(nfsp_engine* e, int parity, float** dev_w, double* eps) {
-  NFSP_REQUIRE(e && dev_w && eps && (parity == 0 || parity == 1), "bad argument");
-  NFSP_REQUIRE(e->snap, "the engine has no snapshots (cfg.slice_lag 1)");
-  *dev_w = e->snap + (size_t)parity * 6 * nn::NP;
-  if (e->snap_eps_dev) {               // a group replica: its snapshots' epsilons are on device
-    NFSP_HIP(hipMemcpyAsync(eps, e->snap_eps_dev + 2 * parity, 2 * sizeof(double), hipMemcpyDeviceToHost,
-                            e->ctx->stream));
-    NFSP_HIP(hipStreamSynchronize(e->ctx->stream));
-    return NFSP_OK;
-  }
-  eps[0] = e->snap_eps[parity][0];
-  eps[1] = e->snap_eps[parity][1];
-  return NFSP_OK;
-}
-
-extern "C" int nfsp_engine_set_update_limit(nfsp_engine* e, int64_t max_updates) {
-  NFSP_REQUIRE(e && max_updates >= 0, "bad argument");
-  e->update_limit = max_updates;
-  return NFSP_OK;
-}
 
 #ifdef NFSP_BRP_STAMPS
 extern "C" int nfsp_debug_brp_stamps(unsigned long long* out, int reset) {

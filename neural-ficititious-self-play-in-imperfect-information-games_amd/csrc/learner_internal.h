@@ -1,6 +1,7 @@
-// What learner.hip (the learner's kernels, the one-engine learner call, the launchers) shares
-// with group.hip (the engine group's host code): the plain structs a learner call's tables are
-// built from, the plan of one engine's call, and the host launchers of learner.hip's kernels.
+// What learner.hip (the learner's kernels and their host launchers) shares with the host code
+// of a learner call -- engine_update.hip (one engine) and group.hip (an engine group): the plain
+// structs a call's arguments and tables are built from, the plan of one engine's call and its
+// jobs (engine_update.hip), and the launchers.
 #pragma once
 #include <initializer_list>
 #include <vector>
@@ -12,15 +13,7 @@
 namespace nfsp {
 namespace eng {
 
-struct AgentPlan {
-  int64_t P0;          // agent's RL inserts before the last rollout
-  int64_t m_first;     // first trigger index (trigger m at RL stream position m * c)
-  int64_t U;           // triggers in the last rollout
-  int64_t m_br0;       // first trigger with a BR update (position > batch)
-  int64_t U_br;
-  int64_t n_sl;        // SL records of the last rollout
-  int64_t sl_total0;   // SL inserts before the last rollout
-};
+using AgentPlan = plan::AgentPlan;   // learn_plan.h
 
 struct PrepArgs {
   Memories M;
@@ -93,25 +86,29 @@ struct FinalArgs {
 using Segment = plan::Segment;   // BR updates [u, v) of the learner call; sync: ends with a target sync
 
 struct LearnPlan {
+  int par;                   // the learner-buffer set of the call: P.LB = LBs[par]
   PrepArgs P;
   int64_t maxU = 0, maxUbr = 0, maxSL = 0;
   std::vector<Segment> seg[2];
+  int64_t ar_u1[2];          // the AR chains' update bound: U, or what the update limit leaves
   int64_t it0[2];
   FinalArgs F;
   nfsp_engine::Sched hs;     // the schedules after this call (commit_plan publishes them)
 };
 
-// The learner call's plan from the rollout's insert counts and the host's schedule mirror.
-// Leaves the engine untouched: commit_plan(e, L) adopts it once every plan of the call (a
-// group's replicas) has succeeded, so a failed plan changes no replica's schedules.
-int plan_update(const nfsp_engine* e, const EngineDev& h, LearnPlan& L);
+// The learner call's plan (learn_plan.h) from the rollout's insert counts and the host's schedule
+// mirror, wired to the engine's memories and its learner-buffer set `par` (slice parity; 0 unless
+// cfg.slice_lag 2).  Leaves the engine untouched: commit_plan(e, L) adopts it once every plan of
+// the call (a group's replicas) has succeeded, so a failed plan changes no replica's schedules.
+int plan_update(const nfsp_engine* e, int par, const EngineDev& h, LearnPlan& L);
 void commit_plan(nfsp_engine* e, const LearnPlan& L);
 
+// The jobs read the buffer set from the plan (L.P.LB).
 // the AR chain of agent a over the whole learner call
 chain::ChainJob ar_job(const nfsp_engine* e, const LearnPlan& L, int a);
 // a BR segment of agent a: its targets and its chain
 TargetJob br_target_job(const nfsp_engine* e, const LearnPlan& L, int a, const Segment& sg);
-chain::ChainJob br_chain_job(const nfsp_engine* e, int a, const Segment& sg);
+chain::ChainJob br_chain_job(const nfsp_engine* e, const LearnPlan& L, int a, const Segment& sg);
 
 // a chain launch's arguments: the cfg's batch and epochs; jobs / lds: a group's device job table
 // and LDS per workgroup (one engine: the jobs go into C.job, a CU each)
@@ -124,8 +121,8 @@ inline chain::ChainArgs chain_args(const nfsp_engine_cfg& cfg, const chain::Chai
   return C;
 }
 
-// The work of `streams` so far joined into `dst`: per stream an event of e's pool, recorded on
-// it, awaited by dst and returned to the pool (reusable once the wait is enqueued).
+// (engine_update.hip) The work of `streams` so far joined into `dst`: per stream an event of e's
+// pool, recorded on it, awaited by dst and returned to the pool (reusable once the wait is enqueued).
 int join_into(nfsp_engine* e, hipStream_t dst, std::initializer_list<hipStream_t> streams);
 
 // ---- launchers (learner.hip).  The one-engine form of a kernel takes its arguments by value,

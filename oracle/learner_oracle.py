@@ -1,5 +1,5 @@
-"""TEST INFRASTRUCTURE ONLY -- the engine's learner step (csrc/learner.hip, nfsp_engine_update)
-restated in numpy, so one whole engine step can be replayed update by update.
+"""TEST INFRASTRUCTURE ONLY -- the engine's learner step (nfsp_engine_update: csrc/engine_update.hip,
+the plan csrc/learn_plan.h, the kernels csrc/learner.hip) restated in numpy, so one whole engine step can be replayed update by update.
 
 Only ``tests/`` imports this module; it is a checker, never the thing measured or shipped.
 
@@ -161,6 +161,22 @@ def ar_minibatches(cfg, state, a, quirks=7, slots=None, build_below=None):
         yield u, xb, ya, perms
 
 
+def trigger_plan(c, B, st):
+    """An agent's triggers of the last rollout: (m_first, U, m_br0, U_br) -- U triggers from
+    trigger m_first, the last U_br of them, from m_br0, with a BR update."""
+    P0 = st["rl_total"] - st["last_rl"]
+    m_first = P0 // c + 1
+    m_last = (P0 + st["last_rl"]) // c
+    m_br0 = max(m_first, B // c + 1)
+    return m_first, max(0, m_last - m_first + 1), m_br0, max(0, m_last - m_br0 + 1)
+
+
+def next_schedule(cfg, quirks, it, eps):
+    """(iteration, epsilon) after one more BR update."""
+    it += 2
+    return it, cfg["epsilon"] if quirks & EXT_EPS_CONST else eps / it
+
+
 def learner_step(cfg, state, quirks=7, max_updates=None, trace=None):
     """Replay nfsp_engine_update.
 
@@ -183,12 +199,7 @@ def learner_step(cfg, state, quirks=7, max_updates=None, trace=None):
     out = []
     for a in (0, 1):
         st = state[a]
-        P0 = st["rl_total"] - st["last_rl"]
-        m_first = P0 // c + 1
-        m_last = (P0 + st["last_rl"]) // c
-        U = max(0, m_last - m_first + 1)
-        m_br0 = max(m_first, B // c + 1)
-        U_br = max(0, m_last - m_br0 + 1)
+        _, U, m_br0, U_br = trigger_plan(c, B, st)
         log_cap = len(st["rl_s_bits"])
         ar = nn.MLP(nn.ACT_SOFTMAX, 64, weights=nn.unpack_weights(st["w"][0]))
         br_act = (nn.ACT_LINEAR_MSE if quirks & EXT_MSE_Q else nn.ACT_LINEAR) if quirks & EXT_LINEAR_Q \
@@ -223,11 +234,9 @@ def learner_step(cfg, state, quirks=7, max_updates=None, trace=None):
                 tg.set_weights(br.get_weights())
             if trace is not None:
                 trace(a, 1, u, br.flat())
-            it += 2
-            eps = cfg["epsilon"] if quirks & EXT_EPS_CONST else eps / it
+            it, eps = next_schedule(cfg, quirks, it, eps)
         for u in range(lim(U_br), U_br):      # schedules of updates past the prefix
-            it += 2
-            eps = cfg["epsilon"] if quirks & EXT_EPS_CONST else eps / it
+            it, eps = next_schedule(cfg, quirks, it, eps)
         # ---- AR updates, the reservoir as of each trigger
         n_sl = st["last_sl"]
         sl0 = st["sl_total"] - n_sl

@@ -333,3 +333,37 @@ def test_pipelined_step_equals_its_declared_schedule(pkg):
             assert np.array_equal(ma[k], mb[k]), (p, k)
         n = int(sa["sl_size"][p])
         assert np.array_equal(a.memories(p)["sl_a"][:n].cpu().numpy(), b.memories(p)["sl_a"][:n].cpu().numpy())
+
+
+@pytest.mark.parametrize("n_lanes,K", [(3072, 3), (2048, 2)])
+def test_pipelined_loss_log_is_the_last_calls(pkg, n_lanes, K):
+    """The loss log of a pipelined engine (slice_lag 2) is that of its last learner call, whichever
+    learner-buffer set that call used: K = 3 ends a step on set 0, K = 2 on set 1.  Its lag-1
+    twin, driven slice by slice as the declared schedule says (one buffer set), reports the same
+    losses after every step, key by key, and the same stats."""
+    kw = dict(n_lanes=n_lanes, slices=K, inserts_per_update=64, rl_capacity=3000, sl_capacity=2000,
+              target_every=7, seed=5150, init_seed=7)
+    a = pkg.engine.SelfPlayEngine(slice_lag=2, **kw)
+    b = pkg.engine.SelfPlayEngine(slice_lag=1, **kw)
+    a.set_loss_log()
+    b.set_loss_log()
+    seen = {"rl": False, "sl": False}
+    for step in range(2):
+        a.step()
+        snap = [_weights_flat(b)] * 2
+        eps = [tuple(float(v) for v in b.stats()["epsilon"])] * 2
+        for j in range(K):
+            b.rollout_with(snap[j & 1], eps[j & 1])
+            b.update()
+            if j + 2 < K:
+                snap[j & 1] = _weights_flat(b)
+                eps[j & 1] = tuple(float(v) for v in b.stats()["epsilon"])
+        la, lb = a.losses(), b.losses()
+        print(step, la)
+        assert la.keys() == lb.keys() and len(la) == 8
+        for k in la:
+            assert la[k] == lb[k] or (np.isnan(la[k]) and np.isnan(lb[k])), (step, k, la[k], lb[k])
+            seen[k[7:9]] |= not np.isnan(la[k])
+        sa, sb = a.stats(), b.stats()
+        assert sa == sb, (step, {k: (sa[k], sb[k]) for k in sa if sa[k] != sb[k]})
+    assert seen == {"rl": True, "sl": True}, seen      # the comparison was of numbers, BR and AR

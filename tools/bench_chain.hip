@@ -20,15 +20,10 @@
 #include "chain_ref.hip"
 #include "chain8_probe.h"
 
-// the host helpers learner.hip's nfsp_engine_update references (unused here)
+// the error helpers of learner.hip's launchers (unused here)
 namespace nfsp {
 int fail(int code, const std::string&) { return code; }
 int hip_fail(hipError_t, const char*) { return NFSP_EHIP; }
-namespace eng {
-hipEvent_t take_event(nfsp_engine*) { return nullptr; }
-int exchange_enqueue(nfsp_engine*, hipStream_t) { return NFSP_EINVAL; }
-int rollout_launch_with(nfsp_engine*, const float*, const double*) { return NFSP_EINVAL; }
-}
 }
 namespace nfsp { namespace chain {
 int launch_chain_br_linear(const ChainArgs&, int, bool, bool, hipStream_t) { return NFSP_EINVAL; }
