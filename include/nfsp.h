@@ -593,6 +593,78 @@ int nfsp_exploitability(nfsp_ctx* ctx, const float* dev_w_ar0, const float* dev_
 int nfsp_exploitability_batch(nfsp_ctx* ctx, const float* const* dev_w_ar0, const float* const* dev_w_ar1,
                               int n, int mode, double* out /*[4n]*/);
 
+/* ---- the evaluator's tree as data (host only: no device, no ctx) ----
+ * The public tree both dealers' hands of `game` run through, exactly the tables the device
+ * walks (csrc/exploit_tree.h), in depth order: a level's nodes are contiguous and a parent
+ * precedes its children.  Replaces reading information sets out of the CPU oracle's Env
+ * (tests/studies/kuhn_policy.py).  kind: 0 decision, 1 chance, 2 terminal.  p: the acting
+ * seat (decision) or the seat of the ending step (terminal).  via: the executed action that
+ * leads here from a decision parent, the public rank from a chance parent.  child: by executed
+ * action (decision) or public rank (chance), -1 where there is none (an illegal raise).  row:
+ * a decision's row of obs / legal / every policy table, a terminal's row of pay. */
+typedef struct {
+  int8_t kind, p, via, nchild;
+  int32_t parent;                       /* -1 at the two roots */
+  int32_t child[3];
+  int32_t row;
+} nfsp_tree_node;                       /* 24 bytes */
+int nfsp_tree_size(int game, int32_t* nn, int32_t* ndec, int32_t* nterm, int32_t* nlev);
+/* obs[d][r]: the acting seat's observation bits at decision row d holding rank r.  legal[d]:
+ * bit 0 = a raise is executed as a raise there, bits 1.. = the acting seat.  pay[t][i][ri][ro]:
+ * seat i's reward at terminal row t with rank ri against rank ro.  lev: level k is nodes
+ * [lev[k], lev[k + 1]).  root: by dealer.  deal[a][b]: P(one seat's rank a, the other's b). */
+int nfsp_tree_export(int game, nfsp_tree_node* nodes /*[nn]*/, uint32_t* obs /*[ndec][3]*/,
+                     uint8_t* legal /*[ndec]*/, float* pay /*[nterm][2][3][3]*/, int32_t* lev /*[nlev+1]*/,
+                     int32_t* root /*[2]*/, double* deal /*[3][3]*/);
+
+/* ---- policies of any kind, scored exactly ----
+ * A policy is a net read one of four ways or a table.  Replaces the CPU-only studies
+ * (tests/studies/kuhn_diag.py br_gap / anticip, kuhn_policy.py) and builds the evaluator the
+ * reference left commented out (main.py:82-120: the BR player against the AR player). */
+#define NFSP_POL_AR_SOFTMAX 0        /* packed f32 net: as nfsp_exploitability mode 0 */
+#define NFSP_POL_AR_ARGMAX 1         /* packed f32 net: as mode 1 */
+#define NFSP_POL_BR_GREEDY 2         /* packed f32 net, ReLU Q head: one-hot argmax, first max wins (an
+                                        all-zero head folds), an illegal raise becomes call: what
+                                        k_rollout executes without the epsilon branch */
+#define NFSP_POL_BR_GREEDY_LINEAR 3  /* the same with the linear head of NFSP_EXT_LINEAR_Q */
+#define NFSP_POL_TABLE 4             /* f64 [ndec][3 ranks][3 actions], rows as nfsp_tree_export's; an
+                                        illegal raise's mass goes to call */
+typedef struct {
+  int32_t kind;                         /* NFSP_POL_* */
+  int32_t reserved;                     /* 0 */
+  const void* dev;                      /* device pointer: the net or the table */
+} nfsp_policy;
+/* Pair k plays seat0[k] at seat 0 against seat1[k] at seat 1.  out[6k..6k+5]: seat 0's best-response
+ * value against seat1[k], seat 1's against seat0[k], their sum, seat 0's on-policy value, and that
+ * value over dealer-0 hands only and over dealer-1 hands only (value0 = half their sum).  One
+ * workgroup per pair (csrc/evaluate.hip k_evaluate: k_exploit_walk's three phases, f64, same
+ * sums); with kinds 0 / 1 on both seats the first four equal nfsp_exploitability's bits.
+ * Synchronises the ctx stream. */
+int nfsp_evaluate_batch(nfsp_ctx* ctx, const nfsp_policy* seat0, const nfsp_policy* seat1, int n,
+                        double* out /*[6n]*/);
+/* The policy as the walk executes it (after the remap), at every decision row and rank, into
+ * dev_out[ndec][3][3] (f64, device); rows where the other seat acts are filled too.  Scoring the
+ * table gives the bits scoring the policy gives.  Replaces kuhn_policy.py's per-information-set
+ * read-out through the oracle's Env.  Synchronises the ctx stream. */
+int nfsp_policy_table(nfsp_ctx* ctx, const nfsp_policy* policy, double* dev_out);
+
+/* ---- CFR+ on the evaluator's tree (csrc/cfr.hip k_cfr_plus) ----
+ * A tabular equilibrium of the game as played here: the absolute anchor the Leduc variant lacked
+ * (Kuhn's is analytic; the reference has no solver).  Alternating updates, regret-matching+,
+ * linearly weighted average (Tammelin 2014).  One workgroup, all state in LDS as f64 during a
+ * launch and in device memory between launches; a run is cut into launches of at most
+ * NFSP_CFR_LAUNCH_ITERS iterations. */
+#define NFSP_CFR_LAUNCH_ITERS 1024
+typedef struct nfsp_cfr nfsp_cfr;
+int nfsp_cfr_create(nfsp_ctx* ctx, nfsp_cfr** out);
+int nfsp_cfr_run(nfsp_cfr* h, int64_t iters);          /* continues the run; synchronises */
+int nfsp_cfr_iterations(nfsp_cfr* h, int64_t* out);
+/* The average strategy after the last run (uniform over legal actions before any), a device
+ * table usable as NFSP_POL_TABLE; owned by the handle. */
+int nfsp_cfr_average(nfsp_cfr* h, const double** dev_table);
+int nfsp_cfr_state(nfsp_cfr* h, double* host_R /*[ndec][3][3]*/, double* host_S /*[ndec][3][3]*/);
+int nfsp_cfr_destroy(nfsp_cfr* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -244,6 +244,23 @@ class SelfPlayEngine:
         mode 0 = softmax mixed strategies, 1 = the argmax the env executes."""
         return exploitability(self.ctx, self._wptr(0, NET_AR), self._wptr(1, NET_AR), mode)
 
+    def policy(self, agent: int, net: int = NET_AR, mode: int = 0):
+        """An ``evaluation.Policy`` reading this engine's weights in place: the AR net as its
+        softmax / argmax, or the BR net played greedily (the head kind from ``cfg.quirks``)."""
+        from . import evaluation
+        if net == NET_AR:
+            return evaluation.Policy.ar(self._wptr(agent, NET_AR), mode, owner=self)
+        return evaluation.Policy.br(self._wptr(agent, net), bool(self.cfg.quirks & native.EXT_LINEAR_Q), owner=self)
+
+    def br_gap(self, ar_mode: int = 0, eta: float | None = None) -> list:
+        """How far each agent's learned best response is from a true one (kuhn_diag's br_gap,
+        exact and on the device).  Per agent i (= seat i): ``br_exact``, the best-response value
+        against the other seat's AR policy; ``br_learned``, the value of i's greedy BR net
+        against it; ``gap`` = their difference (>= 0).  With ``eta`` the opponent is the per-hand
+        mixture eta x greedy BR + (1 - eta) x AR it plays in self-play (``evaluation.mix``):
+        kuhn_diag's ``anticip``."""
+        return _br_gaps(self.ctx, [self], ar_mode, eta)[0]
+
     # -- checkpoints (checkpoint.py, DESIGN.md §10) ----------------------------------
     def save(self, path):
         """Save the engine at a step boundary (nfsp_engine_save_state); returns the bytes written."""
@@ -444,6 +461,19 @@ class EngineGroup:
         w1 = [e._wptr(1, NET_AR) for e in self.replicas]
         return exploitability_batch(self.ctx, w0, w1, mode)
 
+    def br_gap_all(self, ar_mode: int = 0, eta: float | None = None) -> list:
+        """``SelfPlayEngine.br_gap`` of every replica, in one batch call (two pairs per replica)."""
+        return _br_gaps(self.ctx, self.replicas, ar_mode, eta)
+
+    def crossplay(self, mode: int = 0) -> np.ndarray:
+        """[R, R]: seat 0's value when replica i's AR net at seat 0 plays replica j's AR net at
+        seat 1, all R x R pairs in one batch call (nfsp_evaluate_batch)."""
+        from . import evaluation
+        p0 = [e.policy(0, NET_AR, mode) for e in self.replicas]
+        p1 = [e.policy(1, NET_AR, mode) for e in self.replicas]
+        res = evaluation.evaluate_batch(self.ctx, [(a, b) for a in p0 for b in p1])
+        return np.array([r["value0"] for r in res]).reshape(self.R, self.R)
+
     # -- checkpoints (checkpoint.py, DESIGN.md §10) ----------------------------------
     def save(self, path):
         """Save the group at a step boundary (nfsp_group_save_state): every replica, and the
@@ -508,6 +538,32 @@ def exploitability_batch(ctx, dev_w_ar0: list, dev_w_ar1: list, mode: int = 0) -
     native.check(ctx.L.nfsp_exploitability_batch(ctx.h, a0, a1, n, mode, out), "nfsp_exploitability_batch")
     return [{"br0": out[4 * k], "br1": out[4 * k + 1], "exploitability": out[4 * k + 2], "value0": out[4 * k + 3]}
             for k in range(n)]
+
+
+def _br_gaps(ctx, engines, ar_mode, eta) -> list:
+    """br_gap of each engine: per agent {br_exact, br_learned, gap}; one nfsp_evaluate_batch."""
+    from . import evaluation as ev
+    pairs = []
+    keep = []
+    tree = ev.GameTree(ctx.game) if eta is not None else None
+    for e in engines:
+        opp = []
+        for o in (0, 1):                       # the policy agent 1 - o faces at seat o
+            if eta is None:
+                opp.append(e.policy(o, NET_AR, ar_mode))
+            else:
+                ar = ev.policy_table(ctx, e.policy(o, NET_AR, ar_mode), tree).cpu().numpy()
+                br = ev.policy_table(ctx, e.policy(o, NET_BR), tree).cpu().numpy()
+                opp.append(ev.Policy.table(ev.mix(tree, [(eta, br), (1.0 - eta, ar)])))
+        keep.append(opp)
+        pairs += [(e.policy(0, NET_BR), opp[1]), (opp[0], e.policy(1, NET_BR))]
+    res = ev.evaluate_batch(ctx, pairs)
+    out = []
+    for k in range(len(engines)):
+        r0, r1 = res[2 * k], res[2 * k + 1]
+        out.append([{"br_exact": r0["br0"], "br_learned": r0["value0"], "gap": r0["br0"] - r0["value0"]},
+                    {"br_exact": r1["br1"], "br_learned": -r1["value0"], "gap": r1["br1"] + r1["value0"]}])
+    return out
 
 
 def _wrap_device(addr, numel, dtype, device, owner=None) -> torch.Tensor:

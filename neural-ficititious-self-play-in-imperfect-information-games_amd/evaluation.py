@@ -1,0 +1,281 @@
+"""Exact evaluation of any policy, and a tabular equilibrium to measure against.
+
+``engine.exploitability`` scores a pair of AR nets.  This module scores every kind of policy
+the project meets, on the same public tree and with the same f64 walk
+(``nfsp_evaluate_batch``, csrc/evaluate.hip):
+
+* ``Policy.ar(w, mode)``    an average-policy net, as its softmax (mode 0) or argmax (mode 1);
+* ``Policy.br(w, linear)``  a best-response net played greedily, as the rollout executes it
+                            when the epsilon draw does not fire (first maximum wins, an illegal
+                            raise becomes a call) -- the learned best response of the evaluator
+                            the reference left commented out (main.py:82-120);
+* ``Policy.table(t)``       a behavioural strategy ``[ndec][3 ranks][3 actions]`` over the rows of
+                            ``GameTree``: a net read out with ``policy_table``, a ``mix`` of
+                            tables, a ``CfrSolver`` average, anything written by hand.
+
+``GameTree`` (host only, no GPU) is the tree as data; ``CfrSolver`` runs CFR+ on it
+(``nfsp_cfr_*``, csrc/cfr.hip), which anchors the Leduc variant the way the analytic Nash
+family anchors Kuhn.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import native
+
+DECISION, CHANCE, TERMINAL = 0, 1, 2
+ACTIONS = ("fold", "call", "raise")
+NODE_DTYPE = np.dtype([("kind", "i1"), ("p", "i1"), ("via", "i1"), ("nchild", "i1"), ("parent", "<i4"),
+                       ("child", "<i4", (3,)), ("row", "<i4")])
+RESULT_KEYS = ("br0", "br1", "exploitability", "value0", "value0_dealer0", "value0_dealer1")
+
+
+class GameTree:
+    """The evaluator's public tree of ``game`` (``nfsp_tree_export``), in depth order.
+
+    ``nodes`` (NODE_DTYPE), ``obs[ndec, 3]``, ``legal[ndec]`` (whether a raise is executed as a
+    raise), ``seat[ndec]`` (who acts), ``pay[nterm, 2, 3, 3]``, ``lev[nlev + 1]``, ``root[2]``
+    (by dealer), ``deal[3, 3]``; ``node_of_row[ndec]`` maps a decision row back to its node."""
+
+    def __init__(self, game: int = native.GAME_LEDUC):
+        L = native.load()
+        self.game = int(game)
+        n = [C.c_int32(0) for _ in range(4)]
+        native.check(L.nfsp_tree_size(self.game, *[C.byref(x) for x in n]), "nfsp_tree_size")
+        self.nn, self.ndec, self.nterm, self.nlev = (x.value for x in n)
+        self.nodes = np.zeros(self.nn, NODE_DTYPE)
+        assert NODE_DTYPE.itemsize == C.sizeof(native.TreeNode) == 24
+        self.obs = np.zeros((self.ndec, 3), np.uint32)
+        bits = np.zeros(self.ndec, np.uint8)
+        self.pay = np.zeros((self.nterm, 2, 3, 3), np.float32)
+        self.lev = np.zeros(self.nlev + 1, np.int32)
+        self.root = np.zeros(2, np.int32)
+        self.deal = np.zeros((3, 3), np.float64)
+        native.check(L.nfsp_tree_export(self.game, *[a.ctypes.data_as(native.P) for a in (
+            self.nodes, self.obs, bits, self.pay, self.lev, self.root, self.deal)]), "nfsp_tree_export")
+        self.legal = (bits & 1).astype(bool)
+        self.seat = (bits >> 1).astype(np.int8)
+        self.node_of_row = np.full(self.ndec, -1, np.int32)
+        dec = np.nonzero(self.nodes["kind"] == DECISION)[0]
+        self.node_of_row[self.nodes["row"][dec]] = dec
+        self._rows = {(int(self.seat[d]), int(self.obs[d, r])): (d, r)
+                      for d in range(self.ndec) for r in range(3)}
+
+    def row_of(self, seat: int, obs: int) -> tuple:
+        """(row, rank) of the information set in which ``seat`` observes ``obs`` (30 bits)."""
+        return self._rows[(int(seat), int(obs))]
+
+    def path(self, row: int) -> tuple:
+        """(dealer, [node ids from the root to the decision of ``row``])."""
+        chain = [int(self.node_of_row[row])]
+        while self.nodes["parent"][chain[-1]] >= 0:
+            chain.append(int(self.nodes["parent"][chain[-1]]))
+        chain.reverse()
+        return int(np.nonzero(self.root == chain[0])[0][0]), chain
+
+    def describe(self, row: int) -> str:
+        """The decision of ``row`` as text: the dealer, the executed actions so far (by seat),
+        the public rank once it is dealt, and who acts."""
+        dealer, chain = self.path(row)
+        parts, public = [], None
+        for par, n in zip(chain[:-1], chain[1:]):
+            via = int(self.nodes["via"][n])
+            if self.nodes["kind"][par] == CHANCE:
+                public = via
+                parts.append(f"| public {via} |")
+            else:
+                parts.append(f"{int(self.nodes['p'][par])}:{ACTIONS[via]}")
+        hist = " ".join(parts) if parts else "-"
+        pub = "none" if public is None else str(public)
+        return (f"dealer {dealer}, history {hist}, public rank {pub}, seat {int(self.seat[row])} to act"
+                f"{'' if self.legal[row] else ' (raise -> call)'}")
+
+    def uniform(self) -> np.ndarray:
+        """The table that is uniform over the legal actions of every row."""
+        t = np.zeros((self.ndec, 3, 3))
+        t[self.legal] = 1.0 / 3.0
+        t[~self.legal, :, :2] = 0.5
+        return t
+
+    def remap(self, table) -> np.ndarray:
+        """``table`` as executed: an illegal raise's mass goes to call (the env's remap)."""
+        t = np.array(table, np.float64).reshape(self.ndec, 3, 3)
+        il = ~self.legal
+        t[il, :, 1] = t[il, :, 1] + t[il, :, 2]
+        t[il, :, 2] = 0.0
+        return t
+
+    def own_reach(self, table) -> np.ndarray:
+        """[ndec, 3]: the product of the acting seat's own action probabilities (holding rank
+        r, under ``table`` as executed) along the path to each decision."""
+        t = self.remap(table)
+        reach = np.ones((self.nn, 2, 3))          # [node][seat][that seat's rank]
+        N = self.nodes
+        for n in range(self.nn):                  # depth order: parents first
+            par = int(N["parent"][n])
+            if par < 0:
+                continue
+            reach[n] = reach[par]
+            if N["kind"][par] == DECISION:
+                reach[n, N["p"][par]] = reach[par, N["p"][par]] * t[N["row"][par], :, N["via"][n]]
+        return reach[self.node_of_row, self.seat.astype(int)]
+
+
+def mix(tree: GameTree, parts) -> np.ndarray:
+    """The behavioural strategy realisation-equivalent to drawing table k with probability
+    w_k once **per hand** and playing it to the end (Kuhn's theorem) -- how self-play mixes
+    the BR and AR nets (one eta draw per hand and agent, main.py:36-45), so
+    ``mix(tree, [(eta, br_table), (1 - eta, ar_table)])`` is the policy an NFSP agent plays.
+
+    Row (d, r) is the tables' rows weighted by w_k x the own reach of (d, r) under table k
+    (``GameTree.own_reach``); where that total is 0 the row is uniform over the legal actions.
+    The result serves either seat: each row only uses the reach of the seat acting there.
+
+    A mixture drawn anew at every decision needs none of this, it is plain row arithmetic:
+    epsilon-greedy with the reference's random action (agent/agent.py:124-128 draws three
+    uniforms and the env takes their argmax, i.e. uniform over the three actions, then the
+    remap) is ``(1 - eps) * greedy + eps * tree.remap(np.full_like(greedy, 1 / 3))``."""
+    num = np.zeros((tree.ndec, 3, 3))
+    den = np.zeros((tree.ndec, 3))
+    for w, table in parts:
+        t = tree.remap(table)
+        wr = float(w) * tree.own_reach(t)
+        num = num + wr[:, :, None] * t
+        den = den + wr
+    out = tree.uniform()
+    nz = den > 0
+    out[nz] = num[nz] / den[nz][:, None]
+    return out
+
+
+class Policy:
+    """A policy spec (``nfsp_policy``): a kind and the device memory it reads, kept alive here."""
+
+    def __init__(self, kind: int, data=None, ptr: int | None = None, owner=None):
+        self.kind = int(kind)
+        self.data = data            # a torch tensor on the device, or None for a borrowed pointer
+        self.owner = owner          # whatever owns a borrowed pointer
+        self.ptr = int(data.data_ptr() if ptr is None else ptr)
+
+    @staticmethod
+    def _dev(x, dtype, numel=None):
+        import torch
+        if isinstance(x, int):
+            return None, x
+        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(x))
+        t = t.to(device="cuda", dtype=dtype).contiguous().reshape(-1)
+        if numel is not None and t.numel() != numel:
+            raise ValueError(f"expected {numel} values, got {t.numel()}")
+        return t, None
+
+    @classmethod
+    def ar(cls, weights, mode: int = 0, owner=None) -> "Policy":
+        """An AR net (packed f32 weights: array, tensor or device address), softmax or argmax."""
+        import torch
+        if mode not in (0, 1):
+            raise ValueError("mode must be 0 (softmax) or 1 (argmax)")
+        t, p = cls._dev(weights, torch.float32, 30 * 64 + 64 + 64 * 3 + 3)
+        return cls(native.POL_AR_ARGMAX if mode else native.POL_AR_SOFTMAX, t, p, owner)
+
+    @classmethod
+    def br(cls, weights, linear: bool = False, owner=None) -> "Policy":
+        """A BR net played greedily; ``linear`` for the Q head of ``EXT_LINEAR_Q``."""
+        import torch
+        t, p = cls._dev(weights, torch.float32, 30 * 64 + 64 + 64 * 3 + 3)
+        return cls(native.POL_BR_GREEDY_LINEAR if linear else native.POL_BR_GREEDY, t, p, owner)
+
+    @classmethod
+    def table(cls, table, owner=None) -> "Policy":
+        """A table ``[ndec][3][3]`` of doubles (array, tensor or device address)."""
+        import torch
+        t, p = cls._dev(table, torch.float64)
+        return cls(native.POL_TABLE, t, p, owner)
+
+    def spec(self) -> native.PolicySpec:
+        return native.PolicySpec(self.kind, 0, native.P(self.ptr))
+
+
+def _result(out, k):
+    return {key: out[6 * k + j] for j, key in enumerate(RESULT_KEYS)}
+
+
+def evaluate_batch(ctx, pairs) -> list:
+    """``nfsp_evaluate_batch``: for every (policy at seat 0, policy at seat 1) the best-response
+    values br0 / br1 against the other seat's policy, their sum, seat 0's on-policy value and
+    that value over dealer-0 / dealer-1 hands only.  One workgroup per pair."""
+    n = len(pairs)
+    s0 = (native.PolicySpec * max(n, 1))(*[a.spec() for a, _ in pairs])
+    s1 = (native.PolicySpec * max(n, 1))(*[b.spec() for _, b in pairs])
+    out = (C.c_double * (6 * max(n, 1)))()
+    native.check(ctx.L.nfsp_evaluate_batch(ctx.h, s0, s1, n, out), "nfsp_evaluate_batch")
+    return [_result(out, k) for k in range(n)]
+
+
+def evaluate(ctx, seat0: Policy, seat1: Policy) -> dict:
+    return evaluate_batch(ctx, [(seat0, seat1)])[0]
+
+
+def policy_table(ctx, policy: Policy, tree: GameTree | None = None):
+    """``nfsp_policy_table``: the policy as executed at every row, a float64 device tensor
+    ``[ndec, 3, 3]`` (``Policy.table`` of it scores bit-identically to ``policy``)."""
+    import torch
+    tree = tree or GameTree(ctx.game)
+    out = torch.empty((tree.ndec, 3, 3), dtype=torch.float64, device="cuda")
+    spec = policy.spec()
+    native.check(ctx.L.nfsp_policy_table(ctx.h, C.byref(spec), native.P(out.data_ptr())), "nfsp_policy_table")
+    return out
+
+
+class CfrSolver:
+    """CFR+ on the evaluator's tree (``nfsp_cfr_*``): ``run(n)`` continues the run by n
+    iterations, ``average()`` is the linearly weighted average strategy as a ``Policy``."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.tree = GameTree(ctx.game)
+        h = native.P()
+        native.check(ctx.L.nfsp_cfr_create(ctx.h, C.byref(h)), "nfsp_cfr_create")
+        self.h = h
+
+    def run(self, iters: int) -> "CfrSolver":
+        native.check(self.ctx.L.nfsp_cfr_run(self.h, int(iters)), "nfsp_cfr_run")
+        return self
+
+    @property
+    def iterations(self) -> int:
+        n = native.I64(0)
+        native.check(self.ctx.L.nfsp_cfr_iterations(self.h, C.byref(n)), "nfsp_cfr_iterations")
+        return n.value
+
+    def average(self) -> Policy:
+        p = native.P()
+        native.check(self.ctx.L.nfsp_cfr_average(self.h, C.byref(p)), "nfsp_cfr_average")
+        return Policy(native.POL_TABLE, None, p.value, self)
+
+    def average_table(self) -> np.ndarray:
+        import torch
+        from .engine import _wrap_device
+        t = _wrap_device(self.average().ptr, self.tree.ndec * 9, torch.float64,
+                         torch.device("cuda", torch.cuda.current_device()), self)
+        return t.cpu().numpy().reshape(self.tree.ndec, 3, 3).copy()
+
+    def state(self) -> tuple:
+        """(R, S): the regrets and the strategy sums, ``[ndec, 3, 3]`` each."""
+        R = np.zeros((self.tree.ndec, 3, 3))
+        S = np.zeros((self.tree.ndec, 3, 3))
+        native.check(self.ctx.L.nfsp_cfr_state(self.h, R.ctypes.data_as(native.P), S.ctypes.data_as(native.P)),
+                     "nfsp_cfr_state")
+        return R, S
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.L.nfsp_cfr_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

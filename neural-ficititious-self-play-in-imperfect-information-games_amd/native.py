@@ -80,6 +80,17 @@ class StateInfo(C.Structure):
                 ("payload_offset", I64), ("payload_bytes", I64), ("digest", U64 * 2)]
 
 
+class TreeNode(C.Structure):
+    """``nfsp_tree_node``: a node of the evaluator's public tree (nfsp_tree_export)"""
+    _fields_ = [("kind", C.c_int8), ("p", C.c_int8), ("via", C.c_int8), ("nchild", C.c_int8),
+                ("parent", C.c_int32), ("child", C.c_int32 * 3), ("row", C.c_int32)]
+
+
+class PolicySpec(C.Structure):
+    """``nfsp_policy``: a policy kind and its device pointer (a packed net or a table)"""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("dev", P)]
+
+
 PP = C.POINTER(P)
 # name -> (restype, argtypes); must list every symbol include/nfsp.h declares
 SIGNATURES = {
@@ -121,6 +132,16 @@ SIGNATURES = {
     "nfsp_engine_lane_counts": (I32, [P, PP]),
     "nfsp_exploitability": (I32, [P, P, P, I32, P]),
     "nfsp_exploitability_batch": (I32, [P, P, P, I32, I32, P]),
+    "nfsp_tree_size": (I32, [I32] + [C.POINTER(C.c_int32)] * 4),
+    "nfsp_tree_export": (I32, [I32, P, P, P, P, P, P, P]),
+    "nfsp_evaluate_batch": (I32, [P, C.POINTER(PolicySpec), C.POINTER(PolicySpec), I32, P]),
+    "nfsp_policy_table": (I32, [P, C.POINTER(PolicySpec), P]),
+    "nfsp_cfr_create": (I32, [P, C.POINTER(P)]),
+    "nfsp_cfr_run": (I32, [P, I64]),
+    "nfsp_cfr_iterations": (I32, [P, C.POINTER(I64)]),
+    "nfsp_cfr_average": (I32, [P, C.POINTER(P)]),
+    "nfsp_cfr_state": (I32, [P, P, P]),
+    "nfsp_cfr_destroy": (I32, [P]),
     "nfsp_engine_set_loss_log": (I32, [P, I32]),
     "nfsp_engine_losses": (I32, [P, P]),
     "nfsp_engine_set_timing": (I32, [P, I32]),
@@ -169,6 +190,9 @@ GROUP_AVG_AR = 1
 XCHG_AR, XCHG_BR = 1, 2
 DEAL_PHILOX, DEAL_PY3_MT, DEAL_PY2_MT = 0, 1, 2
 GROUP_MAX_REPLICAS = 256
+# nfsp_policy kinds (include/nfsp.h NFSP_POL_*) and the CFR+ launch cap (NFSP_CFR_LAUNCH_ITERS)
+POL_AR_SOFTMAX, POL_AR_ARGMAX, POL_BR_GREEDY, POL_BR_GREEDY_LINEAR, POL_TABLE = 0, 1, 2, 3, 4
+CFR_LAUNCH_ITERS = 1024
 
 _LIB = None
 
@@ -232,6 +256,7 @@ class Context:
               "nfsp_create")
         self.h = h
         self.n = int(n_envs)
+        self.game = int(game)
         check(L.nfsp_set_stream(h, stream_handle()), "nfsp_set_stream")
 
     def call(self, name, *args):
