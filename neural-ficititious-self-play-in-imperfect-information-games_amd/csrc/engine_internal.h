@@ -1,12 +1,13 @@
-// Internals shared by engine.hip (rollout, insert, lifecycle), learner.hip (the learner's kernels
-// and launchers), engine_update.hip (one engine's learner call), group.hip (engine groups) and
-// state.hip.
+// Internals shared by rollout.hip (rollout, insert), engine.hip (lifecycle, introspection),
+// learner.hip (the learner's kernels and launchers), engine_update.hip (one engine's learner
+// call), group.hip (engine groups) and state.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <utility>
 #include <vector>
 
+#include "engine_cfg.h"
 #include "nfsp_internal.h"
 #include "nn_device.h"
 
@@ -36,8 +37,7 @@ __host__ __device__ inline int net_lds_index(int q) {
   if (q < nn::OB2) return LHB + 4 * ((q - nn::OW2) / NA) + 1 + (q - nn::OW2) % NA;
   return LB2 + (q - nn::OB2);
 }
-constexpr int MAX_BATCH = 128;     // learner minibatch (config MiniBatchSize)
-constexpr int CHAIN_MB = 32;       // fit minibatch of the SGD chains (Keras batch_size)
+static_assert(CFG_HIDDEN == nn::H, "engine_cfg.h's hidden width");
 
 // Philox counter word x: the rollout uses the lane id (< 2^24); learner streams use these
 constexpr uint32_t TAG_SAMPLE = 0x81000000u, TAG_PERM = 0x82000000u, TAG_RES = 0x83000000u;
@@ -127,6 +127,7 @@ struct __attribute__((aligned(16))) StepRec {
   uint4 fa[4][32];
   float4 tg[32];
 };
+static_assert(sizeof(StepRec) == STEP_REC_BYTES && CHAIN_MB == 32, "engine_cfg.h's step record");
 
 // A sampled M_RL row before its TD target exists.
 struct BrRow {
@@ -308,8 +309,12 @@ struct nfsp_engine {
 namespace nfsp {
 namespace eng {
 
+// An engine of its own (nfsp_engine_create) has its chain streams; a replica of an engine group
+// has none: the group launches its chains and steps, saves and loads its replicas.
+inline bool standalone(const nfsp_engine* e) { return e->s_ar != nullptr; }
+
 hipEvent_t take_event(nfsp_engine* e);
-int engine_cfg_check(const nfsp_engine_cfg* cfg);   // nfsp_engine_create's cfg rules, host only
+int engine_cfg_check(const nfsp_engine_cfg* cfg);   // engine_cfg_rule as an error, host only
 int engine_create(nfsp_ctx* ctx, const nfsp_engine_cfg* cfg, bool own_streams, nfsp_engine** out);
 int rollout_launch(nfsp_engine* e);   // nfsp_rollout's launches
 // the same with the acting nets / epsilon given (cfg.slice_lag 2: a snapshot)

@@ -77,7 +77,7 @@ void commit_plan(nfsp_engine* e, const LearnPlan& L) {
   e->pending_update = false;
 }
 
-static int64_t recs_per_update(const nfsp_engine* e) { return (int64_t)e->cfg.epochs * (e->cfg.batch / CHAIN_MB); }
+static int64_t recs_per_update(const nfsp_engine* e) { return engine_sizes(e->cfg).steps; }
 
 ChainJob ar_job(const nfsp_engine* e, const LearnPlan& L, int a) {
   const LearnBufs& LB = L.P.LB;
@@ -324,7 +324,7 @@ static int update_impl(nfsp_engine* e, bool pipelined, int par, bool snap_after)
 
 extern "C" int nfsp_engine_update(nfsp_engine* e) {
   NFSP_REQUIRE(e, "null argument");
-  NFSP_REQUIRE(e->s_ar, "a replica of an engine group is stepped by nfsp_group_step");
+  NFSP_REQUIRE(standalone(e), "a replica of an engine group is stepped by nfsp_group_step");
   return update_impl(e, false, 0, false);
 }
 

@@ -4,7 +4,7 @@
 // generalised from "the seat's AR net" to a policy spec per seat:
 //   * the AR net as a softmax or as the executed argmax (k_exploit_walk's modes 0 / 1);
 //   * the BR net's greedy action, ReLU or linear Q head: what k_rollout executes when the
-//     epsilon draw does not fire (engine.hip; agent/agent.py:124-128), the learned best
+//     epsilon draw does not fire (rollout.hip; agent/agent.py:124-128), the learned best
 //     response of the evaluator the reference left commented out (main.py:82-120);
 //   * a table [ndec][3 ranks][3 actions] of doubles, for whatever is not a net.
 // and two more outputs, seat 0's value per dealer.  k_policy_table writes the policy phase's

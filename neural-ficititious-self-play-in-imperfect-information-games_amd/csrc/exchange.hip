@@ -124,7 +124,7 @@ int exchange_enqueue(nfsp_engine* e, hipStream_t s) {
 extern "C" int nfsp_engine_set_exchange(nfsp_engine* e, int every, float scale, void* rccl_comm,
                                         nfsp_exchange_fn fn, void* user) {
   NFSP_REQUIRE(e, "null argument");
-  NFSP_REQUIRE(e->s_ar, "a replica of an engine group exchanges through nfsp_group_set_exchange");
+  NFSP_REQUIRE(standalone(e), "a replica of an engine group exchanges through nfsp_group_set_exchange");
   NFSP_REQUIRE(every >= 0, "every must be >= 0");
   NFSP_REQUIRE(every == 0 || ((rccl_comm != nullptr) != (fn != nullptr)),
                "exactly one transport: an RCCL communicator or a host callback");

@@ -85,37 +85,15 @@ extern "C" int nfsp_group_destroy(nfsp_group* g) {
 }
 
 namespace {
-// The fields the replicas of a group must share: the shapes of the shared launches (lanes,
-// slices, batch, epochs and the learner buffers sized from them), the memories' sizes, the
-// schedule flags, and the two quirk bits that select the BR chain kernel of a shared launch
-// (k_chain3<1 / 2 / 3>).  The first one in which b differs from a, or nullptr.
-constexpr uint32_t GROUP_UNIFORM_QUIRKS = NFSP_EXT_LINEAR_Q | NFSP_EXT_MSE_Q;
+// The first field in which b differs from a, or nullptr (engine_cfg.h's field classes): of those
+// the replicas of a group must share (with quirks' two bits that select the BR chain kernel of a
+// shared launch), and of those that may differ, the seed apart.
 const char* group_uniform_diff(const nfsp_engine_cfg& a, const nfsp_engine_cfg& b) {
-  if (a.n_lanes != b.n_lanes) return "n_lanes";
-  if (a.hidden != b.hidden) return "hidden";
-  if (a.rl_capacity != b.rl_capacity) return "rl_capacity";
-  if (a.sl_capacity != b.sl_capacity) return "sl_capacity";
-  if (a.batch != b.batch) return "batch";
-  if (a.inserts_per_update != b.inserts_per_update) return "inserts_per_update";
-  if (a.epochs != b.epochs) return "epochs";
-  if (a.fit_batch != b.fit_batch) return "fit_batch";
-  if (a.slices != b.slices) return "slices";
-  if (a.slice_lag != b.slice_lag) return "slice_lag";
-  if (a.sched != b.sched) return "sched";
-  if ((a.quirks ^ b.quirks) & GROUP_UNIFORM_QUIRKS) return "quirks (NFSP_EXT_LINEAR_Q | NFSP_EXT_MSE_Q)";
-  return nullptr;
+  return cfg_first_diff(a, b, CFG_SHAPE | CFG_SESSION);
 }
-// The fields that may differ, the seed apart (bit patterns: -0.0 and 0.0 are different cfgs, as
-// in a state blob's comparison): the first one in which b differs from a, or nullptr.
-const char* group_free_diff(const nfsp_engine_cfg& a, const nfsp_engine_cfg& b) {
-  if (memcmp(&a.eta, &b.eta, sizeof(float))) return "eta";
-  if (memcmp(&a.lr_br, &b.lr_br, sizeof(float))) return "lr_br";
-  if (memcmp(&a.lr_ar, &b.lr_ar, sizeof(float))) return "lr_ar";
-  if (memcmp(&a.gamma, &b.gamma, sizeof(double))) return "gamma";
-  if (memcmp(&a.epsilon, &b.epsilon, sizeof(double))) return "epsilon";
-  if (a.target_every != b.target_every) return "target_every";
-  if (a.quirks != b.quirks) return "quirks";
-  return nullptr;
+const char* group_free_diff(const nfsp_engine_cfg& a, nfsp_engine_cfg b) {
+  b.seed = a.seed;
+  return cfg_first_diff(a, b, CFG_HYPER);
 }
 bool group_br_same(const nfsp_engine_cfg& a, const nfsp_engine_cfg& b) {
   return !memcmp(&a.gamma, &b.gamma, sizeof(double)) && !memcmp(&a.lr_br, &b.lr_br, sizeof(float)) &&

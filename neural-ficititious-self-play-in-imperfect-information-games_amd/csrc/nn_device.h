@@ -1,5 +1,5 @@
 // Workgroup-level network routines shared by the fit API (mlp.hip) and the on-device
-// learner (engine.hip): one Keras SGD step of a 30 -> 64 -> 3 head, whole net in LDS.
+// engine (rollout.hip, learner.hip): one Keras SGD step of a 30 -> 64 -> 3 head, whole net in LDS.
 // Formulas = oracle/nn_oracle.py MLP.grads (Huber for the ReLU head, Keras/TF
 // categorical cross-entropy for the softmax head); reference: agent/agent.py:90-116,
 // 243, 261.

@@ -220,27 +220,9 @@ int st_check(const EngineDev& h, const nfsp_engine_cfg& c, const char* what) {
 HostRec host_rec(const nfsp_engine* e) {
   HostRec r;
   memset(&r, 0, sizeof(r));
-  // field by field: the struct's padding stays zero
-  const nfsp_engine_cfg& c = e->cfg;
-  r.cfg.n_lanes = c.n_lanes;
-  r.cfg.hidden = c.hidden;
-  r.cfg.rl_capacity = c.rl_capacity;
-  r.cfg.sl_capacity = c.sl_capacity;
-  r.cfg.batch = c.batch;
-  r.cfg.inserts_per_update = c.inserts_per_update;
-  r.cfg.target_every = c.target_every;
-  r.cfg.epochs = c.epochs;
-  r.cfg.fit_batch = c.fit_batch;
-  r.cfg.quirks = c.quirks;
-  r.cfg.eta = c.eta;
-  r.cfg.lr_br = c.lr_br;
-  r.cfg.lr_ar = c.lr_ar;
-  r.cfg.gamma = c.gamma;
-  r.cfg.epsilon = c.epsilon;
-  r.cfg.seed = c.seed;
-  r.cfg.slices = 1;
-  r.cfg.slice_lag = 1;
-  r.cfg.sched = 0;
+  // field by field (engine_cfg.h's table), bytes into bytes: the struct's padding stays zero
+  const nfsp_engine_cfg c = cfg_stored(e->cfg);
+  memcpy(&r.cfg, &c, sizeof(c));
   r.game = e->ctx->game;
   r.g = (int64_t)(e->rollouts / (uint64_t)e->slices);
   r.learn_tag = e->learn_tag;
@@ -514,22 +496,8 @@ void header_finish(BlobHeader* h, const std::vector<BlobSection>& sec, unsigned 
 // what a blob's engine payload must share with the engine it is loaded into (replica >= 0: a
 // group's replica, named in the message -- its replicas' cfgs may differ from each other)
 int compat_check(const nfsp_engine* e, const HostRec& hr, int replica = -1) {
-  const nfsp_engine_cfg &a = e->cfg, &b = hr.cfg;
-  const char* f = nullptr;
-  if (a.n_lanes != b.n_lanes) f = "n_lanes";
-  else if (a.hidden != b.hidden) f = "hidden";
-  else if (a.rl_capacity != b.rl_capacity) f = "rl_capacity";
-  else if (a.sl_capacity != b.sl_capacity) f = "sl_capacity";
-  else if (a.batch != b.batch) f = "batch";
-  else if (a.inserts_per_update != b.inserts_per_update) f = "inserts_per_update";
-  else if (a.target_every != b.target_every) f = "target_every";
-  else if (a.epochs != b.epochs) f = "epochs";
-  else if (a.fit_batch != b.fit_batch) f = "fit_batch";
-  else if (a.quirks != b.quirks) f = "quirks";
-  else if (memcmp(&a.eta, &b.eta, 4) || memcmp(&a.lr_br, &b.lr_br, 4) || memcmp(&a.lr_ar, &b.lr_ar, 4)) f = "eta / lr_br / lr_ar";
-  else if (memcmp(&a.gamma, &b.gamma, 8) || memcmp(&a.epsilon, &b.epsilon, 8)) f = "gamma / epsilon";
-  else if (a.seed != b.seed) f = "seed";
-  else if (e->ctx->game != hr.game) f = "game";
+  const char* f = cfg_first_diff(e->cfg, hr.cfg, CFG_SHAPE | CFG_HYPER);   // every stored field
+  if (!f && e->ctx->game != hr.game) f = "game";
   if (f && replica >= 0)
     return nfsp::fail(NFSP_EINVAL, std::string("state blob: replica ") + std::to_string(replica) + ": " + f +
                                        " differs from the group's replica " + std::to_string(replica));
@@ -654,7 +622,7 @@ extern "C" int nfsp_engine_state_digest_timed(nfsp_engine* e, uint64_t out[2], d
 
 extern "C" int nfsp_engine_state_bytes(nfsp_engine* e, int64_t* out) {
   NFSP_REQUIRE(e && out, "null argument");
-  NFSP_REQUIRE(e->s_ar, "a replica of an engine group is saved by nfsp_group_save_state");
+  NFSP_REQUIRE(standalone(e), "a replica of an engine group is saved by nfsp_group_save_state");
   int rc = boundary_check(e, "nfsp_engine_state_bytes");
   if (rc != NFSP_OK) return rc;
   if ((rc = engine_sync(e)) != NFSP_OK) return rc;
@@ -666,7 +634,7 @@ extern "C" int nfsp_engine_state_bytes(nfsp_engine* e, int64_t* out) {
 
 extern "C" int nfsp_engine_save_state(nfsp_engine* e, void* host_buf, int64_t cap, int64_t* written) {
   NFSP_REQUIRE(e && host_buf && written, "null argument");
-  NFSP_REQUIRE(e->s_ar, "a replica of an engine group is saved by nfsp_group_save_state");
+  NFSP_REQUIRE(standalone(e), "a replica of an engine group is saved by nfsp_group_save_state");
   int rc = boundary_check(e, "nfsp_engine_save_state");
   if (rc != NFSP_OK) return rc;
   if ((rc = engine_sync(e)) != NFSP_OK) return rc;
@@ -687,7 +655,7 @@ extern "C" int nfsp_engine_save_state(nfsp_engine* e, void* host_buf, int64_t ca
 
 extern "C" int nfsp_engine_load_state(nfsp_engine* e, const void* host_buf, int64_t n) {
   NFSP_REQUIRE(e && host_buf, "null argument");
-  NFSP_REQUIRE(e->s_ar, "a replica of an engine group is loaded by nfsp_group_load_state");
+  NFSP_REQUIRE(standalone(e), "a replica of an engine group is loaded by nfsp_group_load_state");
   // everything that can refuse the blob comes before the first write (and before any device work)
   BlobView v;
   int rc = blob_parse(host_buf, n, &v);
