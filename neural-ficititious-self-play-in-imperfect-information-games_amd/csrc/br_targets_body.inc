@@ -1,8 +1,8 @@
 // The body of k_br_targets (learner.hip): one BR update's targets -- the Q_target forwards of
 // its 128 rows, TD values, the proxy, the row-0 quirk and its step records.  Included by the
-// kernel (one workgroup per update) and by br_targets_item (the persistent group BR kernel's
-// helper workgroups).  In scope: J (TargetJob), bx (update within the segment), B, E,
-// gamma, quirks, lr0.
+// kernel (one workgroup per update) and by br_targets_item (br_targets.h: the persistent group
+// BR kernel's helper workgroups).  In scope: J (TargetJob), bx (update within the segment), B,
+// E, gamma, quirks, lr0, and br_targets.h's emit_recs.
   // threads 0..127: Q_target(s) of row b (waves 0-1); threads 128..255: Q_target(s2) of
   // row b - 128 (waves 2-3) -- the two forwards of a row run side by side
   __shared__ __attribute__((aligned(16))) float sw[NET_LDS];

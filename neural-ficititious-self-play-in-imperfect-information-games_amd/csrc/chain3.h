@@ -414,7 +414,7 @@ __global__ void __launch_bounds__(256) k_chain3(ChainArgs C) {
 #include "chain3_body.inc"
 }
 
-// One job's chain as a device function (k_br_persist, learner.hip): the same body
+// One job's chain as a device function (k_br_persist, br_persist.hip): the same body
 template <int RELU, int LOSS, int TABLE>
 __device__ __forceinline__ void chain3_run(const ChainArgs& C, const ChainJob J, char* smem_raw) {
   Chain3Smem& sm = *reinterpret_cast<Chain3Smem*>(smem_raw);

@@ -1,14 +1,15 @@
 // Engine groups (nfsp_group_*): R replicas stepped together, their chains in shared launches.
 // Host code only: the group object, its cfg rules, exchange, scheduling knobs and trace, and
 // the group's learner call (group_update), which plans the BR work with group_plan.h and
-// launches learner.hip's kernels through its launchers (learner_internal.h).  Built with the
-// default flags: nothing here is on the SGD chains' path.
+// launches learner.hip's kernels through its launchers (learner_internal.h) -- or, opted in
+// (sched.br_persist), the persistent BR kernel through br_persist.h, at five marked call sites.
+// Built with the default flags: nothing here is on the SGD chains' path.
 #include <stdlib.h>
 #include <string.h>
 
 #include <string>
 
-#include "learner_internal.h"
+#include "br_persist.h"
 
 namespace nn = nfsp::nn;
 namespace plan = nfsp::plan;
@@ -22,8 +23,7 @@ struct nfsp_group {
   int R = 0;
   unsigned flags = 0;
   // nfsp_group_create_v: some replica's cfg differs from replica 0's in more than the seed (no
-  // exchange then); br_uniform: gamma, lr_br and quirks are the same everywhere (k_br_persist's
-  // launch-wide BrPersistArgs carry one of each)
+  // exchange then); br_uniform: gamma, lr_br and quirks are the same everywhere (group_br_sched)
   bool hetero = false, br_uniform = true;
   std::vector<nfsp_engine*> eng;
   hipStream_t s_ar = nullptr, s_br = nullptr;
@@ -52,7 +52,7 @@ struct nfsp_group {
   int64_t calls = 0;             // learner calls (slices) so far
   int64_t rounds = 0;            // BR rounds of the last learner call (stats)
   nfsp_group_sched sched{};      // nfsp_group_set_sched (from nfsp_group_default_sched)
-  int32_t* h_err = nullptr;      // k_br_persist's bail flags (pinned host, mapped): group_check_err
+  int32_t* h_err = nullptr;      // br_persist.h: the bail flags
   int chain_lds = 0;             // LDS per chain workgroup: 4R chains on the device's CUs
   bool trace_on = false;         // nfsp_group_set_trace: per call [R][2][AR, BR] update counts
   std::vector<int32_t> trace;
@@ -73,7 +73,7 @@ extern "C" int nfsp_group_destroy(nfsp_group* g) {
       if (ev) (void)hipEventDestroy(ev);
   }
   if (g->h_st) (void)hipHostFree(g->h_st);
-  if (g->h_err) (void)hipHostFree(g->h_err);
+  brp_flags_free(g->h_err);                        // br_persist.h
   for (void* p : {(void*)g->d_war, (void*)g->w0, g->d_roll, (void*)g->d_stp, (void*)g->d_st})
     if (p) (void)hipFree(p);
   for (hipStream_t st : {g->s_ar, g->s_br})
@@ -214,8 +214,7 @@ extern "C" int nfsp_group_create_v(nfsp_ctx* ctx, const nfsp_engine_cfg* cfgs, i
   if (r == hipSuccess) r = hipMalloc((void**)&g->d_stp, sizeof(EngineDev*) * replicas);
   if (r == hipSuccess) r = hipMalloc((void**)&g->d_st, sizeof(EngineDev) * replicas);
   if (r == hipSuccess) r = hipHostMalloc((void**)&g->h_st, sizeof(EngineDev) * replicas, hipHostMallocDefault);
-  if (r == hipSuccess) r = hipHostMalloc((void**)&g->h_err, sizeof(int32_t) * 4, hipHostMallocMapped | hipHostMallocCoherent);
-  if (r == hipSuccess) memset(g->h_err, 0, sizeof(int32_t) * 4);
+  if (r == hipSuccess) r = brp_flags_alloc(&g->h_err);   // br_persist.h
   if (r == hipSuccess) r = hipMemcpy(g->d_stp, stp.data(), sizeof(EngineDev*) * replicas, hipMemcpyHostToDevice);
   if (r != hipSuccess) {
     nfsp_group_destroy(g);
@@ -290,19 +289,6 @@ extern "C" int nfsp_group_set_exchange(nfsp_group* g, unsigned nets, int every, 
   return NFSP_OK;
 }
 
-// k_br_persist's bounded waits: a hand-off that never came ended that kernel with a bail flag
-// set (pinned host memory).  Checked once the kernel has completed: after a learner call's
-// readback sync (the ctx stream has then waited for every earlier slice's BR stream) and by
-// nfsp_group_check (which synchronises first).
-static int group_check_err(nfsp_group* g) {
-  volatile int32_t* h = g->h_err;
-  if (!h || !h[0]) return NFSP_OK;
-  const int cb = h[1], hb = h[2];
-  h[0] = h[1] = h[2] = 0;
-  return nfsp::fail(NFSP_EHIP, "k_br_persist: a bounded wait expired (work-queue hand-off): chain bails " +
-                                   std::to_string(cb) + ", helper bails " + std::to_string(hb));
-}
-
 // ---------------------------------------------------------------------------
 // group_update: one learner call of every replica, a sequence of stages over a GroupCall
 // ---------------------------------------------------------------------------
@@ -323,9 +309,9 @@ static BrSched group_br_sched(const nfsp_group* g, bool loss_log) {
   sc.pace = g->sched.br_pace != 0;
   sc.shared_cus = g->chain_lds < CHAIN_LDS;
   // The persistent BR kernel (sched.br_persist) instead of the rounds: one launch, one stream,
-  // the reference's BR net (k_chain3<1>), no loss log, its 2R chains and BRP_HELPERS helpers a
-  // CU each beside the 2R AR chains (R <= 32, no CU sharing), and one gamma, lr_br and quirks for
-  // the launch (BrPersistArgs): replicas that differ in them keep the rounds
+  // the reference's BR net (k_chain3<1>), no loss log, its 2R chains and BRP_HELPERS helpers
+  // (br_persist.hip) a CU each beside the 2R AR chains (R <= 32, no CU sharing), and one gamma,
+  // lr_br and quirks for the launch: replicas that differ in them keep the rounds
   sc.persist = g->sched.br_persist && !loss_log && !(e0->cfg.quirks & NFSP_EXT_LINEAR_Q) && g->R <= 32 &&
                !sc.shared_cus && g->br_uniform;
   // Partitions: replicas [part_begin(p), part_begin(p + 1)) are partition p, whose BR jobs run
@@ -345,20 +331,7 @@ static BrSched group_br_sched(const nfsp_group* g, bool loss_log) {
   return sc;
 }
 
-// bump-allocate n items of T in the host / device table pair (16-byte aligned offsets)
-struct TabCursor {
-  size_t off = 0;
-  template <class T>
-  size_t take(size_t n) {
-    const size_t o = (off + 15) & ~(size_t)15;
-    off = o + sizeof(T) * n;
-    return o;
-  }
-};
-template <class T>
-static T* tab_at(char* base, size_t off) { return reinterpret_cast<T*>(base + off); }
-
-// the call's tables on device (one copy from the pinned host set)
+// the call's tables on device (one copy from the pinned host set; TabCursor: learner_internal.h)
 struct GroupTabs {
   size_t bytes = 0;
   const PrepArgs* prep = nullptr;   // [R]
@@ -366,7 +339,6 @@ struct GroupTabs {
   const ChainJob* ar = nullptr;     // the AR chains
   const ChainJob* br = nullptr;     // the rounds' pieces
   const TargetJob* tg = nullptr;    // the rounds' targets
-  BrPersistArgs P{};                // k_br_persist's tables (seg_job .. chunk_done)
 };
 
 struct GroupCall {
@@ -382,6 +354,7 @@ struct GroupCall {
   plan::RoundsPlan rounds;          // the BR work: rounds of pieces and targets, or
   plan::PersistPlan pq;             //   (sc.persist) k_br_persist's segments and work queue
   GroupTabs T;
+  BrpTabs PT{};                     // (sc.persist) its tables' offsets in the set
   hipEvent_t fork_br = nullptr, fork = nullptr;   // the BR rows / the AR records are prepared
   hipStream_t sp[GROUP_BR_STREAMS] = {};          // the partitions' streams
 };
@@ -394,7 +367,9 @@ static int group_readback(nfsp_group* g) {
   if (rc != NFSP_OK) return rc;
   NFSP_HIP(hipMemcpyAsync(g->h_st, g->d_st, sizeof(EngineDev) * g->R, hipMemcpyDeviceToHost, s));
   NFSP_HIP(hipStreamSynchronize(s));
-  return group_check_err(g);
+  // br_persist.h: the ctx stream has waited for every earlier slice's BR stream, so a persistent
+  // kernel that bailed has completed
+  return brp_flags_take(g->h_err);
 }
 
 // stage 1b: every replica's plan.  Replica 0's cfg stands for the fields every replica shares
@@ -473,15 +448,11 @@ static int group_fill_tables(GroupCall& c) {
   const int R = g->R;
   const std::vector<plan::Piece>& pc = c.rounds.pieces;
   const std::vector<plan::SegRef>& tg = c.rounds.targets;
-  const plan::PersistPlan& q = c.pq;
   TabCursor cur;
   const size_t o_prep = cur.take<PrepArgs>(R), o_fin = cur.take<FinalArgs>(R);
   const size_t o_ar = cur.take<ChainJob>(c.ar_jobs.size()), o_br = cur.take<ChainJob>(pc.size());
   const size_t o_tg = cur.take<TargetJob>(tg.size());
-  const size_t o_pj = cur.take<ChainJob>(q.segs.size()), o_pt = cur.take<TargetJob>(q.segs.size());
-  const size_t o_pc = cur.take<int32_t>(q.chunk0.size()), o_ps = cur.take<int32_t>(q.jseg0.size());
-  const size_t o_pq = cur.take<uint32_t>(q.slots.size()), o_pn = cur.take<uint32_t>(2);
-  const size_t o_pd = cur.take<uint32_t>((size_t)q.nchunks);
+  c.PT = brp_tabs_take(cur, c.pq);               // br_persist.h (an empty plan unless sc.persist)
   const size_t need = cur.off;
   int rc;
   if ((rc = group_tab_reserve(g, c.par, need)) != NFSP_OK) return rc;
@@ -498,19 +469,7 @@ static int group_fill_tables(GroupCall& c) {
         br_chain_job(g->eng[pc[i].r], c.L[pc[i].r], pc[i].a, Segment{pc[i].u, pc[i].v, pc[i].sync});
   for (size_t i = 0; i < tg.size(); ++i)
     tab_at<TargetJob>(h_tab, o_tg)[i] = br_target_job(g->eng[tg[i].r], c.L[tg[i].r], tg[i].a, seg_of(tg[i]));
-  if (c.sc.persist) {
-    for (size_t i = 0; i < q.segs.size(); ++i) {
-      const plan::SegRef& t = q.segs[i];
-      tab_at<ChainJob>(h_tab, o_pj)[i] = br_chain_job(g->eng[t.r], c.L[t.r], t.a, seg_of(t));
-      tab_at<TargetJob>(h_tab, o_pt)[i] = br_target_job(g->eng[t.r], c.L[t.r], t.a, seg_of(t));
-    }
-    memcpy(h_tab + o_pc, q.chunk0.data(), sizeof(int32_t) * q.chunk0.size());
-    memcpy(h_tab + o_ps, q.jseg0.data(), sizeof(int32_t) * q.jseg0.size());
-    if (!q.slots.empty()) memcpy(h_tab + o_pq, q.slots.data(), sizeof(uint32_t) * q.slots.size());
-    tab_at<uint32_t>(h_tab, o_pn)[0] = 0u;          // helpers' claims
-    tab_at<uint32_t>(h_tab, o_pn)[1] = q.npre;      // queue reservations
-    memset(h_tab + o_pd, 0, sizeof(uint32_t) * (size_t)q.nchunks);
-  }
+  if (c.sc.persist) brp_tabs_fill(h_tab, c.PT, c.pq, g->eng.data(), c.L.data());   // br_persist.h
   GroupTabs& T = c.T;
   T.bytes = need;
   T.prep = tab_at<const PrepArgs>(d_tab, o_prep);
@@ -518,13 +477,6 @@ static int group_fill_tables(GroupCall& c) {
   T.ar = tab_at<const ChainJob>(d_tab, o_ar);
   T.br = tab_at<const ChainJob>(d_tab, o_br);
   T.tg = tab_at<const TargetJob>(d_tab, o_tg);
-  T.P.seg_job = tab_at<const ChainJob>(d_tab, o_pj);
-  T.P.seg_tgt = tab_at<const TargetJob>(d_tab, o_pt);
-  T.P.seg_chunk0 = tab_at<const int32_t>(d_tab, o_pc);
-  T.P.job_seg0 = tab_at<const int32_t>(d_tab, o_ps);
-  T.P.slots = tab_at<uint32_t>(d_tab, o_pq);
-  T.P.ctr = tab_at<uint32_t>(d_tab, o_pn);
-  T.P.chunk_done = tab_at<uint32_t>(d_tab, o_pd);
   return NFSP_OK;
 }
 
@@ -550,23 +502,12 @@ static int group_fork_br(GroupCall& c) {
   return NFSP_OK;
 }
 
-// stage 6, persist: the whole BR call in one launch on s_br
+// stage 6, persist: the whole BR call in one launch on s_br (br_persist.h)
 static int group_launch_persist(GroupCall& c) {
   nfsp_group* g = c.g;
-  const nfsp_engine_cfg& cfg = g->eng[0]->cfg;
-  if (c.pq.jseg0.size() <= 1) return NFSP_OK;   // no BR work
-  BrPersistArgs P = c.T.P;
-  P.C = chain_args(cfg);
-  NFSP_HIP(hipHostGetDevicePointer((void**)&P.err, g->h_err, 0));
-  P.njobs = (int)c.pq.jseg0.size() - 1;
-  P.nitems = (int)c.pq.slots.size();
-  P.chunk = BRP_CHUNK;
-  P.spin = g->sched.br_persist > 1 ? g->sched.br_persist : BRP_SPIN;
-  P.gamma = cfg.gamma;
-  P.lr0 = cfg.lr_br;
-  P.quirks = cfg.quirks;
+  if (!g->rounds) return NFSP_OK;               // no BR work (group_plan_br): nothing to time
   KTimer kc(g->eng[0], KT_CHAIN_BR, g->s_br);
-  return launch_br_persist(P, BRP_HELPERS, g->s_br);
+  return brp_launch(g->d_tab[c.par], c.PT, c.pq, g->eng[0]->cfg, g->sched.br_persist, g->h_err, g->s_br);
 }
 
 // stage 6, rounds: per round its targets launch and its chain launch on the partition's stream.
@@ -781,7 +722,7 @@ extern "C" int nfsp_group_check(nfsp_group* g) {
     if (st) NFSP_HIP(hipStreamSynchronize(st));
   for (hipStream_t st : g->s_brp)
     if (st) NFSP_HIP(hipStreamSynchronize(st));
-  return group_check_err(g);
+  return brp_flags_take(g->h_err);   // br_persist.h
 }
 
 extern "C" int nfsp_group_rounds(nfsp_group* g, int64_t* out) {

@@ -3,7 +3,8 @@
 // This file: the learner's kernels (the BR instantiation of k_chain3 among them: this is the
 // BR chain's translation unit, built with the chain flags) and their host launchers
 // (learner_internal.h).  The host code of a learner call, which launches the kernels through
-// the launchers, is engine_update.hip (one engine) and group.hip (an engine group).
+// the launchers, is engine_update.hip (one engine) and group.hip (an engine group).  The device
+// code of the targets that another translation unit shares is br_targets.h (br_persist.hip).
 //
 // An update's inputs (sampled rows, fit permutations, reservoir contents at that moment,
 // DQN targets) do not depend on the weights being trained, except the targets on the
@@ -26,7 +27,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "learner_internal.h"
+#include "br_targets.h"
 
 using nfsp::u32x4;
 namespace nn = nfsp::nn;
@@ -105,31 +106,6 @@ __global__ void __launch_bounds__(256) k_ar_slots(PrepArgs P0, const PrepArgs* _
     const unsigned long long mine = ((unsigned long long)P.tag << 32) | (unsigned long long)q;
     const unsigned long long old = atomicExch(&P.LB.res_head[(int64_t)a * cap + slot], mine);
     P.LB.res_next[qi] = (uint32_t)(old >> 32) == P.tag ? (int32_t)(old & 0xFFFFFFFFull) : -1;
-  }
-}
-
-// 8 bf16 0/1 values of the layer-1 K slots 8g..8g+7 (bits 4g..4g+3, 16+4g..16+4g+3 of x)
-__device__ inline uint4 bits8u(uint32_t x, int g) {
-  const uint32_t n0 = (x >> (4 * g)) & 0xFu, n1 = (x >> (16 + 4 * g)) & 0xFu;
-  return make_uint4((n0 & 1u) * 0x3F80u + ((n0 >> 1) & 1u) * 0x3F800000u,
-                    ((n0 >> 2) & 1u) * 0x3F80u + ((n0 >> 3) & 1u) * 0x3F800000u,
-                    (n1 & 1u) * 0x3F80u + ((n1 >> 1) & 1u) * 0x3F800000u,
-                    ((n1 >> 2) & 1u) * 0x3F80u + ((n1 >> 3) & 1u) * 0x3F800000u);
-}
-
-// The chain records of one (update, epoch): the thread of fit position b < B holds its
-// observation mask x, targets and the lr; minibatch b >> 5 gets the swizzled fa chunks and
-// tg of its sample b & 31 (the chain reads the transposed operand from fa itself).  Every
-// valid sample also carries the bias input (CHAIN_BIAS_BIT).
-__device__ inline void emit_recs(StepRec* __restrict__ recs, uint32_t x, float t0, float t1, float t2,
-                                 float lr, int B, int b) {
-  if (b < B) {
-    x |= CHAIN_BIAS_BIT;
-    StepRec& R = recs[b >> 5];
-    const int k = b & 31;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) R.fa[g][fa_slot(g, k)] = bits8u(x, g);
-    R.tg[k] = make_float4(t0, t1, t2, lr);
   }
 }
 
@@ -252,15 +228,6 @@ __global__ void __launch_bounds__(256) k_res_apply(PrepArgs P0, const PrepArgs* 
 // ---------------------------------------------------------------------------
 // DQN targets of one BR segment (agent/agent.py:219-241), one update per workgroup
 // ---------------------------------------------------------------------------
-// a workgroup-uniform field of a job that arrived in VGPRs, in SGPRs (as brp_uniform's below)
-__device__ __forceinline__ unsigned tj_uniform(unsigned x) { return __builtin_amdgcn_readfirstlane(x); }
-__device__ __forceinline__ double tj_uniform(double x) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b);
-  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
 // blockIdx.x = update within the segment; blockIdx.y = job (of `jobs`, else `one`).  gamma, lr0
 // and quirks are the job's own (one engine: its cfg's; a group: each replica's).
 __global__ void __launch_bounds__(256) k_br_targets(const TargetJob* __restrict__ jobs, TargetJob one,
@@ -271,190 +238,9 @@ __global__ void __launch_bounds__(256) k_br_targets(const TargetJob* __restrict_
   // it with vector loads, the by-value `one` (kernel-argument memory) included.  The three values
   // that were launch-wide arguments steer branches and selects of the whole workgroup (br_act,
   // the ROW0 / TERMINAL quirks) and the f64 TD and lr arithmetic: made scalar again.
-  const double gamma = tj_uniform(J.gamma), lr0 = tj_uniform(J.lr0);
-  const unsigned quirks = tj_uniform(J.quirks);
+  const double gamma = uniform_f64(J.gamma), lr0 = uniform_f64(J.lr0);
+  const unsigned quirks = uniform32(J.quirks);
 #include "br_targets_body.inc"
-}
-
-// one update's targets by the calling workgroup (k_br_persist's helpers): the same body
-__device__ __forceinline__ void br_targets_item(const TargetJob J, int64_t bx, int B, int E, double gamma,
-                                                unsigned quirks, double lr0) {
-#include "br_targets_body.inc"
-}
-
-// ---------------------------------------------------------------------------
-// k_br_persist: an engine group's whole BR learner call in one launch (nfsp_group_sched.br_persist;
-// round 5, re-landed in round 6 -- DESIGN.md Appendix A.1b).  Workgroups 0 .. njobs - 1 are
-// chains, one per (replica, agent) with BR work: each runs its target-sync segments in order,
-// in pieces of `chunk` updates, each piece as soon as its targets are written.  The others are
-// helpers: they take work items -- (segment, update) -- in queue order and write that update's
-// targets and step records (k_br_targets' body).  The host queues the first segments' items; a
-// chain queues its next segment's items once the segment's last piece has synced the target
-// net they read.  No round waits for another job's segment and no targets launch sits between
-// chains.  The same SGD steps as the rounds, bit for bit (a piece resumes from the weights in
-// memory).
-// Hand-offs, agent scope (per-XCD L2s): the writer's stores, __threadfence in every writing
-// thread, the workgroup barrier, then one release atomic; the reader polls relaxed in one
-// thread, then one acquire fence and the workgroup barrier.  Every wait is bounded (spin x
-// s_sleep 8): on expiry *err is set and the workgroup leaves, so a lost hand-off ends the
-// kernel; the host reports it (group_check_err).
-// Loop shape: each loop has ONE thread-0 region per iteration, at its top, and the iteration
-// ends on a barrier.  The round-5 form also had a thread-0 region at the bottom (the helper's
-// "item done" atomic); the compiler merged the two across the back edge into a loop of their
-// own, which left the barrier-bearing body as an inner loop that lanes 1-63 of wave 0 and waves
-// 1-3 iterated on the stale work word while lane 0 waited for them to leave it: the hang of
-// profiles/r05_group_br_persist (found in round 6 in the ISA, profiles/r06/persist_rootcause).
-// The words that end the loops (a bail, the next item) are read through readfirstlane, so the
-// loops' exits are scalar branches, and a job's fields are made scalar (brp_uniform).
-// ---------------------------------------------------------------------------
-constexpr uint32_t BRP_EMPTY = 0xFFFFFFFFu, BRP_DONE = 0xFFFFFFFEu;
-static_assert(BRP_EMPTY == nfsp::plan::SLOT_EMPTY, "the host fills the queue (group_plan.h)");
-constexpr int BRP_STATIC_LDS = 16 * 1024;   // bound on the kernel's static LDS (the targets buffers)
-
-#ifdef NFSP_BRP_STAMPS
-// diagnostic build only (tools/build_lib_variant.py brpst -DNFSP_BRP_STAMPS=1, tools/brp_stamps.py):
-// per chain [wait cycles, chain cycles, SGD steps, pieces], per helper [wait, work, items, 0]
-__device__ unsigned long long g_brp_stamps[2][64][4];
-#define BRP_T() __builtin_amdgcn_s_memtime()
-#endif
-
-// A job read from the tables arrives in VGPRs (vector loads: the kernel writes global memory,
-// so no scalar loads); readfirstlane makes its fields scalar again, as k_chain3's kernel-argument
-// jobs are -- otherwise every record load's buffer descriptor becomes a readfirstlane loop
-__device__ __forceinline__ int64_t brp_u64(int64_t x) {
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
-  return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-template <class T>
-__device__ __forceinline__ T* brp_ptr(T* p) { return reinterpret_cast<T*>(brp_u64(reinterpret_cast<int64_t>(p))); }
-__device__ __forceinline__ ChainJob brp_uniform(ChainJob J) {
-  J.w = brp_ptr(J.w);
-  J.sync_to = brp_ptr(J.sync_to);
-  J.snap_to = brp_ptr(J.snap_to);
-  J.rec = brp_ptr(J.rec);
-  J.active = brp_ptr(J.active);
-  J.loss_out = brp_ptr(J.loss_out);
-  J.u0 = brp_u64(J.u0);
-  J.u1 = brp_u64(J.u1);
-  return J;
-}
-
-__device__ __forceinline__ void brp_bail(int32_t* err, int k) {
-  __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_fetch_add(err + k, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-__global__ void __launch_bounds__(256) k_br_persist(BrPersistArgs P) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  __shared__ uint32_t s_word;
-#ifdef NFSP_BRP_STAMPS
-  unsigned long long st_wait = 0, st_chain = 0, st_steps = 0, st_pieces = 0, st_t1 = 0;
-#endif
-  if ((int)blockIdx.x < P.njobs) {                         // ---- a chain
-    const int j = blockIdx.x;
-    for (int s = P.job_seg0[j]; s < P.job_seg0[j + 1]; ++s) {
-      const ChainJob JS = brp_uniform(P.seg_job[s]);
-      for (int64_t a = JS.u0, c = 0; a < JS.u1; a += P.chunk, ++c) {
-        const int64_t b = a + P.chunk < JS.u1 ? a + P.chunk : JS.u1;
-        if (threadIdx.x == 0) {                            // the iteration's one thread-0 region
-#ifdef NFSP_BRP_STAMPS
-          const unsigned long long t0 = BRP_T();
-          if (st_t1) st_chain += t0 - st_t1;
-#endif
-          const uint32_t* done = &P.chunk_done[P.seg_chunk0[s] + c];
-          int it = 0;
-          while (__hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (uint32_t)(b - a) &&
-                 ++it < P.spin)
-            __builtin_amdgcn_s_sleep(8);
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-          s_word = it >= P.spin;
-          if (s_word) brp_bail(P.err, 1);
-#ifdef NFSP_BRP_STAMPS
-          st_t1 = BRP_T();
-          st_wait += st_t1 - t0;
-          st_steps += (b - a) * P.C.E * (P.C.B / CHAIN_MB);
-          ++st_pieces;
-#endif
-        }
-        __syncthreads();
-        // readfirstlane: the compiler then knows the value is uniform -- a scalar branch, a loop
-        // with uniform exits (with a vector value the loop's exits are divergent, values carried
-        // in it are taken as divergent and every record load's buffer descriptor became a
-        // readfirstlane loop: 1,280 instructions per 4 steps against k_chain3's 1,217)
-        if (__builtin_amdgcn_readfirstlane(s_word)) return; // workgroup-uniform
-        ChainJob JP = JS;
-        JP.u0 = a;
-        JP.u1 = b;
-        if (b < JS.u1) JP.sync_to = nullptr;               // the segment's last piece syncs
-        chain3_run<1, 0, 1>(P.C, JP, smem_raw);
-        __threadfence();        // the piece's weights (and synced target net) out, for the next
-        __syncthreads();        // piece's loads by other waves and for the helpers
-      }
-      if (s + 1 < P.job_seg0[j + 1]) {                     // queue the next segment's items
-        const uint32_t m = (uint32_t)P.seg_tgt[s + 1].n;
-        if (threadIdx.x == 0) s_word = __hip_atomic_fetch_add(&P.ctr[1], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        const uint32_t base = __builtin_amdgcn_readfirstlane(s_word);
-        for (uint32_t i = threadIdx.x; i < m; i += blockDim.x)
-          __hip_atomic_store(&P.slots[base + i], ((uint32_t)(s + 1) << 16) | i, __ATOMIC_RELEASE,
-                             __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();        // s_word is rewritten by the next wait
-      }
-    }
-#ifdef NFSP_BRP_STAMPS
-    if (threadIdx.x == 0) {
-      if (st_t1) st_chain += BRP_T() - st_t1;
-      unsigned long long* d = g_brp_stamps[0][j & 63];
-      atomicAdd(d + 0, st_wait); atomicAdd(d + 1, st_chain); atomicAdd(d + 2, st_steps); atomicAdd(d + 3, st_pieces);
-    }
-#endif
-    return;
-  }
-  uint32_t* prev_done = nullptr;                           // thread 0: the last item's chunk counter
-  for (;;) {                                                // ---- a helper
-    if (threadIdx.x == 0) {                                // the iteration's one thread-0 region:
-#ifdef NFSP_BRP_STAMPS
-      const unsigned long long t0 = BRP_T();
-      if (st_t1) st_chain += t0 - st_t1;                   // (helpers: work cycles)
-#endif
-      if (prev_done)                                       // publish the last item, take the next
-        __hip_atomic_fetch_add(prev_done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-      const uint32_t p = __hip_atomic_fetch_add(&P.ctr[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      uint32_t v = BRP_DONE;
-      if (p < (uint32_t)P.nitems) {
-        int it = 0;
-        while ((v = __hip_atomic_load(&P.slots[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == BRP_EMPTY &&
-               ++it < P.spin)
-          __builtin_amdgcn_s_sleep(8);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        if (v == BRP_EMPTY) {
-          brp_bail(P.err, 2);
-          v = BRP_DONE;
-        }
-      }
-      s_word = v;
-#ifdef NFSP_BRP_STAMPS
-      st_t1 = BRP_T();
-      st_wait += st_t1 - t0;
-      if (v != BRP_DONE) ++st_steps;
-      if (v == BRP_DONE) {
-        unsigned long long* d = g_brp_stamps[1][(blockIdx.x - P.njobs) & 63];
-        atomicAdd(d + 0, st_wait); atomicAdd(d + 1, st_chain); atomicAdd(d + 2, st_steps);
-      }
-#endif
-    }
-    __syncthreads();
-    const uint32_t v = __builtin_amdgcn_readfirstlane(s_word);
-    __syncthreads();
-    if (v == BRP_DONE) return;                             // workgroup-uniform (scalar)
-    const int s = (int)(v >> 16);
-    const int64_t i = (int64_t)(v & 0xFFFFu);
-    br_targets_item(P.seg_tgt[s], i, P.C.B, P.C.E, P.gamma, P.quirks, P.lr0);
-    __threadfence();
-    __syncthreads();
-    prev_done = &P.chunk_done[P.seg_chunk0[s] + i / P.chunk];
-  }
 }
 
 // mode bits: 1 = the insert counters (both agents; they must be current before the next
@@ -609,27 +395,6 @@ int launch_br_chain(const ChainArgs& C, int blocks, unsigned quirks, bool loss_l
   return launch_chain<1>(C, blocks, loss_log, s, attr);
 }
 
-int launch_br_persist(const BrPersistArgs& P, int helpers, hipStream_t s) {
-  static std::atomic<uint64_t> mask{0};
-  static std::atomic<int> dyn{0};
-  int dev = 0;
-  NFSP_HIP(hipGetDevice(&dev));
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(mask.load(std::memory_order_acquire) & bit)) {
-    hipFuncAttributes fa{};
-    NFSP_HIP(hipFuncGetAttributes(&fa, (const void*)k_br_persist));
-    if ((int)fa.sharedSizeBytes > BRP_STATIC_LDS) return nfsp::fail(NFSP_EINVAL, "k_br_persist: static LDS");
-    const int d = CHAIN_LDS - BRP_STATIC_LDS;
-    if (d < (int)sizeof(Chain3Smem)) return nfsp::fail(NFSP_EINVAL, "k_br_persist: LDS");
-    NFSP_HIP(hipFuncSetAttribute((const void*)k_br_persist, hipFuncAttributeMaxDynamicSharedMemorySize, d));
-    dyn.store(d, std::memory_order_release);
-    mask.fetch_or(bit, std::memory_order_acq_rel);
-  }
-  k_br_persist<<<P.njobs + helpers, 256, dyn.load(std::memory_order_acquire), s>>>(P);
-  NFSP_LAUNCHED("k_br_persist");
-  return NFSP_OK;
-}
-
 template <int TABLE>
 static int launch_finalize_t(const FinalArgs& F, const FinalArgs* tab, int n, int mode, hipStream_t s) {
   k_finalize<TABLE><<<n, 64, 0, s>>>(F, tab, mode);
@@ -662,15 +427,3 @@ int launch_group_xchg(float* const* wtab, float* w0, int R, unsigned nets, unsig
 
 }  // namespace eng
 }  // namespace nfsp
-
-#ifdef NFSP_BRP_STAMPS
-extern "C" int nfsp_debug_brp_stamps(unsigned long long* out, int reset) {
-  NFSP_HIP(hipDeviceSynchronize());
-  NFSP_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_brp_stamps), sizeof(g_brp_stamps)));
-  if (reset) {
-    static unsigned long long zero[2][64][4] = {};
-    NFSP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_brp_stamps), zero, sizeof(zero)));
-  }
-  return NFSP_OK;
-}
-#endif

@@ -1,7 +1,7 @@
 // What learner.hip (the learner's kernels and their host launchers) shares with the host code
 // of a learner call -- engine_update.hip (one engine) and group.hip (an engine group): the plain
 // structs a call's arguments and tables are built from, the plan of one engine's call and its
-// jobs (engine_update.hip), and the launchers.
+// jobs (engine_update.hip), and the launchers.  (The persistent group BR kernel: br_persist.h.)
 #pragma once
 #include <initializer_list>
 #include <vector>
@@ -43,28 +43,18 @@ struct TargetJob {
   unsigned quirks;
 };
 
-// k_br_persist's arguments (learner.hip)
-struct BrPersistArgs {
-  chain::ChainArgs C;           // B, E (the chains' jobs come from seg_job)
-  const chain::ChainJob* seg_job;   // [nseg] chain job of each segment (u0, u1: the segment; sync_to)
-  const TargetJob* seg_tgt;     // [nseg] its targets job
-  const int32_t* seg_chunk0;    // [nseg] its first chunk counter
-  const int32_t* job_seg0;      // [njobs + 1] chain workgroup j's segments: [job_seg0[j], job_seg0[j + 1])
-  uint32_t* slots;              // [nitems] work items (segment << 16 | update in it); BRP_EMPTY until queued
-  uint32_t* ctr;                // [0] helpers' claims, [1] queue reservations
-  uint32_t* chunk_done;         // finished items per chunk
-  int32_t* err;                 // pinned host: [0] a wait expired, [1] chain bails, [2] helper bails
-  int njobs, nitems, chunk;
-  int spin;                     // bound of every wait (s_sleep 8 rounds)
-  double gamma, lr0;
-  unsigned quirks;
+// bump-allocate n items of T in a call's host / device table pair (16-byte aligned offsets)
+struct TabCursor {
+  size_t off = 0;
+  template <class T>
+  size_t take(size_t n) {
+    const size_t o = (off + 15) & ~(size_t)15;
+    off = o + sizeof(T) * n;
+    return o;
+  }
 };
-constexpr int BRP_SPIN = 1 << 18;           // x s_sleep 8 (~56 ms): far past any legitimate wait
-constexpr int BRP_CHUNK = 16;               // updates per chain piece (readiness is checked per piece)
-constexpr int BRP_HELPERS = 48;             // helper workgroups (c4_emul_r8, timeline tool, with
-                                            // the scalar jobs: 96 / 144 / 192 helpers 193.1 /
-                                            // 189.5 / 188.1 ms, the AR chains slowing 155 -> 166;
-                                            // the rounds 179.6)
+template <class T>
+static T* tab_at(char* base, size_t off) { return reinterpret_cast<T*>(base + off); }
 
 // schedule state after the learner (host-computed values + device-side counters)
 struct FinalArgs {
@@ -142,9 +132,6 @@ int launch_finalize_table(const FinalArgs* tab, int n, int mode, hipStream_t s);
 // the targets of `njobs` segments of at most `n` updates (jobs: device table; null: `one`)
 int launch_br_targets(const TargetJob* jobs, const TargetJob& one, int64_t n, int njobs, int B, int E, hipStream_t s);
 int launch_br_chain(const chain::ChainArgs& C, int blocks, unsigned quirks, bool loss_log, hipStream_t s);
-// launch with a CU per workgroup: dynamic LDS up to what the CU has left beside the kernel's
-// static LDS (the helpers' targets buffers), as the one-engine chains reserve theirs
-int launch_br_persist(const BrPersistArgs& P, int helpers, hipStream_t s);
 // engine groups: the replicas' EngineDev gathered into one array; the exchange (k_group_xchg)
 int launch_gather_st(EngineDev* const* src, EngineDev* dst, int R, hipStream_t s);
 int launch_group_xchg(float* const* wtab, float* w0, int R, unsigned nets, unsigned bcast, float scale, hipStream_t s);

@@ -46,13 +46,13 @@ SRCC_WAR = 3          # compiler model: VALU write of an MFMA's SrcC, wait state
 DST_WAW = 8           # compiler model: VALU write (or read) of its result
 PK_WINDOW = 32        # empirical: packed-f32 writes of any MFMA register
 PACKED = ("v_pk_fma_f32", "v_pk_mul_f32", "v_pk_add_f32")
-SOURCES = {"br": "learner.hip", "ar": "chain_ar.hip", "brlin": "chain_brlin.hip"}
+SOURCES = {"br": "learner.hip", "ar": "chain_ar.hip", "brlin": "chain_brlin.hip", "brp": "br_persist.hip"}
 KERNEL_PREFIX = "_ZN4nfsp5chain8k_chain3"
 
 
 def is_chain_kernel(name: str) -> bool:
     """A k_chain3 instance, or the persistent group BR kernel that runs the chain body inlined
-    (learner.hip k_br_persist)."""
+    (br_persist.hip k_br_persist)."""
     return name.startswith(KERNEL_PREFIX) or "k_br_persist" in name
 _REG = re.compile(r"\b([vas])(?:(\d+)|\[(\d+):(\d+)\])")
 
@@ -112,7 +112,9 @@ def functions(asm_lines: list) -> dict:
     i = 0
     while i < len(asm_lines):
         l = asm_lines[i]
-        if is_chain_kernel(l.split(":")[0]) and l.split(":")[0].endswith("E") and not l.startswith("."):
+        # a kernel's label, at the start of its line (its .amdhsa_kernel / .set lines are indented)
+        if (":" in l and not l[:1].isspace() and not l.startswith(".") and is_chain_kernel(l.split(":")[0])
+                and l.split(":")[0].endswith("E")):
             name = l.split(":")[0]
             ins, labels, loops = [], {}, []
             j = i + 1
