@@ -647,6 +647,24 @@ int nfsp_evaluate_batch(nfsp_ctx* ctx, const nfsp_policy* seat0, const nfsp_poli
  * table gives the bits scoring the policy gives.  Replaces kuhn_policy.py's per-information-set
  * read-out through the oracle's Env.  Synchronises the ctx stream. */
 int nfsp_policy_table(nfsp_ctx* ctx, const nfsp_policy* policy, double* dev_out);
+/* The exact best responses as a strategy, where nfsp_evaluate_batch only has their values: one
+ * joint table dev_beta[ndec][3][3] (f64, device).  Rows where seat 0 acts hold seat 0's best
+ * response against seat1, rows where seat 1 acts seat 1's against seat0; every row and rank is
+ * one-hot, information sets the responder's own earlier actions never reach included.  The
+ * argmax is over the legal children in ascending action order and a later action wins only if
+ * strictly greater: a tie, and every information set the opponent never reaches, folds (then
+ * calls); an illegal raise is never chosen.  dev_q[d][r][a] (or NULL): the counterfactual value
+ * of the child under action a -- what k_evaluate's max runs over, summed over the opponent's
+ * rank; 0 for an illegal raise.  dev_reach[d][r] (or NULL): the counterfactual reach of the
+ * information set summed over the opponent's rank, so q / reach is the expected chips of each
+ * action given that it is reached: the quantity the Q net is to learn.  Scoring the table
+ * against the same opponent gives nfsp_evaluate_batch's br0 / br1.  Replaces the action-value
+ * side of kuhn_diag.py's per-information-set read-out.  The outputs must not overlap either
+ * policy's memory or each other (refused).  One workgroup (csrc/evaluate.hip k_best_response: k_evaluate's phases for
+ * its first two evaluations, same sums).  Synchronises the ctx stream. */
+int nfsp_best_response_table(nfsp_ctx* ctx, const nfsp_policy* seat0, const nfsp_policy* seat1,
+                             double* dev_beta /*[ndec][3][3]*/, double* dev_q /*[ndec][3][3] or NULL*/,
+                             double* dev_reach /*[ndec][3] or NULL*/);
 
 /* ---- CFR+ on the evaluator's tree (csrc/cfr.hip k_cfr_plus) ----
  * A tabular equilibrium of the game as played here: the absolute anchor the Leduc variant lacked
@@ -664,6 +682,42 @@ int nfsp_cfr_iterations(nfsp_cfr* h, int64_t* out);
 int nfsp_cfr_average(nfsp_cfr* h, const double** dev_table);
 int nfsp_cfr_state(nfsp_cfr* h, double* host_R /*[ndec][3][3]*/, double* host_S /*[ndec][3][3]*/);
 int nfsp_cfr_destroy(nfsp_cfr* h);
+
+/* ---- full-width extensive-form fictitious play on the evaluator's tree (csrc/xfp.hip k_xfp) ----
+ * XFP (Heinrich, Lanctot and Silver 2015), the algorithm NFSP samples and approximates: every
+ * iteration both seats compute the exact best response (nfsp_best_response_table's tie rule) to
+ * the current average strategy and mix it into the average in realisation weights.  Its curve
+ * is what fictitious play itself does on this tree with a perfect best response and perfect
+ * averaging, in nfsp_evaluate_batch's units: the ideal beside the engine's curves and the CFR+
+ * anchor (the reference has neither).  With eta > 0 the response is to the per-hand mixture
+ * (1 - eta) x average + eta x last best response: NFSP's anticipatory parameter.
+ * A handle holds n independent runs, one workgroup per run in one launch -- a study is a sweep
+ * over eta and the weighting.  Per run: S and B [ndec][3][3], the weighted sum of the best
+ * responses' realisation plans and the last one's (0 / 1, so S holds exact integers), and the
+ * weight sum W; all 0 at creation.  A run is cut into launches of at most NFSP_XFP_LAUNCH_ITERS. */
+#define NFSP_XFP_WEIGHT_UNIFORM 0    /* w_t = 1: fictitious play's 1/t average */
+#define NFSP_XFP_WEIGHT_LINEAR 1     /* w_t = t */
+#define NFSP_XFP_LAUNCH_ITERS 1024
+#define NFSP_XFP_MAX_RUNS 1024
+typedef struct {
+  double eta;                           /* in [0, 1) */
+  int32_t weight;                       /* NFSP_XFP_WEIGHT_* */
+  int32_t reserved;                     /* 0 */
+} nfsp_xfp_cfg;                         /* 16 bytes */
+typedef struct nfsp_xfp nfsp_xfp;
+int nfsp_xfp_create(nfsp_ctx* ctx, const nfsp_xfp_cfg* cfgs /*[n]*/, int n, nfsp_xfp** out);
+/* Continues every run by iters iterations; synchronises.  host_gaps[n][iters] (or NULL): per run
+ * and iteration br_0 + br_1 of the strategy responded to -- with eta = 0 the exploitability of
+ * the average after the iterations before it (the first ever is the uniform policy's). */
+int nfsp_xfp_run(nfsp_xfp* h, int64_t iters, double* host_gaps);
+int nfsp_xfp_iterations(nfsp_xfp* h, int64_t* out);
+/* The average strategy of a run after the last launch: S normalised per row, uniform over the
+ * legal actions where a row's sum is 0 (every row before any iteration).  A device table usable
+ * as NFSP_POL_TABLE; owned by the handle. */
+int nfsp_xfp_average(nfsp_xfp* h, int run, const double** dev_table);
+int nfsp_xfp_state(nfsp_xfp* h, int run, double* host_S /*[ndec][3][3]*/, double* host_B /*[ndec][3][3]*/,
+                   double* W);
+int nfsp_xfp_destroy(nfsp_xfp* h);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,9 @@
 //     response of the evaluator the reference left commented out (main.py:82-120);
 //   * a table [ndec][3 ranks][3 actions] of doubles, for whatever is not a net.
 // and two more outputs, seat 0's value per dealer.  k_policy_table writes the policy phase's
-// result out as such a table.  Oracle: oracle/exploit_oracle.py with a TabularPolicy.
+// result out as such a table; k_best_response keeps the argmax the best-response evaluations
+// take a max over, as a joint one-hot table with the action values beside it.  Oracle:
+// oracle/exploit_oracle.py with a TabularPolicy.
 #include "exploit_tree.h"
 #include "nn_device.h"
 
@@ -201,6 +203,108 @@ __global__ void __launch_bounds__(256) k_policy_table(PtArgs A) {
   }
 }
 
+// The exact best responses as a strategy: k_evaluate's phases for evaluations e = 0 and 1 (the
+// same sums in the same order), with the argmax its max discards.  Seat e's rows of the joint
+// table hold its best response against the other seat's policy; q is the child values the max
+// runs over, rch the counterfactual reach of the information set summed over the opponent's
+// rank.  The first maximum among the legal children wins, so a tie and every information set
+// the opponent never reaches fold.  One workgroup; 2 nlev + 2 barriers.
+struct BrArgs {
+  ExTables T;
+  nfsp_policy pol[2];
+  double* beta;                  // [ndec][3][3]
+  double* q;                     // [ndec][3][3] or null
+  double* rch;                   // [ndec][3] or null
+};
+__host__ __device__ inline size_t br_lds(int nn, int ndec) {
+  return ev_off_pol() + 8 * ((size_t)ndec * 9 + (size_t)nn * 18 + (size_t)nn * 6);
+}
+
+__global__ void __launch_bounds__(256) k_best_response(BrArgs A) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const ExTables& T = A.T;
+  float* sw = reinterpret_cast<float*>(smem_raw);                      // [2][NP]
+  double* pol = reinterpret_cast<double*>(smem_raw + ev_off_pol());    // [ndec][3 ranks][3]
+  double* reach = pol + (size_t)T.ndec * 9;                            // [nn][2 evals][3][3]
+  double* val = reach + (size_t)T.nn * 18;                             // [nn][2 evals][3]
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int NP = nfsp::nn::NP;
+  const nfsp_policy P0 = A.pol[0], P1 = A.pol[1];
+  for (int k = tid; k < 2 * NP; k += nt) {
+    const nfsp_policy& P = k < NP ? P0 : P1;
+    if (kind_is_net(P.kind)) sw[k] = static_cast<const float*>(P.dev)[k < NP ? k : k - NP];
+  }
+  __syncthreads();
+  for (int k = tid; k < T.ndec * 3; k += nt) {
+    const int p = T.legal[k / 3] >> 1;
+    const nfsp_policy& P = p ? P1 : P0;
+    policy_row(P.kind, sw + p * NP, static_cast<const double*>(P.dev), T, k, pol + 3 * (size_t)k);
+  }
+  __syncthreads();
+  // reach of seat e's ranks ri against the opponent's ro, without seat e's own actions
+  for (int L = 0; L < T.nlev; ++L) {
+    const int n0 = T.lev[L], cnt = (T.lev[L + 1] - n0) * 18;
+    for (int k = tid; k < cnt; k += nt) {
+      const int n = n0 + k / 18, e = (k / 9) % 2, ri = (k / 3) % 3, ro = k % 3;
+      const DevNode& N = T.nodes[n];
+      double r;
+      if (N.parent < 0) {
+        r = T.deal[ri][ro];
+      } else {
+        const DevNode& P = T.nodes[N.parent];
+        const double r0 = reach[(size_t)N.parent * 18 + e * 9 + ri * 3 + ro];
+        if (P.kind == TNode::CHANCE) r = r0 * p_public(N.via, ri, ro);
+        else if (P.p == e) r = r0;
+        else r = r0 * pol[(size_t)P.row * 9 + ro * 3 + N.via];
+      }
+      reach[(size_t)n * 18 + e * 9 + ri * 3 + ro] = r;
+    }
+    __syncthreads();
+  }
+  // values bottom-up; a decision of seat e writes its row of the outputs
+  for (int L = T.nlev - 1; L >= 0; --L) {
+    const int n0 = T.lev[L], cnt = (T.lev[L + 1] - n0) * 6;
+    for (int k = tid; k < cnt; k += nt) {
+      const int n = n0 + k / 6, e = (k / 3) % 2, ri = k % 3;
+      const DevNode& N = T.nodes[n];
+      double v = 0.0;
+      if (N.kind == TNode::TERMINAL) {
+        const double* rr = reach + (size_t)n * 18 + e * 9 + ri * 3;
+        const float* py = T.pay + (size_t)N.row * 18 + e * 9 + ri * 3;
+        for (int ro = 0; ro < 3; ++ro)
+          if (rr[ro] != 0.0) v += rr[ro] * (double)py[ro];
+      } else if (N.kind == TNode::DECISION && N.p == e) {
+        int best = -1;
+        double c3[3] = {0.0, 0.0, 0.0};
+        for (int a = 0; a < 3; ++a) {
+          if (N.child[a] < 0) continue;
+          const double c = val[(size_t)N.child[a] * 6 + e * 3 + ri];
+          c3[a] = c;
+          if (best < 0 || c > v) {
+            v = c;
+            best = a;
+          }
+        }
+        const size_t row = (size_t)N.row * 3 + ri;
+        for (int a = 0; a < 3; ++a) {
+          A.beta[3 * row + a] = a == best ? 1.0 : 0.0;
+          if (A.q) A.q[3 * row + a] = c3[a];
+        }
+        if (A.rch) {
+          const double* rr = reach + (size_t)n * 18 + e * 9 + ri * 3;
+          A.rch[row] = (rr[0] + rr[1]) + rr[2];
+        }
+      } else {
+        for (int a = 0; a < 3; ++a)
+          if (N.child[a] >= 0) v += val[(size_t)N.child[a] * 6 + e * 3 + ri];
+      }
+      val[(size_t)n * 6 + e * 3 + ri] = v;
+    }
+    __syncthreads();
+  }
+}
+
 int check_policy(const nfsp_policy& p) {
   NFSP_REQUIRE(p.kind >= NFSP_POL_AR_SOFTMAX && p.kind <= NFSP_POL_TABLE, "unknown policy kind (NFSP_POL_*)");
   NFSP_REQUIRE(p.reserved == 0, "nfsp_policy.reserved must be 0");
@@ -246,6 +350,46 @@ extern "C" int nfsp_evaluate_batch(nfsp_ctx* ctx, const nfsp_policy* seat0, cons
     NFSP_LAUNCHED("k_evaluate");
   }
   NFSP_HIP(hipMemcpyAsync(out, bo.p, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, ctx->stream));
+  NFSP_HIP(hipStreamSynchronize(ctx->stream));
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_best_response_table(nfsp_ctx* ctx, const nfsp_policy* seat0, const nfsp_policy* seat1,
+                                        double* dev_beta, double* dev_q, double* dev_reach) {
+  NFSP_REQUIRE(ctx && seat0 && seat1 && dev_beta, "null argument");
+  int rc = check_policy(*seat0);
+  if (rc == NFSP_OK) rc = check_policy(*seat1);
+  if (rc != NFSP_OK) return rc;
+  const DevTables* D = nullptr;
+  rc = device_tables(ctx, &D);
+  if (rc != NFSP_OK) return rc;
+  const size_t n9 = sizeof(double) * 9 * (size_t)D->T.ndec;
+  const char* outs[3] = {reinterpret_cast<const char*>(dev_beta), reinterpret_cast<const char*>(dev_q),
+                         reinterpret_cast<const char*>(dev_reach)};
+  const size_t outb[3] = {n9, n9, n9 / 3};
+  for (const nfsp_policy* p : {seat0, seat1}) {      // the kernel reads the policies while it writes
+    const char* lo = static_cast<const char*>(p->dev);
+    const char* hi = lo + (p->kind == NFSP_POL_TABLE ? n9 : sizeof(float) * nfsp::nn::NP);
+    for (int k = 0; k < 3; ++k)
+      NFSP_REQUIRE(!outs[k] || outs[k] + outb[k] <= lo || hi <= outs[k],
+                   "nfsp_best_response_table: an output aliases a policy");
+  }
+  for (int k = 0; k < 3; ++k)
+    for (int j = k + 1; j < 3; ++j)
+      NFSP_REQUIRE(!outs[k] || !outs[j] || outs[k] + outb[k] <= outs[j] || outs[j] + outb[j] <= outs[k],
+                   "nfsp_best_response_table: two outputs alias each other");
+  const size_t lds = br_lds(D->T.nn, D->T.ndec);
+  NFSP_REQUIRE(lds <= EX_MAX_LDS, "best-response tables exceed the LDS");
+  NFSP_HIP(hipFuncSetAttribute((const void*)k_best_response, hipFuncAttributeMaxDynamicSharedMemorySize, EX_MAX_LDS));
+  BrArgs A{};
+  A.T = D->T;
+  A.pol[0] = *seat0;
+  A.pol[1] = *seat1;
+  A.beta = dev_beta;
+  A.q = dev_q;
+  A.rch = dev_reach;
+  k_best_response<<<1, 256, lds, ctx->stream>>>(A);
+  NFSP_LAUNCHED("k_best_response");
   NFSP_HIP(hipStreamSynchronize(ctx->stream));
   return NFSP_OK;
 }

@@ -261,6 +261,20 @@ class SelfPlayEngine:
         kuhn_diag's ``anticip``."""
         return _br_gaps(self.ctx, [self], ar_mode, eta)[0]
 
+    def best_response_table(self, eta: float | None = None, values: bool = False):
+        """The exact best responses behind ``br_gap``'s ``br_exact``, as a strategy
+        (``evaluation.best_response``): one joint one-hot table ``[ndec, 3, 3]`` (a float64
+        device tensor) whose rows where seat i acts are seat i's best response against the other
+        agent's AR policy -- with ``eta`` against its per-hand mixture, built as ``br_gap(eta=)``
+        builds it.  Compare it row by row with the greedy BR net's table
+        (``evaluation.policy_table(ctx, engine.policy(i, NET_BR))``) to see where the learned
+        best response deviates; with ``values`` returns ``(beta, q, reach)``, the exact action
+        values there."""
+        from . import evaluation as ev
+        tree = ev.GameTree(self.ctx.game)
+        opp = _opponents(self.ctx, self, 0, eta, tree)
+        return ev.best_response(self.ctx, opp[0], opp[1], values, tree)
+
     # -- checkpoints (checkpoint.py, DESIGN.md §10) ----------------------------------
     def save(self, path):
         """Save the engine at a step boundary (nfsp_engine_save_state); returns the bytes written."""
@@ -540,6 +554,21 @@ def exploitability_batch(ctx, dev_w_ar0: list, dev_w_ar1: list, mode: int = 0) -
             for k in range(n)]
 
 
+def _opponents(ctx, e, ar_mode, eta, tree) -> list:
+    """[the policy agent 1 - o faces at seat o, o = 0, 1]: engine e's AR policy there, or with
+    ``eta`` the per-hand mixture eta x greedy BR + (1 - eta) x AR it plays in self-play."""
+    from . import evaluation as ev
+    opp = []
+    for o in (0, 1):
+        if eta is None:
+            opp.append(e.policy(o, NET_AR, ar_mode))
+        else:
+            ar = ev.policy_table(ctx, e.policy(o, NET_AR, ar_mode), tree).cpu().numpy()
+            br = ev.policy_table(ctx, e.policy(o, NET_BR), tree).cpu().numpy()
+            opp.append(ev.Policy.table(ev.mix(tree, [(eta, br), (1.0 - eta, ar)])))
+    return opp
+
+
 def _br_gaps(ctx, engines, ar_mode, eta) -> list:
     """br_gap of each engine: per agent {br_exact, br_learned, gap}; one nfsp_evaluate_batch."""
     from . import evaluation as ev
@@ -547,14 +576,7 @@ def _br_gaps(ctx, engines, ar_mode, eta) -> list:
     keep = []
     tree = ev.GameTree(ctx.game) if eta is not None else None
     for e in engines:
-        opp = []
-        for o in (0, 1):                       # the policy agent 1 - o faces at seat o
-            if eta is None:
-                opp.append(e.policy(o, NET_AR, ar_mode))
-            else:
-                ar = ev.policy_table(ctx, e.policy(o, NET_AR, ar_mode), tree).cpu().numpy()
-                br = ev.policy_table(ctx, e.policy(o, NET_BR), tree).cpu().numpy()
-                opp.append(ev.Policy.table(ev.mix(tree, [(eta, br), (1.0 - eta, ar)])))
+        opp = _opponents(ctx, e, ar_mode, eta, tree)
         keep.append(opp)
         pairs += [(e.policy(0, NET_BR), opp[1]), (opp[0], e.policy(1, NET_BR))]
     res = ev.evaluate_batch(ctx, pairs)

@@ -11,11 +11,18 @@ the project meets, on the same public tree and with the same f64 walk
                             the reference left commented out (main.py:82-120);
 * ``Policy.table(t)``       a behavioural strategy ``[ndec][3 ranks][3 actions]`` over the rows of
                             ``GameTree``: a net read out with ``policy_table``, a ``mix`` of
-                            tables, a ``CfrSolver`` average, anything written by hand.
+                            tables, a ``CfrSolver`` or ``XfpSolver`` average, a ``best_response``,
+                            anything written by hand.
+
+``best_response`` (``nfsp_best_response_table``) gives the exact best responses the scores
+are the values of as a table, with the exact action values at every information set: where a
+learned BR net deviates, and by how much.
 
 ``GameTree`` (host only, no GPU) is the tree as data; ``CfrSolver`` runs CFR+ on it
 (``nfsp_cfr_*``, csrc/cfr.hip), which anchors the Leduc variant the way the analytic Nash
-family anchors Kuhn.
+family anchors Kuhn.  ``XfpSolver`` runs full-width fictitious play on it (``nfsp_xfp_*``,
+csrc/xfp.hip), n runs over eta and the weighting at once: the curve of the algorithm NFSP
+approximates, with an exact best response and exact averaging.
 """
 from __future__ import annotations
 
@@ -226,6 +233,97 @@ def policy_table(ctx, policy: Policy, tree: GameTree | None = None):
     spec = policy.spec()
     native.check(ctx.L.nfsp_policy_table(ctx.h, C.byref(spec), native.P(out.data_ptr())), "nfsp_policy_table")
     return out
+
+
+def best_response(ctx, seat0: Policy, seat1: Policy, values: bool = False, tree: GameTree | None = None):
+    """``nfsp_best_response_table``: the exact best responses as one joint one-hot table, a
+    float64 device tensor ``[ndec, 3, 3]`` -- rows where seat 0 acts hold its best response
+    against ``seat1``, rows where seat 1 acts its best response against ``seat0`` (first maximum
+    over the legal actions: ties and unreached information sets fold).  ``Policy.table`` of it
+    scores ``evaluate``'s br0 at seat 0 and br1 at seat 1.
+
+    With ``values`` returns ``(beta, q, reach)``: ``q[d, r, a]`` the counterfactual value of
+    action a (0 for an illegal raise), ``reach[d, r]`` the counterfactual reach of the
+    information set, so ``q / reach`` is the exact expected chips per action given that it is
+    reached -- what a BR net's Q head is to learn there."""
+    import torch
+    tree = tree or GameTree(ctx.game)
+    beta = torch.empty((tree.ndec, 3, 3), dtype=torch.float64, device="cuda")
+    q = torch.empty((tree.ndec, 3, 3), dtype=torch.float64, device="cuda") if values else None
+    reach = torch.empty((tree.ndec, 3), dtype=torch.float64, device="cuda") if values else None
+    s0, s1 = seat0.spec(), seat1.spec()
+    native.check(ctx.L.nfsp_best_response_table(
+        ctx.h, C.byref(s0), C.byref(s1), native.P(beta.data_ptr()),
+        native.P(q.data_ptr()) if values else None, native.P(reach.data_ptr()) if values else None),
+        "nfsp_best_response_table")
+    return (beta, q, reach) if values else beta
+
+
+class XfpSolver:
+    """Full-width extensive-form fictitious play on the evaluator's tree (``nfsp_xfp_*``): the
+    ideal curve of the algorithm NFSP approximates.  ``cfgs`` is one ``(eta, weight)`` per
+    independent run (weight: ``native.XFP_WEIGHT_UNIFORM`` / ``_LINEAR`` or "uniform" /
+    "linear"); all runs advance together, one workgroup each.  ``run(n)`` continues them by n
+    iterations (with ``gaps=True`` it returns the ``[runs, n]`` array of br0 + br1 of the
+    strategy each iteration responded to: at eta = 0 the exploitability of the average so far),
+    ``average(k)`` is run k's average strategy as a ``Policy``."""
+
+    WEIGHTS = {"uniform": native.XFP_WEIGHT_UNIFORM, "linear": native.XFP_WEIGHT_LINEAR}
+
+    def __init__(self, ctx, cfgs=((0.0, native.XFP_WEIGHT_UNIFORM),)):
+        self.ctx = ctx
+        self.tree = GameTree(ctx.game)
+        self.cfgs = [(float(eta), int(self.WEIGHTS.get(w, w))) for eta, w in cfgs]
+        self.n = len(self.cfgs)
+        arr = (native.XfpCfg * max(self.n, 1))(*[native.XfpCfg(eta, w, 0) for eta, w in self.cfgs])
+        h = native.P()
+        native.check(ctx.L.nfsp_xfp_create(ctx.h, arr, self.n, C.byref(h)), "nfsp_xfp_create")
+        self.h = h
+
+    def run(self, iters: int, gaps: bool = False):
+        out = np.zeros((self.n, max(int(iters), 0))) if gaps else None    # iters < 0: the library refuses
+        native.check(self.ctx.L.nfsp_xfp_run(self.h, int(iters), out.ctypes.data_as(native.P) if gaps else None),
+                     "nfsp_xfp_run")
+        return out if gaps else self
+
+    @property
+    def iterations(self) -> int:
+        n = native.I64(0)
+        native.check(self.ctx.L.nfsp_xfp_iterations(self.h, C.byref(n)), "nfsp_xfp_iterations")
+        return n.value
+
+    def average(self, run: int = 0) -> Policy:
+        p = native.P()
+        native.check(self.ctx.L.nfsp_xfp_average(self.h, int(run), C.byref(p)), "nfsp_xfp_average")
+        return Policy(native.POL_TABLE, None, p.value, self)
+
+    def average_table(self, run: int = 0) -> np.ndarray:
+        import torch
+        from .engine import _wrap_device
+        t = _wrap_device(self.average(run).ptr, self.tree.ndec * 9, torch.float64,
+                         torch.device("cuda", torch.cuda.current_device()), self)
+        return t.cpu().numpy().reshape(self.tree.ndec, 3, 3).copy()
+
+    def state(self, run: int = 0) -> tuple:
+        """(S, B, W) of a run: the weighted sum of the best responses' realisation plans and
+        the last one's, ``[ndec, 3, 3]`` each, and the sum of the weights."""
+        S = np.zeros((self.tree.ndec, 3, 3))
+        B = np.zeros((self.tree.ndec, 3, 3))
+        W = native.F64(0.0)
+        native.check(self.ctx.L.nfsp_xfp_state(self.h, int(run), S.ctypes.data_as(native.P),
+                                               B.ctypes.data_as(native.P), C.byref(W)), "nfsp_xfp_state")
+        return S, B, W.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.L.nfsp_xfp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class CfrSolver:

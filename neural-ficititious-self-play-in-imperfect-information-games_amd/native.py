@@ -91,6 +91,11 @@ class PolicySpec(C.Structure):
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("dev", P)]
 
 
+class XfpCfg(C.Structure):
+    """``nfsp_xfp_cfg``: one fictitious-play run's eta and weighting (XFP_WEIGHT_*)"""
+    _fields_ = [("eta", C.c_double), ("weight", C.c_int32), ("reserved", C.c_int32)]
+
+
 PP = C.POINTER(P)
 # name -> (restype, argtypes); must list every symbol include/nfsp.h declares
 SIGNATURES = {
@@ -142,6 +147,13 @@ SIGNATURES = {
     "nfsp_cfr_average": (I32, [P, C.POINTER(P)]),
     "nfsp_cfr_state": (I32, [P, P, P]),
     "nfsp_cfr_destroy": (I32, [P]),
+    "nfsp_best_response_table": (I32, [P, C.POINTER(PolicySpec), C.POINTER(PolicySpec), P, P, P]),
+    "nfsp_xfp_create": (I32, [P, C.POINTER(XfpCfg), I32, C.POINTER(P)]),
+    "nfsp_xfp_run": (I32, [P, I64, P]),
+    "nfsp_xfp_iterations": (I32, [P, C.POINTER(I64)]),
+    "nfsp_xfp_average": (I32, [P, I32, C.POINTER(P)]),
+    "nfsp_xfp_state": (I32, [P, I32, P, P, C.POINTER(F64)]),
+    "nfsp_xfp_destroy": (I32, [P]),
     "nfsp_engine_set_loss_log": (I32, [P, I32]),
     "nfsp_engine_losses": (I32, [P, P]),
     "nfsp_engine_set_timing": (I32, [P, I32]),
@@ -193,6 +205,10 @@ GROUP_MAX_REPLICAS = 256
 # nfsp_policy kinds (include/nfsp.h NFSP_POL_*) and the CFR+ launch cap (NFSP_CFR_LAUNCH_ITERS)
 POL_AR_SOFTMAX, POL_AR_ARGMAX, POL_BR_GREEDY, POL_BR_GREEDY_LINEAR, POL_TABLE = 0, 1, 2, 3, 4
 CFR_LAUNCH_ITERS = 1024
+# fictitious-play weightings (NFSP_XFP_WEIGHT_*), the launch cap and the most runs of a handle
+XFP_WEIGHT_UNIFORM, XFP_WEIGHT_LINEAR = 0, 1
+XFP_LAUNCH_ITERS = 1024
+XFP_MAX_RUNS = 1024
 
 _LIB = None
 

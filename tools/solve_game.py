@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """A tabular equilibrium of the game as the engine plays it: CFR+ on the evaluator's tree
-(evaluation.CfrSolver, csrc/cfr.hip), scored by the evaluator itself (nfsp_evaluate_batch).
+(evaluation.CfrSolver, csrc/cfr.hip), scored by the evaluator itself (nfsp_evaluate_batch) --
+or, with --solver xfp, the curve of full-width fictitious play on it (evaluation.XfpSolver,
+csrc/xfp.hip): the algorithm NFSP approximates, with an exact best response and averaging.
 
     python tools/solve_game.py --game leduc --iters 4096 --out eq.npz
+    python tools/solve_game.py --game leduc --solver xfp --weight linear --eta 0.1 --iters 4096
+    python tools/solve_game.py --game leduc --solver xfp --eta 0.5 --runs 64 --every 1024
 
 eq.npz holds ``table`` [ndec, 3 ranks, 3 actions] (rows as evaluation.GameTree's; usable as
 evaluation.Policy.table), ``game``, and per checkpoint (--every, doubling by default)
@@ -10,6 +14,12 @@ evaluation.Policy.table), ``game``, and per checkpoint (--every, doubling by def
 what seat 0 wins per hand when it deals / when seat 1 deals.  The game value per dealer lies
 within the exploitability of that row.  One JSON line per checkpoint goes to stdout, with the
 solver's milliseconds per iteration.
+
+--solver xfp: --eta is the anticipatory parameter (the best response is to (1 - eta) x average
++ eta x last best response), --weight the averaging (uniform: 1/t; linear: t).  --runs N > 1
+runs N independent runs in the one launch, eta evenly spaced over [0, --eta]; the fields above
+are then the last run's (eta = --eta), ``eta_runs`` / ``exploitability_runs`` list every run's,
+and eq.npz also holds ``tables`` [N, ndec, 3, 3].  The milliseconds are the whole handle's.
 """
 import argparse
 import json
@@ -26,8 +36,12 @@ sys.path.insert(0, REPO)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--game", default="leduc", choices=["leduc", "kuhn"])
+    ap.add_argument("--solver", default="cfr", choices=["cfr", "xfp"])
     ap.add_argument("--iters", type=int, default=1024)
     ap.add_argument("--every", type=int, default=0, help="checkpoint every K iterations (default: 1, 2, 4, ...)")
+    ap.add_argument("--eta", type=float, default=0.0, help="xfp: anticipatory parameter, in [0, 1)")
+    ap.add_argument("--weight", default="uniform", choices=["uniform", "linear"], help="xfp: averaging weights")
+    ap.add_argument("--runs", type=int, default=1, help="xfp: runs in one launch, eta spaced over [0, --eta]")
     ap.add_argument("--out", default=None, metavar="PATH")
     args = ap.parse_args()
     import __graft_entry__
@@ -35,7 +49,12 @@ def main():
     ev, nat = pkg.evaluation, pkg.native
     game = nat.GAME_KUHN if args.game == "kuhn" else nat.GAME_LEDUC
     ctx = nat.Context(1, game=game)
-    solver = ev.CfrSolver(ctx)
+    xfp = args.solver == "xfp"
+    if xfp:
+        etas = [args.eta] if args.runs == 1 else [float(e) for e in np.linspace(0.0, args.eta, args.runs)]
+        solver = ev.XfpSolver(ctx, [(e, args.weight) for e in etas])
+    else:
+        solver = ev.CfrSolver(ctx)
     rows = []
     done = 0
     while done < args.iters:
@@ -44,20 +63,34 @@ def main():
         solver.run(nxt - done)
         ms = (time.perf_counter() - t0) * 1e3 / (nxt - done)
         done = nxt
-        eq = solver.average()
-        r = ev.evaluate(ctx, eq, eq)
+        if xfp:
+            avgs = [solver.average(k) for k in range(len(etas))]
+            res = ev.evaluate_batch(ctx, [(a, a) for a in avgs])
+            r = res[-1]
+        else:
+            eq = solver.average()
+            r = ev.evaluate(ctx, eq, eq)
         rec = {"game": args.game, "iterations": done, "exploitability": r["exploitability"], "br0": r["br0"],
                "br1": r["br1"], "value0": r["value0"],
                "value0_dealer": [r["value0_dealer0"], r["value0_dealer1"]], "ms_per_iteration": ms}
+        if xfp:
+            rec.update(solver="xfp", weight=args.weight, eta=etas[-1])
+            if len(etas) > 1:
+                rec.update(eta_runs=etas, exploitability_runs=[x["exploitability"] for x in res])
         rows.append(rec)
         print(json.dumps(rec), flush=True)
     if args.out:
-        np.savez(args.out, table=solver.average_table(), game=args.game,
+        extra = {}
+        if xfp:
+            extra = {"tables": np.stack([solver.average_table(k) for k in range(len(etas))]), "eta": np.array(etas),
+                     "weight": args.weight}
+        np.savez(args.out, table=solver.average_table(len(etas) - 1) if xfp else solver.average_table(),
+                 game=args.game,
                  iterations=np.array([r["iterations"] for r in rows]),
                  exploitability=np.array([r["exploitability"] for r in rows]),
                  br0=np.array([r["br0"] for r in rows]), br1=np.array([r["br1"] for r in rows]),
                  value0=np.array([r["value0"] for r in rows]),
-                 value0_dealer=np.array([r["value0_dealer"] for r in rows]))
+                 value0_dealer=np.array([r["value0_dealer"] for r in rows]), **extra)
     solver.close()
 
 
