@@ -582,9 +582,10 @@ int nfsp_state_digest(const void* payload, int64_t n, uint64_t out[2]);
  * argmax the env executes (leduc/newenv.py:135-145).  out[0] / out[1]: best-response value
  * of seat 0 / 1 against the other seat's policy, over both dealers and all deals;
  * out[2] = out[0] + out[1] (exploitability, chips); out[3] = seat 0's on-policy value.
- * The whole evaluation runs on the device (csrc/exploit.hip k_exploit_walk: the policies,
- * reach top-down and best-response values bottom-up over the public tree, in f64); only
- * the 4 results come back.  Synchronises the ctx stream. */
+ * The whole evaluation runs on the device (csrc/evaluate.hip k_evaluate, as nfsp_evaluate_batch
+ * below with NFSP_POL_AR_SOFTMAX / NFSP_POL_AR_ARGMAX on both seats: the policies, reach
+ * top-down and best-response values bottom-up over the public tree, in f64); only the 4
+ * results come back.  Synchronises the ctx stream. */
 int nfsp_exploitability(nfsp_ctx* ctx, const float* dev_w_ar0, const float* dev_w_ar1, int mode,
                         double* out /*[4]*/);
 /* The same for n pairs of nets at once (one workgroup per pair; e.g. every replica of an
@@ -637,8 +638,8 @@ typedef struct {
 /* Pair k plays seat0[k] at seat 0 against seat1[k] at seat 1.  out[6k..6k+5]: seat 0's best-response
  * value against seat1[k], seat 1's against seat0[k], their sum, seat 0's on-policy value, and that
  * value over dealer-0 hands only and over dealer-1 hands only (value0 = half their sum).  One
- * workgroup per pair (csrc/evaluate.hip k_evaluate: k_exploit_walk's three phases, f64, same
- * sums); with kinds 0 / 1 on both seats the first four equal nfsp_exploitability's bits.
+ * workgroup per pair (csrc/evaluate.hip k_evaluate: three phases, f64, the sums of
+ * csrc/tree_walk.h); with kinds 0 / 1 on both seats the first four are nfsp_exploitability's.
  * Synchronises the ctx stream. */
 int nfsp_evaluate_batch(nfsp_ctx* ctx, const nfsp_policy* seat0, const nfsp_policy* seat1, int n,
                         double* out /*[6n]*/);
@@ -660,8 +661,8 @@ int nfsp_policy_table(nfsp_ctx* ctx, const nfsp_policy* policy, double* dev_out)
  * action given that it is reached: the quantity the Q net is to learn.  Scoring the table
  * against the same opponent gives nfsp_evaluate_batch's br0 / br1.  Replaces the action-value
  * side of kuhn_diag.py's per-information-set read-out.  The outputs must not overlap either
- * policy's memory or each other (refused).  One workgroup (csrc/evaluate.hip k_best_response: k_evaluate's phases for
- * its first two evaluations, same sums).  Synchronises the ctx stream. */
+ * policy's memory or each other (refused).  One workgroup (csrc/evaluate.hip k_best_response:
+ * k_evaluate's walk for its first two evaluations).  Synchronises the ctx stream. */
 int nfsp_best_response_table(nfsp_ctx* ctx, const nfsp_policy* seat0, const nfsp_policy* seat1,
                              double* dev_beta /*[ndec][3][3]*/, double* dev_q /*[ndec][3][3] or NULL*/,
                              double* dev_reach /*[ndec][3] or NULL*/);

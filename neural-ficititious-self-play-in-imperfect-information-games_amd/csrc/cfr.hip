@@ -14,14 +14,15 @@
 //      sum_a sigma_a v(child_a), every other node sums its children;
 //   4. at seat i's decisions R = max(0, R + v(child_a) - v), S += t x own x sigma.
 // (4 recomputes sigma of the rows it changed, which is step 1 of the next half-iteration.)
-// Sums in the evaluator's order (actions, public ranks, opponent ranks ascending), no FMA
-// contraction: tests/policy_ref.py restates it in numpy to the bit.
+// 3 and the rows of 1 are tree_walk.h's steps and 2 is its reach_step with the own reach beside
+// it, so the sums are the evaluator's (actions, public ranks, opponent ranks ascending; no FMA
+// contraction): tests/policy_ref.py restates it in numpy to the bit.
 //
 // The work per level is a few hundred items, so the workgroup is barrier-latency bound (2 nlev
 // + 1 barriers per half-iteration, 34 per Leduc iteration); it runs on the device because
 // that is where the tables and the evaluator are and the library has no host compute path,
 // not for throughput.
-#include "exploit_tree.h"
+#include "tree_walk.h"
 
 struct nfsp_cfr {
   nfsp_ctx* ctx = nullptr;
@@ -51,19 +52,8 @@ __host__ __device__ inline size_t cfr_lds(int nn, int ndec) {
 // regret matching on one row; an illegal raise has R = 0 always
 __device__ inline void match_row(const double* R, bool legal_raise, double* sg) {
 #pragma clang fp contract(off)
-  const double r0 = R[0] > 0.0 ? R[0] : 0.0, r1 = R[1] > 0.0 ? R[1] : 0.0;
-  const double r2 = legal_raise && R[2] > 0.0 ? R[2] : 0.0;
-  const double s = (r0 + r1) + r2;
-  if (s > 0.0) {
-    sg[0] = r0 / s;
-    sg[1] = r1 / s;
-    sg[2] = r2 / s;
-  } else {
-    const double u = 1.0 / (legal_raise ? 3.0 : 2.0);
-    sg[0] = u;
-    sg[1] = u;
-    sg[2] = legal_raise ? u : 0.0;
-  }
+  const double r[3] = {R[0] > 0.0 ? R[0] : 0.0, R[1] > 0.0 ? R[1] : 0.0, legal_raise && R[2] > 0.0 ? R[2] : 0.0};
+  average_row(r, legal_raise, sg);
 }
 
 __global__ void __launch_bounds__(256) k_cfr_plus(CfrArgs A) {
@@ -95,6 +85,7 @@ __global__ void __launch_bounds__(256) k_cfr_plus(CfrArgs A) {
         const int n0 = T.lev[L], cnt = (T.lev[L + 1] - n0) * 9;
         for (int k = tid; k < cnt; k += nt) {
           const int n = n0 + k / 9, ri = (k / 3) % 3, ro = k % 3;
+          // tree_walk.h's reach_step and seat i's own reach in one chain of branches (see there)
           const DevNode& N = nodes[n];
           double c, o;
           if (N.parent < 0) {
@@ -119,19 +110,11 @@ __global__ void __launch_bounds__(256) k_cfr_plus(CfrArgs A) {
         for (int k = tid; k < cnt; k += nt) {
           const int n = n0 + k / 3, ri = k % 3;
           const DevNode& N = nodes[n];
-          double v = 0.0;
-          if (N.kind == TNode::TERMINAL) {
-            const double* rr = cf + (size_t)n * 9 + ri * 3;
-            const float* py = T.pay + (size_t)N.row * 18 + i * 9 + ri * 3;
-            for (int ro = 0; ro < 3; ++ro) v = v + rr[ro] * (double)py[ro];
-          } else if (N.kind == TNode::DECISION && N.p == i) {
-            const double* s = sg + (size_t)N.row * 9 + ri * 3;
-            for (int a = 0; a < 3; ++a)
-              if (N.child[a] >= 0) v = v + s[a] * val[(size_t)N.child[a] * 3 + ri];
-          } else {
-            for (int a = 0; a < 3; ++a)
-              if (N.child[a] >= 0) v = v + val[(size_t)N.child[a] * 3 + ri];
-          }
+          double v;
+          if (N.kind == TNode::TERMINAL) v = terminal_value(T, N, i, ri, cf + (size_t)n * 9 + ri * 3);
+          else if (N.kind == TNode::DECISION && N.p == i)
+            v = weighted_children(N, val + ri, 3, sg + (size_t)N.row * 9 + ri * 3);
+          else v = sum_children(N, val + ri, 3);
           val[(size_t)n * 3 + ri] = v;
         }
         __syncthreads();
@@ -158,28 +141,20 @@ __global__ void __launch_bounds__(256) k_cfr_plus(CfrArgs A) {
     A.R[k] = R[k];
     A.S[k] = S[k];
   }
-  for (int k = tid; k < ndec * 3; k += nt) {
-    const bool legal_raise = T.legal[k / 3] & 1;
-    const double* s = S + 3 * k;
-    const double sum = (s[0] + s[1]) + s[2];
-    const double u = 1.0 / (legal_raise ? 3.0 : 2.0);
-    A.avg[3 * k + 0] = sum > 0.0 ? s[0] / sum : u;
-    A.avg[3 * k + 1] = sum > 0.0 ? s[1] / sum : u;
-    A.avg[3 * k + 2] = !legal_raise ? 0.0 : (sum > 0.0 ? s[2] / sum : u);
-  }
+  for (int k = tid; k < ndec * 3; k += nt) average_row(S + 3 * k, T.legal[k / 3] & 1, A.avg + 3 * k);
 }
 
 }  // namespace
 
 extern "C" int nfsp_cfr_create(nfsp_ctx* ctx, nfsp_cfr** out) {
   NFSP_REQUIRE(ctx && out, "null argument");
-  const DevTables* D = nullptr;
-  const int rc = device_tables(ctx, &D);
+  const ExTables* T = nullptr;
+  const int rc = device_tables(ctx, &T);
   if (rc != NFSP_OK) return rc;
-  NFSP_REQUIRE(cfr_lds(D->T.nn, D->T.ndec) <= EX_MAX_LDS, "CFR+ tables exceed the LDS");
+  NFSP_REQUIRE(cfr_lds(T->nn, T->ndec) <= EX_MAX_LDS, "CFR+ tables exceed the LDS");
   nfsp_cfr* h = new nfsp_cfr;
   h->ctx = ctx;
-  h->ndec = D->T.ndec;
+  h->ndec = T->ndec;
   const size_t b = sizeof(double) * 9 * (size_t)h->ndec;
   hipError_t e = hipMalloc(&h->dev, 3 * b);
   if (e == hipSuccess) e = hipMemsetAsync(h->dev, 0, 3 * b, ctx->stream);
@@ -200,8 +175,8 @@ extern "C" int nfsp_cfr_create(nfsp_ctx* ctx, nfsp_cfr** out) {
 extern "C" int nfsp_cfr_run(nfsp_cfr* h, int64_t iters) {
   NFSP_REQUIRE(h, "null argument");
   NFSP_REQUIRE(iters >= 0, "iters must be >= 0");
-  const DevTables* D = nullptr;
-  const int rc = device_tables(h->ctx, &D);
+  const ExTables* T = nullptr;
+  const int rc = device_tables(h->ctx, &T);
   if (rc != NFSP_OK) return rc;
   NFSP_HIP(hipFuncSetAttribute((const void*)k_cfr_plus, hipFuncAttributeMaxDynamicSharedMemorySize, EX_MAX_LDS));
   const size_t n9 = 9 * (size_t)h->ndec;
@@ -209,13 +184,13 @@ extern "C" int nfsp_cfr_run(nfsp_cfr* h, int64_t iters) {
   do {
     const int m = (int)(left < NFSP_CFR_LAUNCH_ITERS ? left : NFSP_CFR_LAUNCH_ITERS);
     CfrArgs A{};
-    A.T = D->T;
+    A.T = *T;
     A.R = h->dev;
     A.S = h->dev + n9;
     A.avg = h->dev + 2 * n9;
     A.t0 = h->iterations;
     A.iters = m;
-    k_cfr_plus<<<1, 256, cfr_lds(D->T.nn, D->T.ndec), h->ctx->stream>>>(A);
+    k_cfr_plus<<<1, 256, cfr_lds(T->nn, T->ndec), h->ctx->stream>>>(A);
     NFSP_LAUNCHED("k_cfr_plus");
     h->iterations += m;
     left -= m;

@@ -1,18 +1,33 @@
-// Exact scores of any pair of policies on the evaluator's public tree (exploit_tree.h): the
-// walk of exploit.hip (k_exploit_walk: policies, reach top-down, values bottom-up; f64, no
-// FMA contraction, sums in the order of the recursive definition) with the policy phase
-// generalised from "the seat's AR net" to a policy spec per seat:
-//   * the AR net as a softmax or as the executed argmax (k_exploit_walk's modes 0 / 1);
-//   * the BR net's greedy action, ReLU or linear Q head: what k_rollout executes when the
-//     epsilon draw does not fire (rollout.hip; agent/agent.py:124-128), the learned best
-//     response of the evaluator the reference left commented out (main.py:82-120);
-//   * a table [ndec][3 ranks][3 actions] of doubles, for whatever is not a net.
-// and two more outputs, seat 0's value per dealer.  k_policy_table writes the policy phase's
-// result out as such a table; k_best_response keeps the argmax the best-response evaluations
-// take a max over, as a joint one-hot table with the action values beside it.  Oracle:
-// oracle/exploit_oracle.py with a TabularPolicy.
-#include "exploit_tree.h"
+// Exact scores of a pair of policies in the reference's Leduc variant (or the Kuhn swap-in,
+// NFSP_GAME_KUHN), played the way main.train plays it (main.py:21-67: dealer alternating per
+// hand, the dealer acting first in both rounds, the D / L / D scheduler) with the env's rules
+// (leduc/newenv.py, nfsp_device.h hand_step).  SURVEY.md §8(f)1: the true curve beside the
+// reference's proxy (agent/agent.py:235-238 summed at main.py:73) and the MC evaluator the
+// reference left commented out (main.py:82-120: a BR player against the AR player).
+//
+// One workgroup per pair walks the evaluator's public tree (exploit_tree.h) on the GPU:
+//   1. the policies: each seat's policy spec on every decision row, for each of its ranks --
+//        * the AR net (LDS) as a mixed strategy (the softmax, NFSP's average strategy; an illegal
+//          raise's mass goes to call, the env's remap) or as the env executes it (argmax, first
+//          max wins, leduc/newenv.py:135-145): nfsp_exploitability's modes 0 / 1;
+//        * the BR net's greedy action, ReLU or linear Q head: what k_rollout executes when the
+//          epsilon draw does not fire (rollout.hip; agent/agent.py:124-128), the learned best
+//          response of the evaluator the reference left commented out;
+//        * a table [ndec][3 ranks][3 actions] of doubles, for whatever is not a net;
+//   2. reach, top-down one depth level at a time: for each evaluation (seat 0's best response,
+//      seat 1's, seat 0's on-policy value) and (own rank, opponent rank), chance x opponent
+//      reach (x own reach on-policy);
+//   3. values, bottom-up: the best-responding seat takes the max over its actions per own rank.
+// 2 and 3 are tree_walk.h's steps: f64, no FMA contraction, sums in the order of the recursive
+// definition.  Values are in the env's reward units (chips); exploitability = BR_0 + BR_1 (the
+// sum, as main.py:73 sums the two proxies).  k_policy_table writes the policy phase's result out
+// as a table; k_best_response keeps the argmax the best-response evaluations take a max over, as
+// a joint one-hot table with the action values beside it.  Oracle: oracle/exploit_oracle.py
+// (independent brute force over full histories with the reference-restated Env).
+#include <vector>
+
 #include "nn_device.h"
+#include "tree_walk.h"
 
 namespace {
 
@@ -22,7 +37,8 @@ constexpr int EV_PAIRS = 64;   // pairs per launch: 64 x 2 specs x 16 B + the ta
 struct EvArgs {
   ExTables T;
   nfsp_policy pol[EV_PAIRS][2];  // seat 0 / seat 1, per pair
-  double* out;                   // [pairs][6]
+  double* out;                   // [pairs][ncols]
+  int ncols;                     // 6, or 4: without seat 0's value per dealer
 };
 struct PtArgs {
   ExTables T;
@@ -94,17 +110,26 @@ __device__ inline void policy_row(int kind, const float* net, const double* tab,
   }
 }
 
-__global__ void __launch_bounds__(256) k_evaluate(EvArgs A) {
+struct BrOut {
+  double* beta;                  // [ndec][3][3]
+  double* q;                     // [ndec][3][3] or null
+  double* rch;                   // [ndec][3] or null
+};
+
+// The three phases for the first NE evaluations, side by side: e = 0 seat 0 best-responds, 1 seat
+// 1 best-responds, 2 seat 0 on-policy; ri is the rank of seat i = (e == 1).  LDS as ev_lds (NE 3)
+// / br_lds (NE 2) size it.  With KEEP_ARGMAX a best responder's decision writes its row of O.
+// Returns the values [nn][NE][ri].  Every thread calls it, with the same arguments: 2 nlev + 2
+// barriers.
+template <int NE, bool KEEP_ARGMAX>
+__device__ inline const double* walk(char* smem, const ExTables& T, nfsp_policy P0, nfsp_policy P1, const BrOut& O) {
 #pragma clang fp contract(off)
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  const ExTables& T = A.T;
-  float* sw = reinterpret_cast<float*>(smem_raw);                      // [2][NP]
-  double* pol = reinterpret_cast<double*>(smem_raw + ev_off_pol());    // [ndec][3 ranks][3]
-  double* reach = pol + (size_t)T.ndec * 9;                            // [nn][3 evals][3][3]
-  double* val = reach + (size_t)T.nn * 27;                             // [nn][3 evals][3]
+  float* sw = reinterpret_cast<float*>(smem);                          // [2][NP]
+  double* pol = reinterpret_cast<double*>(smem + ev_off_pol());        // [ndec][3 ranks][3]
+  double* reach = pol + (size_t)T.ndec * 9;                            // [nn][NE][ri][ro]
+  double* val = reach + (size_t)T.nn * 9 * NE;                         // [nn][NE][ri]
   const int tid = threadIdx.x, nt = blockDim.x;
   const int NP = nfsp::nn::NP;
-  const nfsp_policy P0 = A.pol[blockIdx.x][0], P1 = A.pol[blockIdx.x][1];
   for (int k = tid; k < 2 * NP; k += nt) {
     const nfsp_policy& P = k < NP ? P0 : P1;
     if (kind_is_net(P.kind)) sw[k] = static_cast<const float*>(P.dev)[k < NP ? k : k - NP];
@@ -117,72 +142,65 @@ __global__ void __launch_bounds__(256) k_evaluate(EvArgs A) {
     policy_row(P.kind, sw + p * NP, static_cast<const double*>(P.dev), T, k, pol + 3 * (size_t)k);
   }
   __syncthreads();
-  // 2. reach, top-down.  Evaluation e: 0 = seat 0 best-responds, 1 = seat 1 best-responds,
-  //    2 = seat 0 on-policy.  Index [node][e][ri][ro], ri = seat i's rank (i = e == 1).
+  // 2. reach, top-down
   for (int L = 0; L < T.nlev; ++L) {
-    const int n0 = T.lev[L], cnt = (T.lev[L + 1] - n0) * 27;
+    const int n0 = T.lev[L], cnt = (T.lev[L + 1] - n0) * 9 * NE;
     for (int k = tid; k < cnt; k += nt) {
-      const int n = n0 + k / 27, e = (k / 9) % 3, ri = (k / 3) % 3, ro = k % 3;
-      const DevNode& N = T.nodes[n];
-      double r;
-      if (N.parent < 0) {
-        r = T.deal[ri][ro];
-      } else {
-        const DevNode& P = T.nodes[N.parent];
-        const double r0 = reach[(size_t)N.parent * 27 + e * 9 + ri * 3 + ro];
-        const int i = e == 1 ? 1 : 0;
-        if (P.kind == TNode::CHANCE) r = r0 * p_public(N.via, ri, ro);
-        else if (P.p == i) r = e < 2 ? r0 : r0 * pol[(size_t)P.row * 9 + ri * 3 + N.via];
-        else r = r0 * pol[(size_t)P.row * 9 + ro * 3 + N.via];
-      }
-      reach[(size_t)n * 27 + e * 9 + ri * 3 + ro] = r;
+      const int n = n0 + k / (9 * NE), e = (k / 9) % NE, ri = (k / 3) % 3, ro = k % 3;
+      double* item = reach + e * 9 + ri * 3 + ro;
+      item[(size_t)n * 9 * NE] = reach_step(T, T.nodes, T.nodes[n], e == 1, ri, ro, pol, item, 9 * NE, e == 2);
     }
     __syncthreads();
   }
-  // 3. values, bottom-up: [node][e][ri]
+  // 3. values, bottom-up
   for (int L = T.nlev - 1; L >= 0; --L) {
-    const int n0 = T.lev[L], cnt = (T.lev[L + 1] - n0) * 9;
+    const int n0 = T.lev[L], cnt = (T.lev[L + 1] - n0) * 3 * NE;
     for (int k = tid; k < cnt; k += nt) {
-      const int n = n0 + k / 9, e = (k / 3) % 3, ri = k % 3;
-      const int i = e == 1 ? 1 : 0;
+      const int n = n0 + k / (3 * NE), e = (k / 3) % NE, ri = k % 3;
+      const int i = e == 1;
       const DevNode& N = T.nodes[n];
-      double v = 0.0;
+      const double* rr = reach + (size_t)n * 9 * NE + e * 9 + ri * 3;
+      double* item = val + e * 3 + ri;
+      double v;
       if (N.kind == TNode::TERMINAL) {
-        const double* rr = reach + (size_t)n * 27 + e * 9 + ri * 3;
-        const float* py = T.pay + (size_t)N.row * 18 + i * 9 + ri * 3;
-        for (int ro = 0; ro < 3; ++ro)
-          if (rr[ro] != 0.0) v += rr[ro] * (double)py[ro];
+        v = terminal_value(T, N, i, ri, rr);
       } else if (N.kind == TNode::DECISION && N.p == i && e < 2) {
-        v = -1e300;
-        for (int a = 0; a < 3; ++a) {
-          if (N.child[a] < 0) continue;
-          const double c = val[(size_t)N.child[a] * 9 + e * 3 + ri];
-          v = c > v ? c : v;
+        int best;
+        v = first_max_child(N, item, 3 * NE, best);
+        if (KEEP_ARGMAX) {
+          const size_t row = (size_t)N.row * 3 + ri;
+          for (int a = 0; a < 3; ++a) {
+            O.beta[3 * row + a] = a == best ? 1.0 : 0.0;
+            if (O.q) O.q[3 * row + a] = N.child[a] >= 0 ? item[(size_t)N.child[a] * 3 * NE] : 0.0;
+          }
+          if (O.rch) O.rch[row] = sum3(rr);
         }
       } else {
-        for (int a = 0; a < 3; ++a)
-          if (N.child[a] >= 0) v += val[(size_t)N.child[a] * 9 + e * 3 + ri];
+        v = sum_children(N, item, 3 * NE);
       }
-      val[(size_t)n * 9 + e * 3 + ri] = v;
+      item[(size_t)n * 3 * NE] = v;
     }
     __syncthreads();
   }
-  if (tid == 0) {
-    double br[2] = {0.0, 0.0}, onp = 0.0, per[2] = {0.0, 0.0};
-    for (int e = 0; e < 3; ++e)
-      for (int d = 0; d < 2; ++d) {
-        const double* v = val + (size_t)T.root[d] * 9 + e * 3;
-        const double s1 = (v[0] + v[1]) + v[2];    // the value given the dealer
-        const double s = 0.5 * s1;
-        if (e < 2) br[e] += s; else { onp += s; per[d] = s1; }
-      }
-    double* o = A.out + 6 * (size_t)blockIdx.x;
-    o[0] = br[0];
-    o[1] = br[1];
-    o[2] = br[0] + br[1];
-    o[3] = onp;
-    o[4] = per[0];
-    o[5] = per[1];
+  return val;
+}
+
+__global__ void __launch_bounds__(256) k_evaluate(EvArgs A) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const ExTables& T = A.T;
+  const double* val = walk<3, false>(smem_raw, T, A.pol[blockIdx.x][0], A.pol[blockIdx.x][1], BrOut{});
+  if (threadIdx.x == 0) {
+    double* o = A.out + (size_t)A.ncols * blockIdx.x;
+    const double br0 = root_value(T, val, 9), br1 = root_value(T, val + 3, 9);
+    o[0] = br0;
+    o[1] = br1;
+    o[2] = br0 + br1;
+    o[3] = root_value(T, val + 6, 9);
+    if (A.ncols == 6) {                            // seat 0's on-policy value given the dealer
+      o[4] = sum3(val + (size_t)T.root[0] * 9 + 6);
+      o[5] = sum3(val + (size_t)T.root[1] * 9 + 6);
+    }
   }
 }
 
@@ -203,112 +221,66 @@ __global__ void __launch_bounds__(256) k_policy_table(PtArgs A) {
   }
 }
 
-// The exact best responses as a strategy: k_evaluate's phases for evaluations e = 0 and 1 (the
-// same sums in the same order), with the argmax its max discards.  Seat e's rows of the joint
-// table hold its best response against the other seat's policy; q is the child values the max
-// runs over, rch the counterfactual reach of the information set summed over the opponent's
-// rank.  The first maximum among the legal children wins, so a tie and every information set
-// the opponent never reaches fold.  One workgroup; 2 nlev + 2 barriers.
+// The exact best responses as a strategy: k_evaluate's walk for evaluations e = 0 and 1, with the
+// argmax its max discards.  Seat e's rows of the joint table hold its best response against the
+// other seat's policy; q is the child values the max runs over, rch the counterfactual reach of
+// the information set summed over the opponent's rank.  The first maximum among the legal
+// children wins, so a tie and every information set the opponent never reaches fold.  One
+// workgroup.
 struct BrArgs {
   ExTables T;
   nfsp_policy pol[2];
-  double* beta;                  // [ndec][3][3]
-  double* q;                     // [ndec][3][3] or null
-  double* rch;                   // [ndec][3] or null
+  BrOut out;
 };
 __host__ __device__ inline size_t br_lds(int nn, int ndec) {
   return ev_off_pol() + 8 * ((size_t)ndec * 9 + (size_t)nn * 18 + (size_t)nn * 6);
 }
 
 __global__ void __launch_bounds__(256) k_best_response(BrArgs A) {
-#pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  const ExTables& T = A.T;
-  float* sw = reinterpret_cast<float*>(smem_raw);                      // [2][NP]
-  double* pol = reinterpret_cast<double*>(smem_raw + ev_off_pol());    // [ndec][3 ranks][3]
-  double* reach = pol + (size_t)T.ndec * 9;                            // [nn][2 evals][3][3]
-  double* val = reach + (size_t)T.nn * 18;                             // [nn][2 evals][3]
-  const int tid = threadIdx.x, nt = blockDim.x;
-  const int NP = nfsp::nn::NP;
-  const nfsp_policy P0 = A.pol[0], P1 = A.pol[1];
-  for (int k = tid; k < 2 * NP; k += nt) {
-    const nfsp_policy& P = k < NP ? P0 : P1;
-    if (kind_is_net(P.kind)) sw[k] = static_cast<const float*>(P.dev)[k < NP ? k : k - NP];
-  }
-  __syncthreads();
-  for (int k = tid; k < T.ndec * 3; k += nt) {
-    const int p = T.legal[k / 3] >> 1;
-    const nfsp_policy& P = p ? P1 : P0;
-    policy_row(P.kind, sw + p * NP, static_cast<const double*>(P.dev), T, k, pol + 3 * (size_t)k);
-  }
-  __syncthreads();
-  // reach of seat e's ranks ri against the opponent's ro, without seat e's own actions
-  for (int L = 0; L < T.nlev; ++L) {
-    const int n0 = T.lev[L], cnt = (T.lev[L + 1] - n0) * 18;
-    for (int k = tid; k < cnt; k += nt) {
-      const int n = n0 + k / 18, e = (k / 9) % 2, ri = (k / 3) % 3, ro = k % 3;
-      const DevNode& N = T.nodes[n];
-      double r;
-      if (N.parent < 0) {
-        r = T.deal[ri][ro];
-      } else {
-        const DevNode& P = T.nodes[N.parent];
-        const double r0 = reach[(size_t)N.parent * 18 + e * 9 + ri * 3 + ro];
-        if (P.kind == TNode::CHANCE) r = r0 * p_public(N.via, ri, ro);
-        else if (P.p == e) r = r0;
-        else r = r0 * pol[(size_t)P.row * 9 + ro * 3 + N.via];
-      }
-      reach[(size_t)n * 18 + e * 9 + ri * 3 + ro] = r;
-    }
-    __syncthreads();
-  }
-  // values bottom-up; a decision of seat e writes its row of the outputs
-  for (int L = T.nlev - 1; L >= 0; --L) {
-    const int n0 = T.lev[L], cnt = (T.lev[L + 1] - n0) * 6;
-    for (int k = tid; k < cnt; k += nt) {
-      const int n = n0 + k / 6, e = (k / 3) % 2, ri = k % 3;
-      const DevNode& N = T.nodes[n];
-      double v = 0.0;
-      if (N.kind == TNode::TERMINAL) {
-        const double* rr = reach + (size_t)n * 18 + e * 9 + ri * 3;
-        const float* py = T.pay + (size_t)N.row * 18 + e * 9 + ri * 3;
-        for (int ro = 0; ro < 3; ++ro)
-          if (rr[ro] != 0.0) v += rr[ro] * (double)py[ro];
-      } else if (N.kind == TNode::DECISION && N.p == e) {
-        int best = -1;
-        double c3[3] = {0.0, 0.0, 0.0};
-        for (int a = 0; a < 3; ++a) {
-          if (N.child[a] < 0) continue;
-          const double c = val[(size_t)N.child[a] * 6 + e * 3 + ri];
-          c3[a] = c;
-          if (best < 0 || c > v) {
-            v = c;
-            best = a;
-          }
-        }
-        const size_t row = (size_t)N.row * 3 + ri;
-        for (int a = 0; a < 3; ++a) {
-          A.beta[3 * row + a] = a == best ? 1.0 : 0.0;
-          if (A.q) A.q[3 * row + a] = c3[a];
-        }
-        if (A.rch) {
-          const double* rr = reach + (size_t)n * 18 + e * 9 + ri * 3;
-          A.rch[row] = (rr[0] + rr[1]) + rr[2];
-        }
-      } else {
-        for (int a = 0; a < 3; ++a)
-          if (N.child[a] >= 0) v += val[(size_t)N.child[a] * 6 + e * 3 + ri];
-      }
-      val[(size_t)n * 6 + e * 3 + ri] = v;
-    }
-    __syncthreads();
-  }
+  walk<2, true>(smem_raw, A.T, A.pol[0], A.pol[1], A.out);
 }
 
 int check_policy(const nfsp_policy& p) {
   NFSP_REQUIRE(p.kind >= NFSP_POL_AR_SOFTMAX && p.kind <= NFSP_POL_TABLE, "unknown policy kind (NFSP_POL_*)");
   NFSP_REQUIRE(p.reserved == 0, "nfsp_policy.reserved must be 0");
   NFSP_REQUIRE(p.dev, "null policy pointer");
+  return NFSP_OK;
+}
+
+// The launch path of both batch entry points: n checked pairs through k_evaluate, EV_PAIRS per
+// launch, the first ncols of each pair's six results to host_out[n][ncols].
+int evaluate_pairs(nfsp_ctx* ctx, const nfsp_policy* seat0, const nfsp_policy* seat1, int n, double* host_out,
+                   int ncols) {
+  if (n == 0) return NFSP_OK;
+  const ExTables* T = nullptr;
+  const int rc = device_tables(ctx, &T);
+  if (rc != NFSP_OK) return rc;
+  const size_t lds = ev_lds(T->nn, T->ndec);
+  NFSP_REQUIRE(lds <= EX_MAX_LDS, "evaluation tables exceed the LDS");
+  NFSP_HIP(hipFuncSetAttribute((const void*)k_evaluate, hipFuncAttributeMaxDynamicSharedMemorySize, EX_MAX_LDS));
+  struct DevBuf {                               // freed on every exit path
+    void* p = nullptr;
+    hipStream_t s;
+    explicit DevBuf(hipStream_t s_) : s(s_) {}
+    ~DevBuf() { if (p) (void)hipFreeAsync(p, s); }
+  } bo(ctx->stream);
+  NFSP_HIP(hipMallocAsync(&bo.p, sizeof(double) * ncols * n, ctx->stream));
+  for (int k0 = 0; k0 < n; k0 += EV_PAIRS) {
+    const int m = n - k0 < EV_PAIRS ? n - k0 : EV_PAIRS;
+    EvArgs A{};
+    A.T = *T;
+    for (int k = 0; k < m; ++k) {
+      A.pol[k][0] = seat0[k0 + k];
+      A.pol[k][1] = seat1[k0 + k];
+    }
+    A.out = static_cast<double*>(bo.p) + ncols * (size_t)k0;
+    A.ncols = ncols;
+    k_evaluate<<<m, 256, lds, ctx->stream>>>(A);
+    NFSP_LAUNCHED("k_evaluate");
+  }
+  NFSP_HIP(hipMemcpyAsync(host_out, bo.p, sizeof(double) * ncols * n, hipMemcpyDeviceToHost, ctx->stream));
+  NFSP_HIP(hipStreamSynchronize(ctx->stream));
   return NFSP_OK;
 }
 
@@ -323,35 +295,29 @@ extern "C" int nfsp_evaluate_batch(nfsp_ctx* ctx, const nfsp_policy* seat0, cons
     if (rc == NFSP_OK) rc = check_policy(seat1[k]);
     if (rc != NFSP_OK) return rc;
   }
-  if (n == 0) return NFSP_OK;
-  const DevTables* D = nullptr;
-  const int rc = device_tables(ctx, &D);
-  if (rc != NFSP_OK) return rc;
-  const size_t lds = ev_lds(D->T.nn, D->T.ndec);
-  NFSP_REQUIRE(lds <= EX_MAX_LDS, "evaluation tables exceed the LDS");
-  NFSP_HIP(hipFuncSetAttribute((const void*)k_evaluate, hipFuncAttributeMaxDynamicSharedMemorySize, EX_MAX_LDS));
-  struct DevBuf {                               // freed on every exit path
-    void* p = nullptr;
-    hipStream_t s;
-    explicit DevBuf(hipStream_t s_) : s(s_) {}
-    ~DevBuf() { if (p) (void)hipFreeAsync(p, s); }
-  } bo(ctx->stream);
-  NFSP_HIP(hipMallocAsync(&bo.p, sizeof(double) * 6 * n, ctx->stream));
-  for (int k0 = 0; k0 < n; k0 += EV_PAIRS) {
-    const int m = n - k0 < EV_PAIRS ? n - k0 : EV_PAIRS;
-    EvArgs A{};
-    A.T = D->T;
-    for (int k = 0; k < m; ++k) {
-      A.pol[k][0] = seat0[k0 + k];
-      A.pol[k][1] = seat1[k0 + k];
-    }
-    A.out = static_cast<double*>(bo.p) + 6 * (size_t)k0;
-    k_evaluate<<<m, 256, lds, ctx->stream>>>(A);
-    NFSP_LAUNCHED("k_evaluate");
+  return evaluate_pairs(ctx, seat0, seat1, n, out, 6);
+}
+
+// Two AR nets per pair, both read the way `mode` says: the first four of nfsp_evaluate_batch's six.
+extern "C" int nfsp_exploitability_batch(nfsp_ctx* ctx, const float* const* dev_w_ar0,
+                                         const float* const* dev_w_ar1, int n, int mode, double* out) {
+  NFSP_REQUIRE(ctx && dev_w_ar0 && dev_w_ar1 && out, "null argument");
+  NFSP_REQUIRE(n >= 0, "n must be >= 0");
+  NFSP_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (softmax mixed) or 1 (argmax as executed)");
+  for (int k = 0; k < n; ++k) NFSP_REQUIRE(dev_w_ar0[k] && dev_w_ar1[k], "null weight pointer");
+  const int kind = mode ? NFSP_POL_AR_ARGMAX : NFSP_POL_AR_SOFTMAX;
+  std::vector<nfsp_policy> seat0(n), seat1(n);
+  for (int k = 0; k < n; ++k) {
+    seat0[k] = nfsp_policy{kind, 0, dev_w_ar0[k]};
+    seat1[k] = nfsp_policy{kind, 0, dev_w_ar1[k]};
   }
-  NFSP_HIP(hipMemcpyAsync(out, bo.p, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, ctx->stream));
-  NFSP_HIP(hipStreamSynchronize(ctx->stream));
-  return NFSP_OK;
+  return evaluate_pairs(ctx, seat0.data(), seat1.data(), n, out, 4);
+}
+
+extern "C" int nfsp_exploitability(nfsp_ctx* ctx, const float* dev_w_ar0, const float* dev_w_ar1, int mode,
+                                   double* out) {
+  NFSP_REQUIRE(ctx && dev_w_ar0 && dev_w_ar1 && out, "null argument");
+  return nfsp_exploitability_batch(ctx, &dev_w_ar0, &dev_w_ar1, 1, mode, out);
 }
 
 extern "C" int nfsp_best_response_table(nfsp_ctx* ctx, const nfsp_policy* seat0, const nfsp_policy* seat1,
@@ -360,10 +326,10 @@ extern "C" int nfsp_best_response_table(nfsp_ctx* ctx, const nfsp_policy* seat0,
   int rc = check_policy(*seat0);
   if (rc == NFSP_OK) rc = check_policy(*seat1);
   if (rc != NFSP_OK) return rc;
-  const DevTables* D = nullptr;
-  rc = device_tables(ctx, &D);
+  const ExTables* T = nullptr;
+  rc = device_tables(ctx, &T);
   if (rc != NFSP_OK) return rc;
-  const size_t n9 = sizeof(double) * 9 * (size_t)D->T.ndec;
+  const size_t n9 = sizeof(double) * 9 * (size_t)T->ndec;
   const char* outs[3] = {reinterpret_cast<const char*>(dev_beta), reinterpret_cast<const char*>(dev_q),
                          reinterpret_cast<const char*>(dev_reach)};
   const size_t outb[3] = {n9, n9, n9 / 3};
@@ -378,16 +344,14 @@ extern "C" int nfsp_best_response_table(nfsp_ctx* ctx, const nfsp_policy* seat0,
     for (int j = k + 1; j < 3; ++j)
       NFSP_REQUIRE(!outs[k] || !outs[j] || outs[k] + outb[k] <= outs[j] || outs[j] + outb[j] <= outs[k],
                    "nfsp_best_response_table: two outputs alias each other");
-  const size_t lds = br_lds(D->T.nn, D->T.ndec);
+  const size_t lds = br_lds(T->nn, T->ndec);
   NFSP_REQUIRE(lds <= EX_MAX_LDS, "best-response tables exceed the LDS");
   NFSP_HIP(hipFuncSetAttribute((const void*)k_best_response, hipFuncAttributeMaxDynamicSharedMemorySize, EX_MAX_LDS));
   BrArgs A{};
-  A.T = D->T;
+  A.T = *T;
   A.pol[0] = *seat0;
   A.pol[1] = *seat1;
-  A.beta = dev_beta;
-  A.q = dev_q;
-  A.rch = dev_reach;
+  A.out = BrOut{dev_beta, dev_q, dev_reach};
   k_best_response<<<1, 256, lds, ctx->stream>>>(A);
   NFSP_LAUNCHED("k_best_response");
   NFSP_HIP(hipStreamSynchronize(ctx->stream));
@@ -399,11 +363,11 @@ extern "C" int nfsp_policy_table(nfsp_ctx* ctx, const nfsp_policy* policy, doubl
   int rc = check_policy(*policy);
   if (rc != NFSP_OK) return rc;
   NFSP_REQUIRE(policy->dev != dev_out, "nfsp_policy_table in place");
-  const DevTables* D = nullptr;
-  rc = device_tables(ctx, &D);
+  const ExTables* T = nullptr;
+  rc = device_tables(ctx, &T);
   if (rc != NFSP_OK) return rc;
   PtArgs A{};
-  A.T = D->T;
+  A.T = *T;
   A.pol = *policy;
   A.out = dev_out;
   k_policy_table<<<1, 256, sizeof(float) * nfsp::nn::NP, ctx->stream>>>(A);

@@ -29,12 +29,13 @@
 // more sweep that only does 4 and 5.  So an iteration is 2 nlev barriers (Leduc, nlev = 8: 16)
 // and a launch nlev + 2 more.  W is the same sum in every thread's registers; thread 0 writes
 // the gap after the bottom-up sweep, inside the iteration.
-// Sums in the evaluator's order, no FMA contraction: tests/xfp_ref.py restates it in numpy, and
-// S, B, W and the argmax path agree to the bit.
+// The reach, value and first-max steps are tree_walk.h's, so the sums are the evaluator's (no
+// FMA contraction): tests/xfp_ref.py restates it in numpy, and S, B, W and the argmax path agree
+// to the bit.
 //
 // LDS (f64): S, B, sigma [ndec][3][3], cf [nn][2][3][3], values and x [nn][2][3], then the node
 // table and beta_t [ndec][3] as bytes -- Leduc (nn 364, ndec 130): 124,566 bytes.
-#include "exploit_tree.h"
+#include "tree_walk.h"
 
 struct nfsp_xfp {
   nfsp_ctx* ctx = nullptr;
@@ -67,30 +68,14 @@ __host__ __device__ inline size_t xfp_lds(int nn, int ndec) {
 __device__ inline void sigma_row(const double* S, const double* B, double W, double eta, bool legal_raise,
                                  double* sg) {
 #pragma clang fp contract(off)
-  double p0 = 0.0, p1 = 0.0, p2 = 0.0;
-  if (W != 0.0) {
-    if (eta == 0.0) {
-      p0 = S[0];
-      p1 = S[1];
-      p2 = S[2];
-    } else {
-      const double k = 1.0 - eta;
-      p0 = k * (S[0] / W) + eta * B[0];
-      p1 = k * (S[1] / W) + eta * B[1];
-      p2 = k * (S[2] / W) + eta * B[2];
-    }
+  double p[3] = {0.0, 0.0, 0.0};
+  if (W != 0.0 && eta == 0.0) {
+    for (int a = 0; a < 3; ++a) p[a] = S[a];
+  } else if (W != 0.0) {
+    const double k = 1.0 - eta;
+    for (int a = 0; a < 3; ++a) p[a] = k * (S[a] / W) + eta * B[a];
   }
-  const double den = (p0 + p1) + p2;
-  if (den > 0.0) {
-    sg[0] = p0 / den;
-    sg[1] = p1 / den;
-    sg[2] = p2 / den;
-  } else {
-    const double u = 1.0 / (legal_raise ? 3.0 : 2.0);
-    sg[0] = u;
-    sg[1] = u;
-    sg[2] = legal_raise ? u : 0.0;
-  }
+  average_row(p, legal_raise, sg);           // S and B are 0 at an illegal raise, so p[2] is too
 }
 
 struct XfpLds {
@@ -111,29 +96,19 @@ __device__ inline void xfp_top_down(const ExTables& T, const XfpLds& M, bool upd
     for (int k = tid; k < cnt; k += nt) {
       const int n = n0 + k / 18, i = (k / 9) % 2, ri = (k / 3) % 3, ro = k % 3;
       const DevNode& N = M.nodes[n];
-      const bool root = N.parent < 0;
-      const DevNode& P = M.nodes[root ? n : N.parent];
-      if (walk) {
-        double c;
-        if (root) {
-          c = T.deal[ri][ro];
-        } else {
-          c = M.cf[(size_t)N.parent * 18 + i * 9 + ri * 3 + ro];
-          if (P.kind == TNode::CHANCE) c = c * p_public(N.via, ri, ro);
-          else if (P.p != i) c = c * M.sg[(size_t)P.row * 9 + ro * 3 + N.via];
-        }
-        M.cf[(size_t)n * 18 + i * 9 + ri * 3 + ro] = c;
+      // both read the parent's level before either writes, so that the loads overlap
+      double* item = M.cf + i * 9 + ri * 3 + ro;
+      double c = 0.0, xo = 1.0;
+      if (walk) c = reach_step(T, M.nodes, N, i, ri, ro, M.sg, item, 18, false);
+      if (update && N.parent >= 0) {
+        const DevNode& P = M.nodes[N.parent];
+        xo = M.x[(size_t)N.parent * 6 + i * 3 + ri];
+        if (P.kind == TNode::DECISION && P.p == i) xo = xo * (M.beta[P.row * 3 + ri] == N.via ? 1.0 : 0.0);
       }
+      if (walk) item[(size_t)n * 18] = c;
       if (ro != 0) continue;
       // (node, seat i, its rank ri): the own reach, and at seat i's decision the row
-      double xo = 1.0;
-      if (update) {
-        if (!root) {
-          xo = M.x[(size_t)N.parent * 6 + i * 3 + ri];
-          if (P.kind == TNode::DECISION && P.p == i) xo = xo * (M.beta[P.row * 3 + ri] == N.via ? 1.0 : 0.0);
-        }
-        M.x[(size_t)n * 6 + i * 3 + ri] = xo;
-      }
+      if (update) M.x[(size_t)n * 6 + i * 3 + ri] = xo;
       if (N.kind != TNode::DECISION || N.p != i) continue;
       const size_t row = (size_t)N.row * 9 + ri * 3;
       if (update) {
@@ -186,40 +161,23 @@ __global__ void __launch_bounds__(256) k_xfp(XfpArgs A) {
       for (int k = tid; k < cnt; k += nt) {
         const int n = n0 + k / 6, i = (k / 3) % 2, ri = k % 3;
         const DevNode& N = M.nodes[n];
-        double v = 0.0;
+        double* item = M.val + i * 3 + ri;
+        double v;
         if (N.kind == TNode::TERMINAL) {
-          const double* rr = M.cf + (size_t)n * 18 + i * 9 + ri * 3;
-          const float* py = T.pay + (size_t)N.row * 18 + i * 9 + ri * 3;
-          for (int ro = 0; ro < 3; ++ro) v = v + rr[ro] * (double)py[ro];
+          v = terminal_value(T, N, i, ri, M.cf + (size_t)n * 18 + i * 9 + ri * 3);
         } else if (N.kind == TNode::DECISION && N.p == i) {
-          int best = -1;
-          for (int a = 0; a < 3; ++a) {
-            if (N.child[a] < 0) continue;
-            const double c = M.val[(size_t)N.child[a] * 6 + i * 3 + ri];
-            if (best < 0 || c > v) {
-              v = c;
-              best = a;
-            }
-          }
+          int best;
+          v = first_max_child(N, item, 6, best);
           M.beta[N.row * 3 + ri] = (uint8_t)best;
         } else {
-          for (int a = 0; a < 3; ++a)
-            if (N.child[a] >= 0) v = v + M.val[(size_t)N.child[a] * 6 + i * 3 + ri];
+          v = sum_children(N, item, 6);
         }
-        M.val[(size_t)n * 6 + i * 3 + ri] = v;
+        item[(size_t)n * 6] = v;
       }
       __syncthreads();
     }
     // 3. the roots' values stand until the next bottom-up sweep ends
-    if (tid == 0) {
-      double br[2];
-      for (int i = 0; i < 2; ++i) {
-        const double* v0 = M.val + (size_t)T.root[0] * 6 + i * 3;
-        const double* v1 = M.val + (size_t)T.root[1] * 6 + i * 3;
-        br[i] = 0.5 * ((v0[0] + v0[1]) + v0[2]) + 0.5 * ((v1[0] + v1[1]) + v1[2]);
-      }
-      A.gaps[(size_t)run * A.iters + it] = br[0] + br[1];
-    }
+    if (tid == 0) A.gaps[(size_t)run * A.iters + it] = root_value(T, M.val, 6) + root_value(T, M.val + 3, 6);
     w = linear ? (double)(A.t0 + 1 + it) : 1.0;
     W = W + w;
   }
@@ -229,16 +187,7 @@ __global__ void __launch_bounds__(256) k_xfp(XfpArgs A) {
     gS[n9 + k] = M.B[k];
   }
   if (tid == 0) A.W[run] = W;
-  for (int k = tid; k < ndec * 3; k += nt) {
-    const bool legal_raise = T.legal[k / 3] & 1;
-    const double* s = M.S + 3 * k;
-    const double sum = (s[0] + s[1]) + s[2];
-    const double u = 1.0 / (legal_raise ? 3.0 : 2.0);
-    double* avg = gS + 2 * n9 + 3 * (size_t)k;
-    avg[0] = sum > 0.0 ? s[0] / sum : u;
-    avg[1] = sum > 0.0 ? s[1] / sum : u;
-    avg[2] = !legal_raise ? 0.0 : (sum > 0.0 ? s[2] / sum : u);
-  }
+  for (int k = tid; k < ndec * 3; k += nt) average_row(M.S + 3 * k, T.legal[k / 3] & 1, gS + 2 * n9 + 3 * (size_t)k);
 }
 
 int check_cfg(const nfsp_xfp_cfg& c) {
@@ -260,13 +209,13 @@ extern "C" int nfsp_xfp_create(nfsp_ctx* ctx, const nfsp_xfp_cfg* cfgs, int n, n
     if (rc != NFSP_OK) return rc;
   }
   NFSP_REQUIRE(ctx, "null argument");
-  const DevTables* D = nullptr;
-  const int rc = device_tables(ctx, &D);
+  const ExTables* T = nullptr;
+  const int rc = device_tables(ctx, &T);
   if (rc != NFSP_OK) return rc;
-  NFSP_REQUIRE(xfp_lds(D->T.nn, D->T.ndec) <= EX_MAX_LDS, "XFP tables exceed the LDS");
+  NFSP_REQUIRE(xfp_lds(T->nn, T->ndec) <= EX_MAX_LDS, "XFP tables exceed the LDS");
   nfsp_xfp* h = new nfsp_xfp;
   h->ctx = ctx;
-  h->ndec = D->T.ndec;
+  h->ndec = T->ndec;
   h->n = n;
   const size_t doubles = (size_t)n * (27 * (size_t)h->ndec + 1 + NFSP_XFP_LAUNCH_ITERS);
   hipError_t e = hipMalloc(&h->dev, sizeof(double) * doubles);
@@ -291,8 +240,8 @@ extern "C" int nfsp_xfp_create(nfsp_ctx* ctx, const nfsp_xfp_cfg* cfgs, int n, n
 extern "C" int nfsp_xfp_run(nfsp_xfp* h, int64_t iters, double* host_gaps) {
   NFSP_REQUIRE(iters >= 0, "iters must be >= 0");
   NFSP_REQUIRE(h, "null argument");
-  const DevTables* D = nullptr;
-  const int rc = device_tables(h->ctx, &D);
+  const ExTables* T = nullptr;
+  const int rc = device_tables(h->ctx, &T);
   if (rc != NFSP_OK) return rc;
   NFSP_HIP(hipFuncSetAttribute((const void*)k_xfp, hipFuncAttributeMaxDynamicSharedMemorySize, EX_MAX_LDS));
   const size_t n27 = 27 * (size_t)h->ndec;
@@ -300,14 +249,14 @@ extern "C" int nfsp_xfp_run(nfsp_xfp* h, int64_t iters, double* host_gaps) {
   do {
     const int m = (int)(left < NFSP_XFP_LAUNCH_ITERS ? left : NFSP_XFP_LAUNCH_ITERS);
     XfpArgs A{};
-    A.T = D->T;
+    A.T = *T;
     A.cfg = h->dev_cfg;
     A.state = h->dev;
     A.W = h->dev + (size_t)h->n * n27;
     A.gaps = A.W + h->n;                         // [n][m] in this launch
     A.t0 = h->iterations;
     A.iters = m;
-    k_xfp<<<h->n, 256, xfp_lds(D->T.nn, D->T.ndec), h->ctx->stream>>>(A);
+    k_xfp<<<h->n, 256, xfp_lds(T->nn, T->ndec), h->ctx->stream>>>(A);
     NFSP_LAUNCHED("k_xfp");
     if (host_gaps && m > 0)
       NFSP_HIP(hipMemcpy2DAsync(host_gaps + done, sizeof(double) * (size_t)iters, A.gaps, sizeof(double) * (size_t)m,

@@ -97,16 +97,14 @@ def oracle_table_scores(tree, table0, table1, **kw):
     return oracle_scores(tree, oracle_policy(tree, table0, 0), oracle_policy(tree, table1, 1), **kw)
 
 
-# ---- CFR+ ---------------------------------------------------------------------------------
-class CfrRef:
-    """k_cfr_plus in numpy: regret-matching+, alternating updates, average weighted by t."""
+# ---- what the solvers' restatements share (xfp_ref.py too) -----------------------------------
+class NodeTable:
+    """The node table unpacked once (plain ints index faster than numpy scalars)."""
 
     def __init__(self, tree):
-        self.tree = tree
-        self.R = np.zeros((tree.ndec, 3, 3))
-        self.S = np.zeros((tree.ndec, 3, 3))
-        self.t = 0
         N = tree.nodes
+        self.tree = tree
+        self.nn = tree.nn
         self.par = N["parent"].astype(int)
         self.kind = N["kind"].astype(int)
         self.p = N["p"].astype(int)
@@ -114,6 +112,30 @@ class CfrRef:
         self.row = N["row"].astype(int)
         self.kids = [[(a, int(c)) for a, c in enumerate(N["child"][n]) if c >= 0] for n in range(tree.nn)]
         self.pay = tree.pay.astype(np.float64)
+        self.root = [int(r) for r in tree.root]
+
+
+def average_rows(tree, S):
+    """The strategy sums S [ndec, 3, 3] normalised per row; uniform over the legal actions where
+    a row's sum is 0: the tail of k_cfr_plus and k_xfp."""
+    s = (S[..., 0] + S[..., 1]) + S[..., 2]
+    legal = tree.legal[:, None] & np.ones(3, bool)[None, :]
+    u = np.where(legal, 1.0 / 3.0, 1.0 / 2.0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        avg = np.where((s > 0.0)[..., None], S / s[..., None], u[..., None])
+    avg[..., 2] = np.where(legal, avg[..., 2], 0.0)
+    return avg
+
+
+# ---- CFR+ ---------------------------------------------------------------------------------
+class CfrRef(NodeTable):
+    """k_cfr_plus in numpy: regret-matching+, alternating updates, average weighted by t."""
+
+    def __init__(self, tree):
+        super().__init__(tree)
+        self.R = np.zeros((tree.ndec, 3, 3))
+        self.S = np.zeros((tree.ndec, 3, 3))
+        self.t = 0
 
     def match(self, R, legal):
         """[.., 3] regrets -> strategies; ``legal`` [..]: whether the raise is legal."""
@@ -177,12 +199,4 @@ class CfrRef:
         return self
 
     def average(self):
-        T = self.tree
-        S = self.S
-        s = (S[..., 0] + S[..., 1]) + S[..., 2]
-        legal = T.legal[:, None] & np.ones(3, bool)[None, :]
-        u = np.where(legal, 1.0 / 3.0, 1.0 / 2.0)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            avg = np.where((s > 0.0)[..., None], S / s[..., None], u[..., None])
-        avg[..., 2] = np.where(legal, avg[..., 2], 0.0)
-        return avg
+        return average_rows(self.tree, self.S)

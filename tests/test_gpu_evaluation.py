@@ -1,5 +1,6 @@
 """nfsp_evaluate_batch / nfsp_policy_table / nfsp_cfr_* on the GPU (csrc/evaluate.hip,
-csrc/cfr.hip) against nfsp_exploitability (bit for bit where they overlap), the brute-force
+csrc/cfr.hip) against nfsp_exploitability (the same kernel behind a wrapper that maps modes to
+kinds and drops two columns: bit for bit where they overlap), the brute-force
 oracle (oracle/exploit_oracle.py, 1e-5 chips as tests/test_exploit.py: net outputs agree to
 ~1e-7 and payoffs are <= 6.5 chips; 1e-9 where both sides read the same f64 table) and the numpy
 restatements of the kernels (tests/policy_ref.py)."""

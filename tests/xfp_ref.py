@@ -11,23 +11,6 @@ DECISION, CHANCE, TERMINAL = pr.DECISION, pr.CHANCE, pr.TERMINAL
 WEIGHT_UNIFORM, WEIGHT_LINEAR = 0, 1
 
 
-class _Tree:
-    """The node table unpacked once (plain ints index faster than numpy scalars)."""
-
-    def __init__(self, tree):
-        N = tree.nodes
-        self.tree = tree
-        self.nn = tree.nn
-        self.par = N["parent"].astype(int)
-        self.kind = N["kind"].astype(int)
-        self.p = N["p"].astype(int)
-        self.via = N["via"].astype(int)
-        self.row = N["row"].astype(int)
-        self.kids = [[(a, int(c)) for a, c in enumerate(N["child"][n]) if c >= 0] for n in range(tree.nn)]
-        self.pay = tree.pay.astype(np.float64)
-        self.root = [int(r) for r in tree.root]
-
-
 def first_max(vals):
     """[(action, [3] values)] of the legal children in ascending action order -> (best value,
     best action) per rank: a later action wins only where it is strictly greater."""
@@ -44,7 +27,7 @@ def first_max(vals):
 def best_response(tree, table0, table1):
     """k_best_response: (beta [ndec, 3, 3] one-hot, q [ndec, 3, 3], reach [ndec, 3]).  Rows where
     seat i acts hold seat i's best response against the other seat's table."""
-    T = _Tree(tree)
+    T = pr.NodeTable(tree)
     pol = (tree.remap(table0), tree.remap(table1))
     nn = T.nn
     reach = np.zeros((nn, 2, 3, 3))       # [node][e = responding seat][ri][ro]
@@ -90,7 +73,7 @@ class XfpRef:
     """k_xfp in numpy: one run of full-width fictitious play with simultaneous updates."""
 
     def __init__(self, tree, eta=0.0, weight=WEIGHT_UNIFORM):
-        self.T = _Tree(tree)
+        self.T = pr.NodeTable(tree)
         self.tree = tree
         self.eta = float(eta)
         self.weight = int(weight)
@@ -169,11 +152,4 @@ class XfpRef:
         return self
 
     def average(self):
-        S = self.S
-        s = (S[..., 0] + S[..., 1]) + S[..., 2]
-        legal = self.tree.legal[:, None] & np.ones(3, bool)[None, :]
-        u = np.where(legal, 1.0 / 3.0, 1.0 / 2.0)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            avg = np.where((s > 0.0)[..., None], S / s[..., None], u[..., None])
-        avg[..., 2] = np.where(legal, avg[..., 2], 0.0)
-        return avg
+        return pr.average_rows(self.tree, self.S)
