@@ -2,10 +2,13 @@
 (3,408 exhaustive + 4,000 random hands, tests/golden/env_kat.npz): every hand runs
 in its own env of ONE ctx, stepped in lock-step through nfsp_env_step, and every
 get_state of both players after every step must match bit for bit."""
+import itertools
+
 import numpy as np
 import pytest
 import torch
 
+import rollout_dist_ref as rd
 from conftest import golden
 
 pytestmark = pytest.mark.gpu
@@ -74,6 +77,23 @@ def test_env_philox_deals_are_valid_and_uniform(pkg):
     for c in range(3):
         freq = np.bincount(rk[:, c], minlength=3) / n
         assert np.allclose(freq, 1 / 3, atol=0.01)
+    # the joint (P0, P1, public): one deal per env, so the 27 cells are a true multinomial with
+    # p = count / 120 of the 6-card deck's ordered triples.  25 statistics (the 24 cells of
+    # non-zero probability and Pearson's X^2): |z| <= z* with 25 erfc(z* / sqrt 2) <= 1e-6
+    want = np.zeros(27)
+    for a, b, c in itertools.permutations(range(6), 3):
+        want[(a >> 1) * 9 + (b >> 1) * 3 + (c >> 1)] += 1.0 / 120.0
+    got = np.bincount(rk[:, 0].astype(np.int64) * 9 + rk[:, 1] * 3 + rk[:, 2], minlength=27).astype(np.float64)
+    nz = want > 0
+    assert nz.sum() == 24 and got[~nz].sum() == 0
+    zs = rd.z_star(25)
+    z = (got[nz] - n * want[nz]) / np.sqrt(n * want[nz] * (1.0 - want[nz]))
+    x2 = float((((got[nz] - n * want[nz]) ** 2) / (n * want[nz])).sum())
+    dof = int(nz.sum()) - 1
+    print(f"joint deal: z* {zs:.2f} max |z| {np.abs(z).max():.2f} rms z {np.sqrt((z * z).mean()):.2f} "
+          f"X2 {x2:.1f} (dof {dof}, bound {dof + zs * np.sqrt(2 * dof):.1f})")
+    assert np.abs(z).max() <= zs
+    assert x2 <= dof + zs * np.sqrt(2.0 * dof)
     ctx2 = nat.Context(n, seed=99)
     ctx2.call("nfsp_env_reset", nat.ptr(dealer))
     hb2 = torch.empty_like(hb)
