@@ -65,30 +65,22 @@ typedef __attribute__((address_space(3))) const volatile floatx4 lds_vfloatx4;
 __device__ inline floatx4 lds4v(const void* p) { return *(lds_vfloatx4*)p; }
 
 // Packed f32 (v_pk_fma_f32 / v_pk_mul_f32: two values per instruction, each half rounded
-// exactly as the scalar instruction) where a step has pairs of independent scalar operations
-// (round 4, tools/ar_var.sh; weight hashes after 400 updates identical to the scalar chain):
-//   PK_W   the W1 update (8 fma -> 4), both chains
+// exactly as the scalar instruction) where a step has pairs of independent scalar operations:
+//   PK_W   the W1 update (8 fma -> 4)
 //   PK_SM  AR softmax: y = e / S and d = y T_M - m for outputs 0 / 1
 //   PK_L2  layer 2: the two sample halves' partial outputs (24 fma -> 12)
-//   PK_O   outputs 0 / 1 of the 4-wave partial sums (8 add -> 4)
-// Kept: AR PK_W | PK_SM (AR 0.788 -> 0.761 us per SGD step in the microbenchmark); BR PK_W until
-// the X^T reads moved (NFSP_CH_BR below): with them the packed update breaks the hazard rule.
-// Not kept, because their results were not reproducible:
-//  * PK_L2 in the AR chain (whose Z1 MFMAs are scheduled freely, see the fences in the
-//    step): the weights differed on every run (4e-3 .. 9e-3 from the f32 reference chain
-//    after 200 updates); in that schedule a packed FMA overwrote the SrcC registers of a
-//    dependent MFMA 2-3 wait states after it issued;
-//  * PK_L2 / PK_O in the BR chain: bit-identical and 0.750 -> 0.712 us with a CU per chain,
-//    but with 4 chain workgroups per CU (engine groups of 200 replicas,
-//    tests/test_gpu_group.py) replicas differed from standalone engines by up to 3e-4 on
-//    some runs (tools/group_share_probe.py).  Their schedules overwrite the SrcC or result
-//    registers of in-flight MFMAs by VALU instructions 4-7 wait states after issue 16 times
-//    per step, against 4 in the scalar chain: the compiler's MFMA hazard padding is not
-//    enough there when other waves share the matrix cores.  Every kept variant was checked
-//    with that probe (R = 200, exact) as well as the GPU parity suite.
-//  * also measured: PK_O in the AR chain (0.772, slower), the BR Huber loss on pairs (0.737).
-constexpr unsigned PK_L2 = 1, PK_O = 2, PK_W = 4, PK_SM = 8;
-#ifndef NFSP_PK_AR                 // build-time override, for A/B builds (tools/build_lib_variant.py)
+// The AR chain runs PK_W | PK_SM (scalar in its LOSS build), the BR chain none: with the X^T
+// fragments live from layer 2 to dW1 its register allocator rotates W1 through the registers of
+// the dz split and the dW1 accumulators, and a packed W1 update would write MFMA registers 7-30
+// wait states after issue (the packed-f32 rule of tools/mfma_hazards.py).
+// PK_L2 must never ship.  Its schedules overwrite SrcC or result registers of in-flight MFMAs
+// a few wait states after issue; the compiler's hazard padding does not cover that when other
+// waves share the matrix cores, and results were not reproducible.  It
+// stays, with the NFSP_PK_AR / NFSP_PK_BR build-time overrides, as the negative control of the
+// hazard scanner: tests/test_mfma_hazards.py builds -DNFSP_PK_AR=13 -DNFSP_PK_BR=5 and requires
+// tools/mfma_hazards.py to flag it.
+constexpr unsigned PK_L2 = 1, PK_W = 4, PK_SM = 8;
+#ifndef NFSP_PK_AR
 #define NFSP_PK_AR (PK_W | PK_SM)
 #endif
 #ifndef NFSP_PK_BR
@@ -96,72 +88,6 @@ constexpr unsigned PK_L2 = 1, PK_O = 2, PK_W = 4, PK_SM = 8;
 #endif
 template <int RELU>
 constexpr unsigned chain_pk() { return RELU == 0 ? (NFSP_PK_AR) : (NFSP_PK_BR); }
-// NFSP_CHAIN_G0ROW: gb2[0] enters the V transpose as each lane row's 16-sample sum instead of
-// the 32-sample total (see own1_sc).  Measured in round 6 and left off: tools/r06.sh chain_ab
-// gave AR 0.760 -> 0.750 us per SGD step but BR 0.721 -> 0.727; built into the AR chain only,
-// the driver's bench read 7.02M hands/s (7.09M without) and the Leduc learner parity case with
-// the textbook extensions (quirks 120) moved to 2.1e-3 against its 1e-3 bound (a ReLU crossing
-// follows the new summation order).  Also measured and dropped: the BR loss without relu(o)
-// in e and with -1 / (3 x batch) folded into the rate, 5 instructions fewer per step but
-// 0.721 -> 0.736 (the schedule moved).
-#ifndef NFSP_CHAIN_G0ROW
-#define NFSP_CHAIN_G0ROW 0
-#endif
-// Where a step's LDS reads sit (chain3_body.inc).  One wave per SIMD issues in order and LDS
-// returns a wave's reads in order, so a read parks the serial chain when its s_waitcnt is reached
-// early, and it delays every read queued behind it.  None of these switches changes an operation
-// or its order: the microbenchmark's weight hashes (tools/bench_chain.hip, 400 updates, 1 and 2
-// blocks, both nets) are the same with every combination measured.
-//   CH_OWN  the lane's row-owned W2 / b2 values are carried in two registers instead of being
-//           read back from LDS every step (the stores stay: other rows and the epilogue read them)
-//   CH_XT2  the X^T reads (ds_read_b64_tr_b16) at the head of the layer-2 arithmetic, after the
-//           Z1^T MFMAs, instead of after the barrier (BR: ahead of the partial sums the loss
-//           waits on) / after the loss (AR: ahead of the dW1 MFMAs).  The ring slot was
-//           published by the previous step's barrier, and ~45 VALU instructions cover the reads
-//   CH_TG2  the targets' read there as well, instead of between the Z1 MFMAs before the barrier
-//   CH_TG   the targets' read at the step top with the fa reads
-//   CH_XT   the X^T reads beside the Z1 MFMAs, between the partial stores and the barrier
-//   CH_XTF  AR with CH_XT: that window fenced with sched_barrier, as the BR chain has it
-//   CH_W2   the W2 / b2 reads of layer 2 and the backward in front of the W split instead of
-//           after it (CH_W2F: pinned there by a sched_barrier)
-// Kept (us per SGD step, 2,000 updates, run-to-run spread 0.001; DESIGN Appendix A.0b has every
-// combination measured -- the parts do not add up, the compiler's schedule moves with each):
-//  * AR CH_OWN | CH_XT2: 0.757 -> 0.738;
-//  * BR CH_OWN | CH_XT2 | CH_TG with the scalar W1 update (NFSP_PK_BR 0): 0.720 -> 0.714.  With
-//    the X^T fragments live from layer 2 to dW1, the register allocator rotates W1 through the
-//    registers of the dz split and the dW1 accumulators, so the packed W1 update wrote MFMA
-//    registers 7-30 wait states after issue -- the packed-f32 rule of tools/mfma_hazards.py.
-//    (CH_OWN | CH_XT2 | CH_TG2 with PK_W measured 0.707, and is not shipped for that reason;
-//    with the dW1 MFMAs' registers held live past the update it is clean and 0.721.)
-// Per chain, as NFSP_PK_*; -DNFSP_CH_AR=<mask> / -DNFSP_CH_BR=<mask> for A/B builds.
-constexpr unsigned CH_OWN = 1, CH_XT = 2, CH_XTF = 4, CH_TG = 8, CH_W2 = 16, CH_XT2 = 32, CH_TG2 = 64,
-                   CH_W2F = 128;
-#ifndef NFSP_CH_AR
-#define NFSP_CH_AR (CH_OWN | CH_XT2)
-#endif
-#ifndef NFSP_CH_BR
-#define NFSP_CH_BR (CH_OWN | CH_XT2 | CH_TG)
-#endif
-template <int RELU>
-constexpr unsigned chain_ch() { return RELU == 0 ? (NFSP_CH_AR) : (NFSP_CH_BR); }
-
-__device__ inline float dpp_f(float x, int ctrl) {
-  switch (ctrl) {   // the control word must be an immediate
-    case 0x128: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xF, 0xF, false));
-    case 0xB1: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, false));
-    case 0x4E: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xF, 0xF, false));
-    default: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x141, 0xF, 0xF, false));
-  }
-}
-
-__device__ inline float dpp_any(float x, int ctrl) {
-  switch (ctrl) {
-    case 0x121: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x121, 0xF, 0xF, false));
-    case 0x122: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x122, 0xF, 0xF, false));
-    case 0x124: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x124, 0xF, 0xF, false));
-    default: return dpp_f(x, ctrl);
-  }
-}
 
 // x + partner(lane ^ 32) in every lane
 __device__ inline float sum_x32(float x) {
@@ -175,11 +101,11 @@ __device__ inline float sum_x16(float x) {
 }
 
 // Sums over the 32 samples held by the loss lanes (k_chain3's `ls` layout: every sample in 2
-// lanes), in every lane, added in exactly the round-3 chain's order (it held sample c in lane
-// c of rows 0 / 1 and 16 + c in rows 2 / 3, summed each row by DPP row_ror 8, 4, 2, 1, then
-// the two halves): pairs s, s ^ 8 (rows g, g ^ 2), s ^ 4 (lanes c, c ^ 8), s ^ 2, s ^ 1 (quad
-// permutes), then samples 0-15 + 16-31 (lanes c, c ^ 4).  a + b == b + a bit for bit, so
-// every level is the round-3 level, and the 32-sample totals are bit-identical to it.
+// lanes), in every lane, in a fixed order: pairs s, s ^ 8 (rows g, g ^ 2), s ^ 4 (lanes c,
+// c ^ 8), s ^ 2, s ^ 1 (quad permutes), then samples 0-15 + 16-31 (lanes c, c ^ 4).  This is
+// the order of a layout with sample c in lane c of rows 0 / 1 and 16 + c in rows 2 / 3, each
+// row summed by DPP row_ror 8, 4, 2, 1 and then the two halves (the f32 reference chain,
+// tools/chain_ref.hip): a + b == b + a bit for bit, so the totals are bit-identical to it.
 template <int CTRL>
 __device__ inline float dpp_bc(float x) {           // every lane has a source: bound_ctrl on
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true));
@@ -262,16 +188,13 @@ inline int chain_lds_shared(int per_cu) {
 // packed conversion (v_cvt_pk_bf16_f32, round to nearest even) and the two residuals by a
 // bf16 dot: a - hi(a) = dot((hi(a), hi(b)), (-1, 0)) + a, exact (the product is exact and the
 // difference is representable).  v = hi + mid + lo exactly.  7 instructions per pair instead
-// of 11 (a shift / mask and a subtract per residual).  History (tools/chain_ab.sh, results
-// bit-identical throughout): the builtin's accumulating v_dot2c_f32_bf16 took BR 0.906 ->
-// 0.884 us, AR 0.93 -> 0.923 us per SGD step; the asm form below saves its v_movs (0.885 ->
-// 0.877 / 0.930 -> 0.921).  Details:
+// of 11 (a shift / mask and a subtract per residual).  Details:
 //  * the (-1, 0) / (0, -1) operands come from VGPRs made once per kernel: written as the
-//    literal 0x0000bf80 the pair did not reach the instruction as given;
-//  * an asm conversion next to compiler-placed dot2c moved the chain's results (up to 2e-3
-//    after 200 updates): gfx950 needs wait states between a DOT write and another VALU
-//    instruction's read, and the compiler pads only for instructions it can see.  So the
-//    whole split is ONE asm statement that spaces them itself.
+//    literal 0x0000bf80 the pair does not reach the instruction as given;
+//  * gfx950 needs wait states between a DOT write and another VALU instruction's read, and the
+//    compiler pads only for instructions it can see (an asm conversion next to compiler-placed
+//    dot2c moves the chain's results by up to 2e-3 after 200 updates).  So the whole split is
+//    ONE asm statement that spaces them itself.
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 __device__ inline uint32_t cvt_pk_bf16(float a, float b) {
   const bf16x2 r = {(__bf16)a, (__bf16)b};
@@ -366,8 +289,7 @@ __device__ inline floatx4 mfma3t(bf16x8 ahi, bf16x8 amid, bf16x8 alo, bf16x8 b) 
 // into the FMAs (the loss lanes are laid out so that lane j of row g holds exactly that
 // sample, see `ls` in k_chain3):
 //   g2_k += h * x_k  (k = 0..2),   dh = fma(x2, W2_2, fma(x0, W2_0, x1 * W2_1))
-// the same operations in the same order as the round-3 chain (which read the x_k back from
-// an LDS copy of dL/dz2 and compiled (x0 W2_0 + x1 W2_1) + x2 W2_2 to exactly those fmas).  The compiler does not fuse a DPP
+// -- the fmas that (x0 W2_0 + x1 W2_1) + x2 W2_2 compiles to.  The compiler does not fuse a DPP
 // move into v_fmac_f32, hence asm.  Hazard: a DPP source read >= 2 wait states after the
 // VALU write of that register; the x_k are written before slot 0's statement, which starts
 // with s_nop 1 (slot j + 1 reads slot j's g2 sums, so slot 0's statement comes first).  Not

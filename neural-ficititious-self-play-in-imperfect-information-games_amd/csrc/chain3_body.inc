@@ -1,7 +1,11 @@
 // The body of k_chain3 (chain3.h), included textually by the kernel and by chain3_run (the
-// persistent group BR kernel, learner.hip), so that the one-engine kernel's source -- and
-// with it its schedule, which moves with the smallest change -- stays exactly as it is.
+// persistent group BR kernel, br_persist.hip): as a function the body compiles to another
+// register assignment across the whole kernel, and the chain's schedule moves with it.
 // In scope: C (ChainArgs), J (ChainJob), sm (Chain3Smem&), RELU, LOSS, TABLE.
+// One wave per SIMD issues in order and LDS returns a wave's reads in order, so a read parks the
+// serial chain when its s_waitcnt is reached early, and it delays every read queued behind it:
+// hence the comments below on where each LDS read sits.  The placements that lost are in
+// DESIGN.md Appendix A.0b / A.2 and profiles/r07_chain_reads/.
   // the loss-log build (a diagnostic, tests/test_gpu_nn / observability) runs the scalar forms:
   // its extra loss code put packed writes near MFMA registers (tools/mfma_hazards.py rule 2);
   // the packed forms round exactly as the scalar ones, so its weights are the same either way
@@ -81,16 +85,12 @@
   //   is 4 gb2[0], scaled by 1/4 -- exact)        rows 0, 1: b2[1]   rows 2, 3: b2[2]  (own2)
   float* const own1 = g == 3 ? &sm.b2s[w][0] : reinterpret_cast<float*>(&sm.w2t[w][c]) + (g == 0 ? 0 : g == 1 ? 2 : 1);
   float* const own2 = &sm.b2s[w][g < 2 ? 1 : 2];
-  // NFSP_CHAIN_G0ROW (round 6): gb2[0] enters the V transpose as each row's own 16-sample sum
-  // (tot_rows) instead of the 32-sample total replicated in every lane (tot32: one permlane32 and
-  // a copy more); rows g and g ^ 1 hold the same 16 samples, so row 3's total is 2 gb2[0]
-  const float own1_sc = g == 3 ? (NFSP_CHAIN_G0ROW ? 0.5f : 0.25f) : 1.0f;
-  // CH_OWN: the lane's two owned values stay in registers across the steps (ov1, ov2: what
-  // publish() and the b2s stores below put into the own1 / own2 slots).  Each lane is the
-  // only writer of the value it holds (the lanes that share a b2 slot compute bit-identical
-  // totals, see `ls`), so the register is what the read-back returned; LDS keeps its copy for
-  // the other rows' reads next step and for the epilogue
-  constexpr unsigned CH = chain_ch<RELU>();
+  const float own1_sc = g == 3 ? 0.25f : 1.0f;
+  // The lane's two owned values stay in registers across the steps (ov1, ov2: what publish()
+  // and the b2s stores below put into the own1 / own2 slots).  Each lane is the only writer of
+  // the value it holds (the lanes that share a b2 slot compute bit-identical totals, see `ls`),
+  // so nothing is read back; LDS keeps its copy for the other rows' reads next step and for
+  // the epilogue
   float ov1 = g == 3 ? b2_0 : g == 0 ? W2_0 : g == 1 ? W2_2 : W2_1;
   float ov2 = g < 2 ? b2_1 : b2_2;
 #ifdef NFSP_CHAIN_STAMPS
@@ -112,20 +112,17 @@
     const StepRec& R = sm.ring[slot];
     const bf16x8 fa0 = __builtin_bit_cast(bf16x8, R.fa[g][c ^ fsw]);
     const bf16x8 fa1 = __builtin_bit_cast(bf16x8, R.fa[g][(16 + c) ^ fsw]);
-    // X^T, read where each chain measured fastest (results identical): at the head of the
-    // layer-2 arithmetic (CH_XT2, chain3.h).  Without the switches: BR right after the barrier, AR
-    // after the loss (round 3: after the dm reads).  Beside the fa reads both were slower in
-    // round 3 (BR 0.831 -> 0.90 us, bimodal), as was carrying them from the previous step.
-    bf16x8 ba0, ba1;
+    bf16x8 ba0, ba1;                             // X^T, read at the head of layer 2 below
     const char* const rtr = reinterpret_cast<const char*>(&R.fa[0][0]) + tr_off;
+    // the targets: BR here with the fa reads, AR after the Z1 MFMAs (each where it measured fastest)
     float4 tg;
-    if constexpr (CH & CH_TG) tg = R.tg[ls];
+    if constexpr (RELU) tg = R.tg[ls];
     // ---- layer 1, both orientations
     bf16x8 whi, wmid, wlo;
-    // CH_W2: the reads below come before the W split.  They need no barrier: w2t[w] / b2s[w] are
-    // this wave's own rows, last written by its own-stores at the end of the previous step (or
-    // the prologue), and LDS executes a wave's operations in order
-    if constexpr (!(CH & CH_W2)) split3(wr, whi, wmid, wlo, SK);
+    split3(wr, whi, wmid, wlo, SK);
+    // W2 / b2 after the W split.  The reads need no barrier: w2t[w] / b2s[w] are this wave's own
+    // rows, last written by its own-stores at the end of the previous step (or the prologue), and
+    // LDS executes a wave's operations in order
     float W2h[4][3];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -136,27 +133,20 @@
     const float W2_0 = w2c[0], W2_1 = w2c[1], W2_2 = w2c[2];
     const floatx4 b2v = lds4(&sm.b2s[w][0]);
     const float b2_0 = b2v[0], b2_1 = b2v[1], b2_2 = b2v[2];
-    if constexpr (CH & CH_W2) {
-      if constexpr (CH & CH_W2F) __builtin_amdgcn_sched_barrier(0);   // pins the reads above the split
-      split3(wr, whi, wmid, wlo, SK);
-    }
     // Z1^T first (layer 2 waits on it); Z1 (needed only by the backward) is issued after
     // layer 2, so its matrix-core time overlaps the barrier wait
     const floatx4 zh0 = mfma3t(whi, wmid, wlo, fa0);     // Z1^T: hidden 16w+4g+r, sample c
     const floatx4 zh1 = mfma3t(whi, wmid, wlo, fa1);     //                      sample 16+c
     __builtin_amdgcn_sched_barrier(0);
     CHAIN_STAMP(0);
-    // CH_XT2 / CH_TG2: ring slot `slot` was published by the previous step's barrier, so X^T and
-    // the targets are readable before this step's; here the layer-2 arithmetic covers the reads,
-    // and the partial sums are the first reads in the LDS queue after the barrier
-    if constexpr (CH & CH_XT2) {
-      ba0 = tr_pair(rtr, rtr + 256);
-      ba1 = tr_pair(rtr + 8, rtr + 264);
-    }
-    if constexpr (CH & CH_TG2) tg = R.tg[ls];
+    // X^T: ring slot `slot` was published by the previous step's barrier, so it is readable before
+    // this step's; here the ~45 VALU instructions of layer 2 cover the reads, and the partial sums
+    // are the first reads in the LDS queue after the barrier
+    ba0 = tr_pair(rtr, rtr + 256);
+    ba1 = tr_pair(rtr + 8, rtr + 264);
     // ---- layer 2 partial over the slice, from Z1^T
     float p0[3], p1[3];
-    if constexpr (PK & PK_L2) {     // the two sample halves as pairs
+    if constexpr (PK & PK_L2) {     // the two sample halves as pairs (never shipped: chain3.h)
       floatx2 P[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) P[k] = floatx2{0.f, 0.f};
@@ -198,45 +188,28 @@
       pr[g & 1] = __uint_as_float(r01[0]) + __uint_as_float(r01[1]);
       pr[2] = sum_x16(q[2]);
     }
-    // BR: the Z1 MFMAs (and, without CH_TG / CH_TG2, the targets' read) fenced between the
-    // partial stores and the barrier (they overlap the barrier wait).  AR: left to the scheduler,
-    // which measured faster (AR 0.810 -> 0.787 us per SGD step; the BR chain unfenced 0.751 ->
-    // 0.786; tools/chain_ab.sh, results identical)
-    constexpr bool fenced = RELU || (CH & CH_XTF);
+    // BR: the Z1 MFMAs fenced between the partial stores and the barrier (they overlap the
+    // barrier wait).  AR: left to the scheduler, which is faster there (AR fenced 0.787 -> 0.810 us
+    // per SGD step, BR unfenced 0.751 -> 0.786; results identical)
+    constexpr bool fenced = RELU;
     if (fenced) __builtin_amdgcn_sched_barrier(0);
-    if constexpr (CH & CH_XT) {
-      ba0 = tr_pair(rtr, rtr + 256);
-      ba1 = tr_pair(rtr + 8, rtr + 264);
-    }
     const floatx4 zs0 = mfma3(fa0, whi, wmid, wlo);      // Z1: sample 4g+r, hidden 16w+c
     const floatx4 zs1 = mfma3(fa1, whi, wmid, wlo);      //     sample 16+4g+r
-    if constexpr (!(CH & (CH_TG | CH_TG2))) tg = R.tg[ls];   // read before the barrier pins it early
+    if constexpr (!RELU) tg = R.tg[ls];                  // AR: read before the barrier pins it early
     if (fenced) __builtin_amdgcn_sched_barrier(0);       // ... and the Z1 MFMAs issue before it
     CHAIN_STAMP(1);
     __syncthreads();
     CHAIN_STAMP(2);
-    if (RELU && !(CH & (CH_XT | CH_XT2))) {
-      ba0 = tr_pair(rtr, rtr + 256);
-      ba1 = tr_pair(rtr + 8, rtr + 264);
-    }
     // ---- output + loss of sample ls (every wave redundantly, identical results)
     float d0, d1, d2, lr_step;
     float o_keep[3], tt_keep[3], p_keep[3];     // for the optional loss log
     {
-      constexpr bool vo = PK & PK_O;
-      const floatx4 a0 = vo ? lds4v(&sm.po[buf][0][ls][0]) : lds4(&sm.po[buf][0][ls][0]);
-      const floatx4 a1 = vo ? lds4v(&sm.po[buf][1][ls][0]) : lds4(&sm.po[buf][1][ls][0]);
-      const floatx4 a2 = vo ? lds4v(&sm.po[buf][2][ls][0]) : lds4(&sm.po[buf][2][ls][0]);
-      const floatx4 a3 = vo ? lds4v(&sm.po[buf][3][ls][0]) : lds4(&sm.po[buf][3][ls][0]);
-      float o0, o1;
-      if constexpr (PK & PK_O) {
-        const floatx2 o01 = (((a0.xy + a1.xy) + a2.xy) + a3.xy) + floatx2{b2_0, b2_1};
-        o0 = o01.x;
-        o1 = o01.y;
-      } else {
-        o0 = (((a0[0] + a1[0]) + a2[0]) + a3[0]) + b2_0;
-        o1 = (((a0[1] + a1[1]) + a2[1]) + a3[1]) + b2_1;
-      }
+      const floatx4 a0 = lds4(&sm.po[buf][0][ls][0]);
+      const floatx4 a1 = lds4(&sm.po[buf][1][ls][0]);
+      const floatx4 a2 = lds4(&sm.po[buf][2][ls][0]);
+      const floatx4 a3 = lds4(&sm.po[buf][3][ls][0]);
+      const float o0 = (((a0[0] + a1[0]) + a2[0]) + a3[0]) + b2_0;
+      const float o1 = (((a0[1] + a1[1]) + a2[1]) + a3[1]) + b2_1;
       const float o2 = (((a0[2] + a1[2]) + a2[2]) + a3[2]) + b2_2;
       lr_step = tg.w;
       const float tt[3] = {tg.x, tg.y, tg.z};
@@ -311,7 +284,7 @@
           acc -= (tt_keep[k] * (float)CHAIN_MB) * __logf(fminf(fmaxf(p_keep[k], 1e-7f), 1.0f - 1e-7f));
         Ls = acc;
       }
-      const float x = tot32(Ls);             // the 32 samples, round-3 order
+      const float x = tot32(Ls);             // the 32 samples, tot32's order
       if (w == 0 && l == 0) {
         const int in_u = t % spu;
         loss_acc += x * invm;
@@ -322,16 +295,12 @@
         }
       }
     }
-    // gb2 = the 32-sample sums of d (round-3 order): gb2[0] in every lane, gb2[1] in rows 0 / 1
+    // gb2 = the 32-sample sums of d (tot32's order): gb2[0] in every lane, gb2[1] in rows 0 / 1
     // and gb2[2] in rows 2 / 3 (U, the rows that own b2[1] / b2[2])
-    const float G0 = NFSP_CHAIN_G0ROW ? tot_rows(d0) : tot32(d0);
+    const float G0 = tot32(d0);
     const float U = tot32_pair(d1, d2);
     CHAIN_STAMP(3);
     // ---- backward in the sample-major layout: samples 16 mt + 4g + r, hidden 16w + c
-    if (!RELU && !(CH & (CH_XT | CH_XT2))) {
-      ba0 = tr_pair(rtr, rtr + 256);
-      ba1 = tr_pair(rtr + 8, rtr + 264);
-    }
     float dz[8];
     float g2_0, g2_1, g2_2;          // started by slot 0 (bwd_dpp<0>)
     {
@@ -364,13 +333,10 @@
     }
     CHAIN_STAMP(4);
     const float lr = lr_step;
-    {
-      const float v1 = (CH & CH_OWN) ? ov1 : *own1, v2 = (CH & CH_OWN) ? ov2 : *own2;
-      ov1 = v1 - (lr * own1_sc) * V;
-      ov2 = v2 - lr * U;
-      *own1 = ov1;
-      *own2 = ov2;
-    }
+    ov1 = ov1 - (lr * own1_sc) * V;
+    ov2 = ov2 - lr * U;
+    *own1 = ov1;
+    *own2 = ov2;
     if constexpr (PK & PK_W) {      // W1 -= lr dW1, two rows per instruction
       const floatx2 nl = {-lr, -lr};
 #pragma unroll

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import learner_oracle as LO
+from engine_ref import learner_state, nets, oracle_cfg
 
 pytestmark = pytest.mark.gpu
 
@@ -25,41 +26,13 @@ TINY = dict(n_lanes=1024, rl_capacity=200, sl_capacity=150)
 QUIRKS = 7
 
 
-def _bits(xf):
-    x = np.asarray(xf).reshape(len(xf), -1) != 0
-    return (x.astype(np.int64) << np.arange(x.shape[1])).sum(axis=1)
-
-
-def _snapshot(eng):
-    st = eng.stats()
-    out = []
-    for a in (0, 1):
-        m = {k: (v.cpu().numpy().copy() if torch.is_tensor(v) else v) for k, v in eng.memories(a).items()}
-        n_sl = int(st["last_sl"][a])
-        out.append(dict(
-            w={n: eng.get_weights(a, n) for n in (0, 1, 2)},
-            rl_total=int(st["rl_total"][a]), last_rl=int(st["last_rl"][a]),
-            sl_total=int(st["sl_total"][a]), last_sl=n_sl,
-            iteration=int(st["iteration"][a]), br_updates=int(st["br_updates"][a]),
-            epsilon=float(st["epsilon"][a]),
-            rl_s_bits=_bits(m["rl_s"]), rl_s2_bits=_bits(m["rl_s2"]), rl_a=m["rl_a"],
-            rl_r=m["rl_r"], rl_t=m["rl_t"],
-            sl_s_bits=_bits(m["sl_s"]), sl_a=m["sl_a"],
-            pend_x=m["pend_x"][:n_sl].astype(np.int64) & 0xFFFFFFFF, pend_a=m["pend_a"][:n_sl],
-            pend_pos=m["pend_pos"][:n_sl]))
-    return st, out
-
-
 def _update_against_oracle(eng):
     """One learner call from the engine's present memories; returns the stats before it, the
     weights before it and the oracle's result, after checking counters and weights."""
-    st0, state = _snapshot(eng)
+    st0, state = learner_state(eng)
     eng.update()
     st1 = eng.stats()
-    c = eng.cfg
-    cfg = dict(c=c.inserts_per_update, batch=c.batch, epochs=c.epochs, rl_capacity=c.rl_capacity,
-               sl_capacity=c.sl_capacity, target_every=c.target_every, lr_br=c.lr_br, lr_ar=c.lr_ar,
-               gamma=c.gamma, seed=c.seed, epsilon=c.epsilon)
+    cfg = oracle_cfg(eng.cfg)
     want = LO.learner_step(cfg, state, quirks=QUIRKS)
     for a in (0, 1):
         W = want[a]
@@ -72,10 +45,6 @@ def _update_against_oracle(eng):
             assert d.max() <= 1e-4, (a, n, d.max())
             assert np.median(d) <= 1e-7, (a, n, np.median(d))
     return st0, state, want
-
-
-def _nets(eng):
-    return [eng.get_weights(a, n) for a in (0, 1) for n in (0, 1, 2)]
 
 
 @pytest.mark.parametrize("batch,epochs,target_every", [
@@ -128,7 +97,7 @@ def test_loss_log_changes_no_weight(pkg):
             eng.step()
         st = eng.stats()
         assert min(st["br_updates"]) > 3 and min(st["ar_updates"]) > 0
-        out.append(_nets(eng))
+        out.append(nets(eng))
     for x, y in zip(*out):
         assert np.array_equal(x, y)
 
@@ -139,13 +108,13 @@ def test_table_launch_matches_standalone(pkg):
     kw = dict(quirks=QUIRKS, target_every=3, **TINY)
     g = pkg.engine.EngineGroup(2, seed=99, init_seed=5, **kw)
     solo = [pkg.engine.SelfPlayEngine(seed=99 + r, init_seed=5 + r, **kw) for r in range(2)]
-    w0 = _nets(solo[0])
+    w0 = nets(solo[0])
     g.step()
     for e in solo:
         e.step()
     torch.cuda.synchronize()
     for r in range(2):
         assert min(solo[r].stats()["br_updates"]) > 3
-        for x, y in zip(_nets(g.replicas[r]), _nets(solo[r])):
+        for x, y in zip(nets(g.replicas[r]), nets(solo[r])):
             assert np.array_equal(x, y), r
-    assert not np.array_equal(_nets(solo[0])[1], w0[1])     # the BR net moved
+    assert not np.array_equal(nets(solo[0])[1], w0[1])     # the BR net moved

@@ -3,7 +3,7 @@
 C2: 65,536 lanes, M_RL = M_SL = 40,000, eta 0.1.
 * sampled lanes of a rollout (wave / workgroup edges, the last lane, random ones) are
   replayed one by one by oracle/rollout_oracle.py._one_lane and found in the memories
-  through the per-lane record counts (test_gpu_fullsize._check_lanes);
+  through the per-lane record counts (engine_ref.check_lanes);
 * one whole learner call (nfsp_engine_update, ~1,000 updates per agent and net, with the
   memories full: M_RL wraps, the reservoir replaces) is replayed update by update by
   oracle/learner_oracle.py.
@@ -29,43 +29,13 @@ every distinct observation in M_RL within 5e-3 (measured: 1.1e-3).
 """
 import numpy as np
 import pytest
-import torch
 
 import learner_oracle as LO
 import nn_oracle as nn
-from test_gpu_fullsize import _bits_dev, _check_lanes, _sample_lanes
+from engine_ref import C2, C3, learner_state, obs_bits_dev, oracle_cfg, sample_lanes
+from engine_ref import check_lanes as check_sampled_lanes      # _c2_engine has a flag named check_lanes
 
 pytestmark = pytest.mark.gpu
-
-C2 = dict(n_lanes=65_536, rl_capacity=40_000, sl_capacity=40_000, eta=0.1)
-C3 = dict(n_lanes=1_048_576, rl_capacity=200_000, sl_capacity=2_000_000)
-
-
-def _snapshot(eng):
-    """The engine after a rollout, in learner_oracle's state layout (bits computed on device)."""
-    st = eng.stats()
-    out = []
-    for a in (0, 1):
-        m = eng.memories(a)
-        n_sl = int(st["last_sl"][a])
-        out.append(dict(
-            w={n: eng.get_weights(a, n) for n in (0, 1, 2)},
-            rl_total=int(st["rl_total"][a]), last_rl=int(st["last_rl"][a]),
-            sl_total=int(st["sl_total"][a]), last_sl=n_sl,
-            iteration=int(st["iteration"][a]), br_updates=int(st["br_updates"][a]),
-            epsilon=float(st["epsilon"][a]),
-            rl_s_bits=_bits_dev(m["rl_s"]), rl_s2_bits=_bits_dev(m["rl_s2"]),
-            rl_a=m["rl_a"].cpu().numpy(), rl_r=m["rl_r"].cpu().numpy(), rl_t=m["rl_t"].cpu().numpy(),
-            sl_s_bits=_bits_dev(m["sl_s"]), sl_a=m["sl_a"].cpu().numpy(),
-            pend_x=m["pend_x"][:n_sl].cpu().numpy().astype(np.int64) & 0xFFFFFFFF,
-            pend_a=m["pend_a"][:n_sl].cpu().numpy(), pend_pos=m["pend_pos"][:n_sl].cpu().numpy()))
-    return st, out
-
-
-def _oracle_cfg(c):
-    return dict(c=c.inserts_per_update, batch=c.batch, epochs=c.epochs, rl_capacity=c.rl_capacity,
-                sl_capacity=c.sl_capacity, target_every=c.target_every, lr_br=c.lr_br, lr_ar=c.lr_ar,
-                gamma=c.gamma, seed=c.seed, epsilon=c.epsilon)
 
 
 def _check_learner(eng, st0, st1, want, state, prefix=None, strict=True):
@@ -95,7 +65,7 @@ def _check_learner(eng, st0, st1, want, state, prefix=None, strict=True):
             assert np.abs(y0 - y1).max() <= (1e-5 if strict else 5e-3), (a, n, np.abs(y0 - y1).max())
         m = eng.memories(a)
         size = int(st1["sl_size"][a])
-        assert np.array_equal(_bits_dev(m["sl_s"][:size]), W["res_x"][:size])
+        assert np.array_equal(obs_bits_dev(m["sl_s"][:size]), W["res_x"][:size])
         assert np.array_equal(m["sl_a"][:size].cpu().numpy(), W["res_a"][:size])
 
 
@@ -105,15 +75,15 @@ def _c2_engine(pkg, check_lanes=False):
     eng = pkg.engine.SelfPlayEngine(seed=seed, init_seed=3, **C2)
     eng.rollout()
     if check_lanes:
-        _check_lanes(eng, seed, 0, _sample_lanes(C2["n_lanes"], 64, 11))
+        check_sampled_lanes(eng, seed, 0, sample_lanes(C2["n_lanes"], 64, 11))
     eng.update()
     for _ in range(5):
         eng.step()
     before = tuple(int(v) for v in eng.stats()["rl_total"])
     eng.rollout()                                   # g = 6
     if check_lanes:
-        _check_lanes(eng, seed, 6, _sample_lanes(C2["n_lanes"], 64, 12), rl_before=before)
-    st0, state = _snapshot(eng)
+        check_sampled_lanes(eng, seed, 6, sample_lanes(C2["n_lanes"], 64, 12), rl_before=before)
+    st0, state = learner_state(eng)
     assert min(st0["rl_total"]) > C2["rl_capacity"] and max(st0["sl_total"]) > C2["sl_capacity"]
     return eng, st0, state
 
@@ -125,7 +95,7 @@ def test_c2_rollout_sampled_lanes_and_learner_call(pkg, prefix):
         eng.set_update_limit(prefix)
     eng.update()
     st1 = eng.stats()
-    want = LO.learner_step(_oracle_cfg(eng.cfg), state, quirks=eng.cfg.quirks, max_updates=prefix)
+    want = LO.learner_step(oracle_cfg(eng.cfg), state, quirks=eng.cfg.quirks, max_updates=prefix)
     assert min(w["U_br"] for w in want) > 500
     _check_learner(eng, st0, st1, want, state, prefix=prefix, strict=prefix is not None)
 
@@ -135,11 +105,11 @@ def test_c3_learner_prefix(pkg):
     for _ in range(2):
         eng.step()
     eng.rollout()
-    st0, state = _snapshot(eng)
+    st0, state = learner_state(eng)
     assert min(st0["rl_total"]) > C3["rl_capacity"]          # M_RL is the capacity window
     prefix = 200
     eng.set_update_limit(prefix)
     eng.update()
     st1 = eng.stats()
-    want = LO.learner_step(_oracle_cfg(eng.cfg), state, quirks=eng.cfg.quirks, max_updates=prefix)
+    want = LO.learner_step(oracle_cfg(eng.cfg), state, quirks=eng.cfg.quirks, max_updates=prefix)
     _check_learner(eng, st0, st1, want, state, prefix=prefix)

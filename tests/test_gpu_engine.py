@@ -10,6 +10,7 @@ import torch
 
 import nn_oracle as nn
 import rollout_oracle as R
+from engine_ref import check_rollout, obs_bits, weights_flat
 from rollout_oracle import philox4x32
 
 pytestmark = pytest.mark.gpu
@@ -17,48 +18,8 @@ pytestmark = pytest.mark.gpu
 U32 = np.uint32
 
 
-def bits(rows):
-    rows = np.asarray(rows)
-    assert np.all((rows == 0) | (rows == 1))
-    return (rows.astype(np.uint64) << np.arange(30, dtype=np.uint64)).sum(axis=1)
-
-
 def engine(pkg, **kw):
     return pkg.engine.SelfPlayEngine(**kw)
-
-
-def weights_flat(eng):
-    return np.concatenate([eng.get_weights(a, n) for a in (0, 1) for n in (0, 1, 2)])
-
-
-def check_rollout(eng, ref, rl_before=(0, 0)):
-    for p in (0, 1):
-        m = eng.memories(p)
-        st = eng.stats()
-        n = st["last_rl"][p]
-        assert n == len(ref["rl"][p]), (p, n, len(ref["rl"][p]))
-        lo = rl_before[p]
-        rows = (np.arange(lo, lo + n) % m["log_cap"])
-        s = m["rl_s"].cpu().numpy()[rows]
-        s2 = m["rl_s2"].cpu().numpy()[rows]
-        a = m["rl_a"].cpu().numpy()[rows]
-        r = m["rl_r"].cpu().numpy()[rows]
-        t = m["rl_t"].cpu().numpy()[rows]
-        exp = ref["rl"][p]
-        assert np.array_equal(bits(s), np.array([e[0] for e in exp], np.uint64))
-        assert np.array_equal(bits(s2), np.array([e[3] for e in exp], np.uint64))
-        assert np.abs(a - np.array([e[1] for e in exp])).max() <= 1e-6
-        assert np.array_equal(r, np.array([e[2] for e in exp], np.float32))
-        assert np.array_equal(t, np.array([e[4] for e in exp], np.uint8))
-        k = st["last_sl"][p]
-        assert k == len(ref["sl"][p])
-        px = m["pend_x"][:k].cpu().numpy().astype(np.uint32)
-        pa = m["pend_a"][:k].cpu().numpy()
-        pp = m["pend_pos"][:k].cpu().numpy()
-        assert np.array_equal(px, np.array([e[0] for e in ref["sl"][p]], np.uint32))
-        exp_a = np.array([e[1] for e in ref["sl"][p]], np.float32).reshape(-1, 3)    # k may be 0 (eta = 0)
-        assert np.abs(pa - exp_a).max(initial=0.0) <= 1e-6
-        assert np.array_equal(pp, np.array([e[2] for e in ref["sl"][p]]))
 
 
 @pytest.mark.parametrize("quirks", [7, 3, 120, 248])  # 120: one-hot SL, reservoir, linear Q, const eps;
@@ -182,7 +143,7 @@ def test_reservoir_replacement_rule(pkg):
                 res_x[slot] = int(pend[a]["pend_x"][q]) & 0xFFFFFFFF
                 res_a[slot] = pend[a]["pend_a"][q]
         m = eng.memories(a)
-        assert np.array_equal(bits(m["sl_s"].cpu().numpy()[:cap]), res_x)
+        assert np.array_equal(obs_bits(m["sl_s"].cpu().numpy()[:cap]), res_x)
         assert np.array_equal(m["sl_a"].cpu().numpy()[:cap], res_a)
         assert eng.stats()["sl_size"][a] == cap
 

@@ -21,67 +21,9 @@ import numpy as np
 import pytest
 import torch
 
-import rollout_oracle as R
+from engine_ref import C3, check_lanes, obs_bits_dev, sample_lanes, weights_flat
 
 pytestmark = pytest.mark.gpu
-
-C3 = dict(n_lanes=1_048_576, rl_capacity=200_000, sl_capacity=2_000_000)
-
-
-def _weights_flat(eng):
-    return np.concatenate([eng.get_weights(a, n) for a in (0, 1) for n in (0, 1, 2)])
-
-
-def _bits_dev(x):
-    """[n, 30] 0/1 float rows (device) -> int64 bit masks (host)."""
-    w = (torch.ones(30, dtype=torch.int64, device=x.device) << torch.arange(30, device=x.device))
-    return ((x != 0).to(torch.int64) * w).sum(dim=1).cpu().numpy()
-
-
-def _sample_lanes(n, k, seed):
-    edges = [0, 1, 63, 64, 255, 256, 4095, 4096, n // 2, n - 2, n - 1]
-    rng = np.random.RandomState(seed)
-    return sorted(set(edges) | set(rng.randint(0, n, size=k).tolist()))
-
-
-def _check_lanes(eng, seed, g, lanes, game="leduc", rl_before=(0, 0)):
-    st = eng.stats()
-    cnt = eng.lane_counts()
-    assert cnt[:, 0].sum() == st["last_rl"][0] and cnt[:, 1].sum() == st["last_rl"][1]
-    assert cnt[:, 2].sum() == st["last_sl"][0] and cnt[:, 3].sum() == st["last_sl"][1]
-    pre = np.zeros_like(cnt)
-    pre[1:] = np.cumsum(cnt, axis=0)[:-1]
-    w = _weights_flat(eng)
-    alias = bool(eng.cfg.quirks & 4)
-    eps = (float(st["epsilon"][0]), float(st["epsilon"][1]))
-    mems = [eng.memories(p) for p in (0, 1)]
-    for L in lanes:
-        ref = R._one_lane(L, g, seed, w, eps, eng.cfg.eta, alias, game)
-        for p in (0, 1):
-            m = mems[p]
-            n = len(ref["rl"][p])
-            assert cnt[L, p] == n, (L, p)
-            rows = torch.tensor((rl_before[p] + pre[L, p] + np.arange(n)) % m["log_cap"],
-                                dtype=torch.int64, device=m["rl_s"].device)
-            if n:
-                exp = ref["rl"][p]
-                assert np.array_equal(_bits_dev(m["rl_s"][rows]), [e[0] for e in exp]), (L, p)
-                assert np.array_equal(_bits_dev(m["rl_s2"][rows]), [e[3] for e in exp]), (L, p)
-                a = m["rl_a"][rows].cpu().numpy()
-                assert np.abs(a - np.array([e[1] for e in exp])).max() <= 1e-6, (L, p)
-                assert np.array_equal(m["rl_r"][rows].cpu().numpy(), np.array([e[2] for e in exp], np.float32))
-                assert np.array_equal(m["rl_t"][rows].cpu().numpy(), np.array([e[4] for e in exp], np.uint8))
-            k = len(ref["sl"][p])
-            assert cnt[L, 2 + p] == k, (L, p)
-            if k:
-                q = slice(int(pre[L, 2 + p]), int(pre[L, 2 + p]) + k)
-                px = m["pend_x"][q].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
-                assert np.array_equal(px, [e[0] for e in ref["sl"][p]]), (L, p)
-                pa = m["pend_a"][q].cpu().numpy()
-                assert np.abs(pa - np.array([e[1] for e in ref["sl"][p]])).max() <= 1e-6
-                pos = m["pend_pos"][q].cpu().numpy()
-                assert np.array_equal(pos, [rl_before[p] + pre[L, p] + e[2] for e in ref["sl"][p]])
-    return cnt
 
 
 def _valid_obs(bits, game):
@@ -104,14 +46,14 @@ def test_fullsize_rollout_sampled_lanes_and_records(pkg, game):
     eng.rollout()
     st = eng.stats()
     assert st["hands"] == C3["n_lanes"]
-    _check_lanes(eng, seed, 0, _sample_lanes(C3["n_lanes"], 96, 5), game)
+    check_lanes(eng, seed, 0, sample_lanes(C3["n_lanes"], 96, 5), game)
     # every record of the rollout
     assert st["reward"][0] + st["reward"][1] == 0.0          # zero-sum hands
     for p in (0, 1):
         m = eng.memories(p)
         n = int(st["last_rl"][p])
         for key in ("rl_s", "rl_s2"):
-            b = _bits_dev(m[key][:n])
+            b = obs_bits_dev(m[key][:n])
             assert _valid_obs(b, game).all(), key
         r = m["rl_r"][:n].cpu().numpy()
         assert np.all(2 * r == np.round(2 * r)) and np.abs(r).max() <= 13
@@ -124,7 +66,7 @@ def test_fullsize_rollout_sampled_lanes_and_records(pkg, game):
     eng.update()
     before = tuple(int(v) for v in eng.stats()["rl_total"])
     eng.rollout()
-    _check_lanes(eng, seed, 1, _sample_lanes(C3["n_lanes"], 32, 6), game, rl_before=before)
+    check_lanes(eng, seed, 1, sample_lanes(C3["n_lanes"], 32, 6), game, rl_before=before)
 
 
 def _eps_after(eps0, updates):
@@ -161,7 +103,7 @@ def test_fullsize_step_is_deterministic(pkg):
     def run():
         e = pkg.engine.SelfPlayEngine(seed=4321, init_seed=2, **C3)
         e.step()
-        return e.stats(), _weights_flat(e)
+        return e.stats(), weights_flat(e)
     s1, w1 = run()
     torch.cuda.empty_cache()
     s2, w2 = run()

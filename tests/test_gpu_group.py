@@ -14,26 +14,13 @@ import numpy as np
 import pytest
 import torch
 
+from engine_ref import STAT_KEYS, mem, nets
+
 pytestmark = pytest.mark.gpu
 
 # small memories (M_RL wraps, M_SL replaces) and a short target-sync period, so one step has
 # several BR rounds whose segments differ between replicas and agents
 SMALL = dict(n_lanes=2048, rl_capacity=3000, sl_capacity=2000, target_every=7)
-
-
-def nets(eng):
-    return [eng.get_weights(a, n) for a in (0, 1) for n in (0, 1, 2)]
-
-
-def mem(eng, a):
-    m = eng.memories(a)
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in m.items() if isinstance(v, torch.Tensor)}
-
-
-STAT_KEYS = ("hands", "rl_total", "sl_total", "rl_size", "sl_size", "br_updates", "ar_updates",
-             "iteration", "target_syncs", "actions", "reward", "epsilon", "temp", "lr_br",
-             "exploitability")
 
 
 @pytest.mark.parametrize("quirks,R", [(None, 3), (120, 2)])

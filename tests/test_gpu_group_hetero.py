@@ -4,11 +4,11 @@ hyperparameter sweep in one launch.
 
 Bar, everywhere: replica r is BIT-IDENTICAL to a standalone SelfPlayEngine built from cfgs[r]
 and the same init seed and stepped as often -- the six nets, the counters and schedules
-(test_gpu_group.STAT_KEYS), the memories and state_digest().  No tolerance anywhere."""
+(engine_ref.STAT_KEYS), the memories and state_digest().  No tolerance anywhere."""
 import numpy as np
 import pytest
 
-from test_gpu_group import STAT_KEYS, mem, nets
+from engine_ref import STAT_KEYS, mem, nets
 
 pytestmark = pytest.mark.gpu
 

@@ -17,9 +17,9 @@ Tolerances:
 """
 import numpy as np
 import pytest
-import torch
 
 import learner_oracle as LO
+from engine_ref import learner_state, obs_bits, oracle_cfg
 
 CFG = dict(n_lanes=4096, rl_capacity=3000, sl_capacity=2000, target_every=30, seed=4242)
 # edge cases: memories barely above the batch (the RL window is always capacity-bound, the
@@ -32,31 +32,6 @@ CASES = {
     "batch64_e3": (dict(n_lanes=4096, rl_capacity=3000, sl_capacity=2000, target_every=20, seed=11,
                         batch=64, epochs=3, inserts_per_update=96), "leduc"),
 }
-
-
-def _bits(xf):
-    x = np.asarray(xf).reshape(len(xf), -1) != 0
-    return (x.astype(np.int64) << np.arange(x.shape[1])).sum(axis=1)
-
-
-def _snapshot(eng):
-    st = eng.stats()
-    out = []
-    for a in (0, 1):
-        m = {k: (v.cpu().numpy().copy() if torch.is_tensor(v) else v) for k, v in eng.memories(a).items()}
-        n_sl = int(st["last_sl"][a])
-        out.append(dict(
-            w={n: eng.get_weights(a, n) for n in (0, 1, 2)},
-            rl_total=int(st["rl_total"][a]), last_rl=int(st["last_rl"][a]),
-            sl_total=int(st["sl_total"][a]), last_sl=n_sl,
-            iteration=int(st["iteration"][a]), br_updates=int(st["br_updates"][a]),
-            epsilon=float(st["epsilon"][a]),
-            rl_s_bits=_bits(m["rl_s"]), rl_s2_bits=_bits(m["rl_s2"]), rl_a=m["rl_a"],
-            rl_r=m["rl_r"], rl_t=m["rl_t"],
-            sl_s_bits=_bits(m["sl_s"]), sl_a=m["sl_a"],
-            pend_x=m["pend_x"][:n_sl].astype(np.int64) & 0xFFFFFFFF, pend_a=m["pend_a"][:n_sl],
-            pend_pos=m["pend_pos"][:n_sl]))
-    return st, out
 
 
 @pytest.mark.gpu
@@ -76,13 +51,11 @@ def test_learner_step_matches_oracle(pkg, case, quirks):
     for _ in range(2):
         eng.step()
     eng.rollout()
-    st0, state = _snapshot(eng)
+    st0, state = learner_state(eng)
     eng.update()
     st1 = eng.stats()
     c = eng.cfg
-    cfg = dict(c=c.inserts_per_update, batch=c.batch, epochs=c.epochs, rl_capacity=c.rl_capacity,
-               sl_capacity=c.sl_capacity, target_every=c.target_every, lr_br=c.lr_br, lr_ar=c.lr_ar,
-               gamma=c.gamma, seed=c.seed, epsilon=c.epsilon)
+    cfg = oracle_cfg(c)
     want = LO.learner_step(cfg, state, quirks=quirks)
     for a in (0, 1):
         W = want[a]
@@ -107,7 +80,7 @@ def test_learner_step_matches_oracle(pkg, case, quirks):
             assert np.median(d) <= tol_med, (a, n, np.median(d))
         m = eng.memories(a)
         size = int(st1["sl_size"][a])
-        assert np.array_equal(_bits(m["sl_s"].cpu().numpy()[:size]), W["res_x"][:size])
+        assert np.array_equal(obs_bits(m["sl_s"].cpu().numpy()[:size]), W["res_x"][:size])
         assert np.array_equal(m["sl_a"].cpu().numpy()[:size], W["res_a"][:size])
 
 
@@ -119,9 +92,7 @@ def test_single_lane_engine_matches_oracle(pkg):
     eng = pkg.engine.SelfPlayEngine(n_lanes=1, rl_capacity=300, sl_capacity=150, target_every=3,
                                     eta=0.5, seed=31337, init_seed=5)
     c = eng.cfg
-    cfg = dict(c=c.inserts_per_update, batch=c.batch, epochs=c.epochs, rl_capacity=c.rl_capacity,
-               sl_capacity=c.sl_capacity, target_every=c.target_every, lr_br=c.lr_br, lr_ar=c.lr_ar,
-               gamma=c.gamma, seed=c.seed, epsilon=c.epsilon)
+    cfg = oracle_cfg(c)
     checked = ar_checked = 0
     for _ in range(4000):
         eng.rollout()
@@ -131,7 +102,7 @@ def test_single_lane_engine_matches_oracle(pkg):
         if not due:
             eng.update()
             continue
-        st0, state = _snapshot(eng)
+        st0, state = learner_state(eng)
         eng.update()
         st1 = eng.stats()
         want = LO.learner_step(cfg, state, quirks=c.quirks)
@@ -147,7 +118,7 @@ def test_single_lane_engine_matches_oracle(pkg):
                 assert d.max() <= 1e-4, (a, n, d.max())
             size = int(st1["sl_size"][a])
             m = eng.memories(a)
-            assert np.array_equal(_bits(m["sl_s"].cpu().numpy()[:size]), W["res_x"][:size])
+            assert np.array_equal(obs_bits(m["sl_s"].cpu().numpy()[:size]), W["res_x"][:size])
         checked += 1
         if (checked >= 12 and ar_checked >= 4 and min(st1["rl_total"]) > c.rl_capacity
                 and max(st1["sl_total"]) > c.sl_capacity):

@@ -24,13 +24,11 @@ import pytest
 import torch
 
 import learner_oracle as LO
-import nn_oracle as nn
-from test_gpu_configs import C2, _oracle_cfg, _snapshot
+from engine_ref import C2, learner_state, oracle_cfg, replay_ar
 
 pytestmark = pytest.mark.gpu
 
 CH = 64
-REL = 4e-7
 
 
 def _engine_after(pkg, k):
@@ -48,40 +46,10 @@ def _engine_after(pkg, k):
     return eng
 
 
-def _replay(cfg, mbs, u0, u1, w, lr, rel=REL, closest=None, relu_closest=None):
-    """Oracle AR updates [u0, u1) from weights w; returns (weights, set of updates with an
-    ambiguous clip decision: some p within a relative `rel` of a clip bound).  `closest`
-    (dict): per update, the smallest relative distance of any p to a clip bound."""
-    net = nn.MLP(nn.ACT_SOFTMAX, 64, weights=nn.unpack_weights(w))
-    amb = set()
-    cur = [None]
-    lo, hi = float(nn.CE_EPS), 1.0 - float(nn.CE_EPS)
-
-    def probe(p):
-        p = np.asarray(p, np.float64)
-        r = np.minimum(np.abs(p - hi) / hi, np.abs(p - lo) / lo)
-        if closest is not None:
-            closest[cur[0]] = min(closest.get(cur[0], np.inf), float(r.min()))
-        if (r <= rel).any():
-            amb.add(cur[0])
-    net.clip_probe = probe
-
-    def rprobe(z):
-        if relu_closest is not None:
-            relu_closest[cur[0]] = min(relu_closest.get(cur[0], np.inf), float(np.abs(z).min()))
-    net.relu_probe = rprobe
-    for u, xb, ya, perms in mbs[u0:u1]:
-        if xb is None:
-            continue
-        cur[0] = u
-        net.fit(LO.bits_to_x(xb), ya, np.float32(lr), epochs=cfg["epochs"], perms=perms)
-    return net.flat(), amb
-
-
 def test_whole_c2_call_divergence_is_a_relu_kink(pkg):
     eng0 = _engine_after(pkg, 0)
-    st0, state = _snapshot(eng0)
-    cfg = _oracle_cfg(eng0.cfg)
+    st0, state = learner_state(eng0)
+    cfg = oracle_cfg(eng0.cfg)
     quirks = eng0.cfg.quirks
     del eng0
     mbs = [list(LO.ar_minibatches(cfg, state, a, quirks)) for a in (0, 1)]
@@ -100,7 +68,7 @@ def test_whole_c2_call_divergence_is_a_relu_kink(pkg):
         for a in (0, 1):
             if u0 >= len(mbs[a]):
                 continue
-            w_or, amb = _replay(cfg, mbs[a], u0, min(u1, len(mbs[a])), weights_at[u0][a], cfg["lr_ar"])
+            w_or, amb = replay_ar(cfg, mbs[a], u0, min(u1, len(mbs[a])), weights_at[u0][a], cfg["lr_ar"])
             d = float(np.abs(w_or - weights_at[u1][a]).max())
             report.append((a, u0, u1, d, sorted(amb)))
             ambiguous_total += len(amb)
@@ -119,7 +87,7 @@ def test_whole_c2_call_divergence_is_a_relu_kink(pkg):
             if u0 >= len(mbs[a]):
                 continue
             rc = {}
-            w, _ = _replay(cfg, mbs[a], u0, u1, w, cfg["lr_ar"], closest=closest, relu_closest=rc)
+            w, _ = replay_ar(cfg, mbs[a], u0, u1, w, cfg["lr_ar"], closest=closest, relu_closest=rc)
             d = float(np.abs(w - weights_at[bounds[i + 1]][a]).max())
             near = min(((v, u) for u, v in closest.items() if u < u1), default=(np.inf, None))
             rnear = min(((v, u) for u, v in rc.items()), default=(np.inf, None))

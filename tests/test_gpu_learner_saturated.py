@@ -25,8 +25,7 @@ import pytest
 import torch
 
 import learner_oracle as LO
-from test_gpu_configs import _oracle_cfg, _snapshot
-from test_gpu_learner_divergence import _replay
+from engine_ref import learner_state, oracle_cfg, replay_ar
 
 pytestmark = pytest.mark.gpu
 
@@ -59,8 +58,8 @@ def _rel(a, b):
 
 def test_saturated_ar_single_updates_agree_and_divergence_starts_at_clip_flips(pkg):
     eng0 = _engine_after(pkg, 0)
-    st0, state = _snapshot(eng0)
-    cfg = _oracle_cfg(eng0.cfg)
+    st0, state = learner_state(eng0)
+    cfg = oracle_cfg(eng0.cfg)
     quirks = eng0.cfg.quirks
     del eng0
     mbs = [list(LO.ar_minibatches(cfg, state, a, quirks)) for a in (0, 1)]
@@ -77,7 +76,7 @@ def test_saturated_ar_single_updates_agree_and_divergence_starts_at_clip_flips(p
     for a in (0, 1):
         for k in range(n):
             closest = {}
-            w_or, amb = _replay(cfg, mbs[a], k, k + 1, w_at[k][a], cfg["lr_ar"], rel=REL, closest=closest)
+            w_or, amb = replay_ar(cfg, mbs[a], k, k + 1, w_at[k][a], cfg["lr_ar"], rel=REL, closest=closest)
             d = _rel(w_or, w_at[k + 1][a])
             resync.append((a, k, d, closest.get(mbs[a][k][0], np.inf), bool(amb)))
             if d > 1e-5:
@@ -87,7 +86,7 @@ def test_saturated_ar_single_updates_agree_and_divergence_starts_at_clip_flips(p
         prev = 0.0
         for k in range(n):
             rc, closest = {}, {}
-            w, amb = _replay(cfg, mbs[a], k, k + 1, w, cfg["lr_ar"], rel=REL, closest=closest, relu_closest=rc)
+            w, amb = replay_ar(cfg, mbs[a], k, k + 1, w, cfg["lr_ar"], rel=REL, closest=closest, relu_closest=rc)
             d = _rel(w, w_at[k + 1][a])
             z = min(rc.values(), default=np.inf)
             if d > 1e-4 and prev <= 1e-4:               # an onset

@@ -57,9 +57,7 @@ import pytest
 
 import learner_oracle as LO
 import rollout_oracle as R
-from test_gpu_configs import _oracle_cfg
-from test_gpu_engine import check_rollout, weights_flat
-from test_gpu_learner import _bits, _snapshot
+from engine_ref import check_rollout, learner_state, obs_bits, oracle_cfg, weights_flat
 
 pytestmark = pytest.mark.gpu
 
@@ -105,10 +103,10 @@ def test_learner_step_off_default(pkg, case):
         for _ in range(2):
             eng.step()
     eng.rollout()
-    st0, state = _snapshot(eng)
+    st0, state = learner_state(eng)
     eng.update()
     st1 = eng.stats()
-    cfg = _oracle_cfg(c)
+    cfg = oracle_cfg(c)
     want = LO.learner_step(cfg, state, quirks=quirks)
     tol_max, tol_med = (1e-3, 1e-6) if quirks >= 8 else (1e-4, 1e-7)
     tol_max, tol_med = tol_max * factor, tol_med * factor
@@ -159,7 +157,7 @@ def test_learner_step_off_default(pkg, case):
             assert md <= tol_med, (a, n, md)
         m = eng.memories(a)
         size = int(st1["sl_size"][a])
-        assert np.array_equal(_bits(m["sl_s"].cpu().numpy()[:size]), W["res_x"][:size])
+        assert np.array_equal(obs_bits(m["sl_s"].cpu().numpy()[:size]), W["res_x"][:size])
         assert np.array_equal(m["sl_a"].cpu().numpy()[:size], W["res_a"][:size])
 
 

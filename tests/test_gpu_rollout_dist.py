@@ -42,6 +42,7 @@ import pytest
 import torch
 
 import rollout_dist_ref as rd
+from engine_ref import weights_flat
 
 pytestmark = pytest.mark.gpu
 
@@ -82,10 +83,6 @@ def z_file(pkg):
     closed form of case g (twice) and the 11 independence statistics."""
     led, kuhn = rd.stats_per_rollout(tree_of(pkg, "leduc").ndec), rd.stats_per_rollout(tree_of(pkg, "kuhn").ndec)
     return rd.z_star(16 * led + 2 * kuhn + 6 * led + 4 * led + 2 * 9 * tree_of(pkg, "leduc").ndec + 11)
-
-
-def weights_flat(eng):
-    return np.concatenate([eng.get_weights(a, n) for a in (0, 1) for n in (0, 1, 2)])
 
 
 def _cell_counts(tree, p, codes, counts, shape):

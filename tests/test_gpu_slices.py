@@ -26,11 +26,10 @@ import pytest
 import torch
 
 import rollout_oracle as R
-from test_gpu_fullsize import _bits_dev, _sample_lanes, _weights_flat
+from engine_ref import C3, obs_bits_dev, sample_lanes, weights_flat
 
 pytestmark = pytest.mark.gpu
 
-C3 = dict(n_lanes=1_048_576, rl_capacity=200_000, sl_capacity=2_000_000)
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -78,7 +77,7 @@ def _check_slice_lanes(eng, seed, lanes, rl_before, w=None, eps=None, game="ledu
     assert cnt[:, 0].sum() == st["last_rl"][0] and cnt[:, 1].sum() == st["last_rl"][1]
     pre = np.zeros_like(cnt)
     pre[1:] = np.cumsum(cnt, axis=0)[:-1]
-    w = _weights_flat(eng) if w is None else w
+    w = weights_flat(eng) if w is None else w
     eps = (float(st["epsilon"][0]), float(st["epsilon"][1])) if eps is None else eps
     mems = [eng.memories(p) for p in (0, 1)]
     for L in lanes:
@@ -92,8 +91,8 @@ def _check_slice_lanes(eng, seed, lanes, rl_before, w=None, eps=None, game="ledu
                 rows = torch.tensor((rl_before[p] + pre[L, p] + np.arange(n)) % m["log_cap"],
                                     dtype=torch.int64, device=m["rl_s"].device)
                 exp = ref["rl"][p]
-                assert np.array_equal(_bits_dev(m["rl_s"][rows]), [e[0] for e in exp]), (L, p)
-                assert np.array_equal(_bits_dev(m["rl_s2"][rows]), [e[3] for e in exp]), (L, p)
+                assert np.array_equal(obs_bits_dev(m["rl_s"][rows]), [e[0] for e in exp]), (L, p)
+                assert np.array_equal(obs_bits_dev(m["rl_s2"][rows]), [e[3] for e in exp]), (L, p)
                 assert np.abs(m["rl_a"][rows].cpu().numpy() - np.array([e[1] for e in exp])).max() <= 1e-6
                 assert np.array_equal(m["rl_r"][rows].cpu().numpy(), np.array([e[2] for e in exp], np.float32))
             k = len(ref["sl"][p])
@@ -120,7 +119,7 @@ def test_c3_sliced_rollouts_replay_on_the_oracle(pkg):
         before = tuple(int(v) for v in eng.stats()["rl_total"])
         eng.rollout()
         assert eng.last_slice() == (k * S, 1)
-        _check_slice_lanes(eng, seed, _sample_lanes(S, 48, 10 + k), before)
+        _check_slice_lanes(eng, seed, sample_lanes(S, 48, 10 + k), before)
         eng.update()
 
 
@@ -134,7 +133,7 @@ def test_pipelined_slices_act_with_the_nets_two_slices_back(pkg, K):
     eng = pkg.engine.SelfPlayEngine(seed=seed, init_seed=5, slices=K, slice_lag=2,
                                     n_lanes=262_144, rl_capacity=200_000, sl_capacity=2_000_000)
     eng.step()                                     # the learner has trained
-    w_start = _weights_flat(eng)
+    w_start = weights_flat(eng)
     eps_start = tuple(float(v) for v in eng.stats()["epsilon"])
     eng.step()
     st = eng.stats()
@@ -146,10 +145,10 @@ def test_pipelined_slices_act_with_the_nets_two_slices_back(pkg, K):
         w, eps = eng.snapshot((K - 1) & 1)
         assert not np.array_equal(w, w_start)      # trained past the step's start
     # the acting nets are not the final ones: the last slices' learners ran after they acted
-    assert not np.array_equal(w.reshape(2, 3, -1)[:, :2], _weights_flat(eng).reshape(2, 3, -1)[:, :2])
+    assert not np.array_equal(w.reshape(2, 3, -1)[:, :2], weights_flat(eng).reshape(2, 3, -1)[:, :2])
     assert eng.last_slice() == ((K - 1) * eng.slice_lanes, 1)
     before = tuple(int(st["rl_total"][p] - st["last_rl"][p]) for p in (0, 1))
-    _check_slice_lanes(eng, seed, _sample_lanes(eng.slice_lanes, 48, 20 + K), before, w, eps)
+    _check_slice_lanes(eng, seed, sample_lanes(eng.slice_lanes, 48, 20 + K), before, w, eps)
 
 
 def test_pipelined_snapshot_keeps_the_epsilon_its_slice_acted_with(pkg):
@@ -188,7 +187,7 @@ def test_kuhn_textbook_pipelined_slices_replay_on_the_oracle(pkg):
     w, eps = eng.snapshot((K - 1) & 1)
     assert eng.last_slice() == ((K - 1) * eng.slice_lanes, 1)
     before = tuple(int(st["rl_total"][p] - st["last_rl"][p]) for p in (0, 1))
-    _check_slice_lanes(eng, seed, _sample_lanes(eng.slice_lanes, 48, 77), before, w, eps, game="kuhn")
+    _check_slice_lanes(eng, seed, sample_lanes(eng.slice_lanes, 48, 77), before, w, eps, game="kuhn")
 
 
 def test_pipelined_step_is_deterministic(pkg):
@@ -196,7 +195,7 @@ def test_pipelined_step_is_deterministic(pkg):
         e = pkg.engine.SelfPlayEngine(seed=808, init_seed=6, slices=16, slice_lag=2, **C3)
         e.step()
         e.step()
-        return e.stats(), _weights_flat(e)
+        return e.stats(), weights_flat(e)
     s1, w1 = run()
     torch.cuda.empty_cache()
     s2, w2 = run()
@@ -315,17 +314,17 @@ def test_pipelined_step_equals_its_declared_schedule(pkg):
     b = pkg.engine.SelfPlayEngine(slice_lag=1, **kw)
     for step in range(3):
         a.step()
-        snap = [_weights_flat(b)] * 2
+        snap = [weights_flat(b)] * 2
         eps = [tuple(float(v) for v in b.stats()["epsilon"])] * 2
         for j in range(K):
             b.rollout_with(snap[j & 1], eps[j & 1])
             b.update()
             if j + 2 < K:
-                snap[j & 1] = _weights_flat(b)
+                snap[j & 1] = weights_flat(b)
                 eps[j & 1] = tuple(float(v) for v in b.stats()["epsilon"])
         sa, sb = a.stats(), b.stats()
         assert sa == sb, (step, {k: (sa[k], sb[k]) for k in sa if sa[k] != sb[k]})
-        assert np.array_equal(_weights_flat(a), _weights_flat(b)), step
+        assert np.array_equal(weights_flat(a), weights_flat(b)), step
     assert min(sa["br_updates"]) > 50 and sa["target_syncs"][0] > 3
     for p in (0, 1):
         ma, mb = _logical_rl(a, p), _logical_rl(b, p)
@@ -350,13 +349,13 @@ def test_pipelined_loss_log_is_the_last_calls(pkg, n_lanes, K):
     seen = {"rl": False, "sl": False}
     for step in range(2):
         a.step()
-        snap = [_weights_flat(b)] * 2
+        snap = [weights_flat(b)] * 2
         eps = [tuple(float(v) for v in b.stats()["epsilon"])] * 2
         for j in range(K):
             b.rollout_with(snap[j & 1], eps[j & 1])
             b.update()
             if j + 2 < K:
-                snap[j & 1] = _weights_flat(b)
+                snap[j & 1] = weights_flat(b)
                 eps[j & 1] = tuple(float(v) for v in b.stats()["epsilon"])
         la, lb = a.losses(), b.losses()
         print(step, la)

@@ -154,7 +154,7 @@ def test_gpu_kuhn_exploitability_matches_oracle(pkg, mode):
 def test_gpu_kuhn_engine_rollout_matches_oracle(pkg):
     """The fused rollout with game = Kuhn against rollout_oracle's Kuhn lanes."""
     import rollout_oracle as R
-    from test_gpu_engine import check_rollout, weights_flat
+    from engine_ref import check_rollout, weights_flat
     N, seed = 2000, 99
     eng = pkg.engine.SelfPlayEngine(n_lanes=N, seed=seed, init_seed=4, eta=0.3, inserts_per_update=1 << 30,
                                     game=pkg.native.GAME_KUHN)

@@ -1,8 +1,26 @@
 // Reference SGD chain for tools/bench_chain.hip's agreement check: the previous
 // production kernel (hidden split over 4 waves, layer-1 forward and dW1 as chained
 // v_mfma_f32_16x16x4_f32, exact f32), reading plain fit rows.  Not part of libnfsp.
-// Included by bench_chain.hip after learner.hip (uses its dpp / permlane helpers).
+// Included by bench_chain.hip after learner.hip (uses its permlane helpers).
 namespace chainref {
+
+__device__ inline float dpp_f(float x, int ctrl) {
+  switch (ctrl) {   // the control word must be an immediate
+    case 0x128: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xF, 0xF, false));
+    case 0xB1: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, false));
+    case 0x4E: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xF, 0xF, false));
+    default: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x141, 0xF, 0xF, false));
+  }
+}
+
+__device__ inline float dpp_any(float x, int ctrl) {
+  switch (ctrl) {
+    case 0x121: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x121, 0xF, 0xF, false));
+    case 0x122: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x122, 0xF, 0xF, false));
+    case 0x124: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x124, 0xF, 0xF, false));
+    default: return dpp_f(x, ctrl);
+  }
+}
 
 struct __attribute__((aligned(16))) FitRow {   // observation bits + 3 fit targets
   uint32_t x;

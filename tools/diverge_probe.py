@@ -14,7 +14,7 @@ for p in (REPO, os.path.join(REPO, "oracle"), os.path.join(REPO, "tests")):
 import torch  # noqa: E402
 
 import learner_oracle as LO  # noqa: E402
-from test_gpu_configs import C2, _oracle_cfg, _snapshot  # noqa: E402
+from engine_ref import C2, learner_state, oracle_cfg  # noqa: E402
 
 
 def engine_at(pkg, k):
@@ -22,7 +22,7 @@ def engine_at(pkg, k):
     for _ in range(6):
         eng.step()
     eng.rollout()
-    st, state = _snapshot(eng)
+    st, state = learner_state(eng)
     if k is not None:
         eng.set_update_limit(k)
     eng.update()
@@ -35,7 +35,7 @@ def main():
     pkg = __graft_entry__.load_package()
     e0, state = engine_at(pkg, None)
     tr = {}
-    LO.learner_step(_oracle_cfg(e0.cfg), state,
+    LO.learner_step(oracle_cfg(e0.cfg), state,
                     trace=lambda a, n, u, w: tr.__setitem__((a, n, u), w))
     out = []
     for k in (1, 2, 5, 10, 25, 50, 100, 200, 300, 400, 500):
@@ -59,7 +59,7 @@ def detail():
     import __graft_entry__
     pkg = __graft_entry__.load_package()
     eng, state = engine_at(pkg, None)
-    want = LO.learner_step(_oracle_cfg(eng.cfg), state)
+    want = LO.learner_step(oracle_cfg(eng.cfg), state)
     obs = np.unique(np.concatenate([state[a]["rl_s2_bits"] for a in (0, 1)]))
     x = LO.bits_to_x(obs)
     for a in (0, 1):
