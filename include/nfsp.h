@@ -720,6 +720,57 @@ int nfsp_xfp_state(nfsp_xfp* h, int run, double* host_S /*[ndec][3][3]*/, double
                    double* W);
 int nfsp_xfp_destroy(nfsp_xfp* h);
 
+/* ---- the memories as tables (csrc/memtab.hip k_memtab, k_memtab_sum) ----
+ * M_SL (utils/ReservoirBuffer.py:18-28) and M_RL (utils/replay_buffer.py:30-41) counted per
+ * information set where they lie, from the packed device records (SlRec 16 B {obs bits, a[3]},
+ * RlRec 32 B {s, s2, argmax | t << 8 | r << 16, a[3], pad}).  The reference can
+ * only sample its memories; M_SL per information set IS NFSP's tabular average strategy, and the
+ * AR net a fit of it.
+ * A record belongs to (seat, observation), one (row, rank) of nfsp_tree_export's rows; agent i
+ * is seat i.  out[ndec][3 ranks][3 actions][3 fields], int64 -- integers only, so the bits do not
+ * depend on the order of accumulation:
+ *   NFSP_MEM_SL  [k][0] records of the set whose argmax3(a) is k (the rollout's first-maximum
+ *                rule, before the raise-to-call remap); [k][1] the sum over ALL records of the set
+ *                of fix(a_k); [k][2] 0
+ *   NFSP_MEM_RL  [k][0] records of the set whose stored argmax (meta & 0xff) is k; [k][1] the sum
+ *                of their r in half units (the int8 in meta); [k][2] how many of them have t set.
+ *                The key is the stored s: under NFSP_QUIRK_ALIAS_RL the stored s and a of every
+ *                tuple of a hand are that hand's LAST ones, and the table reports
+ *                the records as stored.  A stored argmax above 2 matches no information set.
+ * fix(x) = rint((double)x * 2^NFSP_MEMTAB_FIX_SHIFT) as int64, ties to even: exact for one-hot rows
+ * and for the 24-bit uniform draws.  A component with |x| >= 256 or not finite is saturated to
+ * +-(2^32 - 1) (NaN: 0) and counted in `clamped`, so with fewer than 2^31 records per table no sum
+ * overflows; more are NFSP_EINVAL.
+ * A call for `seat` writes every value of every row where that seat acts and leaves the other
+ * seat's rows untouched: two calls into one buffer give the joint table.  Records whose observation
+ * is no information set of the seat add to `unmatched` only.  Every call synchronises its stream. */
+#define NFSP_MEM_SL 0
+#define NFSP_MEM_RL 1
+#define NFSP_MEMTAB_FIX_SHIFT 24
+#define NFSP_MEMTAB_MAX_SEGMENTS 8
+typedef struct { const void* dev_recs; int64_t n; } nfsp_mem_segment;   /* packed SlRec (16 B) / RlRec (32 B), 16-byte aligned */
+typedef struct { int64_t records, matched, unmatched, clamped; } nfsp_memtab_info;
+/* Host only: row * 3 + rank of the information set in which `seat` observes `obs`, -1 if there is
+ * none -- read from the very lookup table the kernel stages. */
+int nfsp_memtab_lookup(int game, int seat, uint32_t obs);
+/* Host only: fix(x), the one host definition (the kernel shares its source). */
+int64_t nfsp_memtab_fix(float x);
+/* Raw form: the records of up to NFSP_MEMTAB_MAX_SEGMENTS device segments, on the ctx stream. */
+int nfsp_memory_table(nfsp_ctx* ctx, int game, int kind, int seat, const nfsp_mem_segment* segs, int nsegs,
+                      int64_t* dev_out, nfsp_memtab_info* info);
+/* An engine's memories, both agents in one launch into the joint table: M_SL rows [0, sl_size),
+ * the live M_RL records as the at most two pieces of the circular log.  Requires what
+ * nfsp_engine_state_digest requires (a step boundary, so no pending M_SL list; else NFSP_EINVAL)
+ * and synchronises the engine's streams first.  A group replica's handle is accepted. */
+int nfsp_engine_memory_table(nfsp_engine* e, int kind, int64_t* dev_out /*[ndec][3][3][3]*/,
+                             nfsp_memtab_info info[2]);
+/* Every replica's joint table in ONE launch, through a device job table (2R jobs). */
+int nfsp_group_memory_tables(nfsp_group* g, int kind, int64_t* dev_out /*[R][ndec][3][3][3]*/,
+                             nfsp_memtab_info* info /*[R][2]*/);
+/* The two kernels' time in this thread's last table call (HIP events around them): how
+ * profiles/memtab/ was measured. */
+int nfsp_memtab_last_ms(double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 // Internals shared by rollout.hip (rollout, insert), engine.hip (lifecycle, introspection),
 // learner.hip (the learner's kernels and launchers), engine_update.hip (one engine's learner
-// call), group.hip (engine groups) and state.hip.
+// call), group.hip (engine groups), state.hip and memtab.hip (the memories as tables).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -348,6 +348,17 @@ struct GroupState {
   int n_streams;
 };
 int group_state(nfsp_group* g, GroupState* out);
+// What reads the memories where they lie shares with the digest (state.hip): the engine (group)
+// at a step boundary with its streams idle -- anything else is NFSP_EINVAL naming `what` -- its
+// EngineDev read back, and an agent's live M_RL records as the at most two pieces (first row,
+// rows) of its circular log, oldest first.
+int engine_quiesce(nfsp_engine* e, const char* what, EngineDev* h);
+int group_quiesce(nfsp_group* g, const char* what, GroupState* G, std::vector<EngineDev>* h);
+struct RlPieces {
+  int n = 0;
+  int64_t row[2], len[2];
+};
+RlPieces rl_live_pieces(const nfsp_engine* e, const EngineDev& h, int a);
 
 // RAII bracket: records start/stop events around launches on `stream` when timing is on
 struct KTimer {

@@ -1,0 +1,466 @@
+// M_SL / M_RL tabulated per information set on the device (include/nfsp.h nfsp_memory_table,
+// nfsp_engine_memory_table, nfsp_group_memory_tables).
+//
+// A record belongs to (seat, observation) = one (row, rank) of the evaluator's tree
+// (exploit_tree.h).  Per game and seat the host builds an open-addressing table observation ->
+// sid = 3 x (the seat's compact row) + rank from HostTables; k_memtab stages the seat's table to
+// LDS, reads every record once (one 16-byte load: an M_RL record's key, argmax, t and r all sit
+// in its first half) and adds into LDS bins [sid][action][field], int64, one copy per workgroup,
+// with plain LDS adds (ds_add_u64): neither a copy per wave nor folding the lanes of a wave that
+// share a key paid (DESIGN.md §9 has the measurement).  A workgroup writes its bins with plain
+// stores and k_memtab_sum adds the workgroups' partials: integers only and no global atomics,
+// so every order of accumulation gives the same bits.
+//
+// One launch serves any number of tables (a seat of an engine or of a group's replica each)
+// through a device job table, as the chains' ChainJob does.
+#include <math.h>
+
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "engine_internal.h"
+#include "exploit_tree.h"
+
+using namespace nfsp::eng;
+
+namespace {
+
+constexpr int MT_H = 1024;              // hash slots per seat (Leduc: 195 keys)
+constexpr int MT_HSHIFT = 22;           // 32 - log2(MT_H)
+constexpr uint32_t MT_EMPTY = 0xFFFFFFFFu;   // no observation has bits 30, 31
+constexpr int MT_MAX_ROWS = 128;        // decision rows of one seat (Leduc: 65)
+constexpr int MT_MAX_SEG = 8;
+constexpr int MT_WG = 1024;             // 16 waves
+constexpr int MT_U = 4;                 // records per lane in flight
+constexpr int MT_BLOCKS = 512;          // 2 workgroups per CU of an MI355X
+constexpr int MT_LDS_MAX = 64 * 1024;
+constexpr int64_t MT_SAT = 4294967295ll;   // 2^32 - 1
+
+static_assert(sizeof(SlRec) == 16 && sizeof(RlRec) == 32, "record layout");
+static_assert(1 << (32 - MT_HSHIFT) == MT_H, "hash width");
+
+__host__ __device__ inline uint32_t mt_hash(uint32_t x) { return (x * 0x9E3779B1u) >> MT_HSHIFT; }
+
+// fix(x) = rint(x * 2^24), ties to even; |x| >= 256 or not finite saturates (NaN: 0) and counts
+__host__ __device__ inline int64_t mt_fix(float x, int& clamped) {
+  if (!(fabsf(x) < 256.f)) {
+    ++clamped;
+    return x != x ? 0 : x > 0.f ? MT_SAT : -MT_SAT;
+  }
+  return (int64_t)rint((double)x * (double)(1 << NFSP_MEMTAB_FIX_SHIFT));
+}
+
+// ---------------------------------------------------------------------------
+// host: the lookup of a game
+// ---------------------------------------------------------------------------
+struct MtHost {
+  int ndec = 0;
+  int nrows[2] = {0, 0};
+  int32_t rows[2][MT_MAX_ROWS];          // the seat's compact row -> decision row
+  uint32_t keys[2][MT_H];
+  uint16_t vals[2][MT_H];                // sid = 3 x compact row + rank
+};
+
+int mt_host(int game, const MtHost** out) {
+  static std::mutex mu;
+  static std::map<int, MtHost> cache;
+  const nfsp::ex::HostTables* H = nullptr;
+  int rc = nfsp::ex::host_tables(game, &H);
+  if (rc != NFSP_OK) return rc;
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = cache.find(game);
+  if (it == cache.end()) {
+    MtHost M;
+    M.ndec = (int)H->legal.size();
+    for (int s = 0; s < 2; ++s)
+      for (int h = 0; h < MT_H; ++h) {
+        M.keys[s][h] = MT_EMPTY;
+        M.vals[s][h] = 0;
+      }
+    for (int d = 0; d < M.ndec; ++d) {
+      const int s = H->legal[d] >> 1;
+      NFSP_REQUIRE((s == 0 || s == 1) && M.nrows[s] < MT_MAX_ROWS && 6 * (M.nrows[s] + 1) <= MT_H,
+                   "memory table: the tree has more rows per seat than the lookup holds");
+      const int c = M.nrows[s]++;
+      M.rows[s][c] = d;
+      for (int r = 0; r < 3; ++r) {
+        const uint32_t x = H->obs[(size_t)d * 3 + r];
+        uint32_t h = mt_hash(x);
+        while (M.keys[s][h] != MT_EMPTY) {
+          NFSP_REQUIRE(M.keys[s][h] != x, "memory table: two information sets of a seat share an observation");
+          h = (h + 1) & (MT_H - 1);
+        }
+        M.keys[s][h] = x;
+        M.vals[s][h] = (uint16_t)(c * 3 + r);
+      }
+    }
+    it = cache.emplace(game, M).first;
+  }
+  *out = &it->second;
+  return NFSP_OK;
+}
+
+// sid of (seat, obs), -1: none.  The table is at most a third full, so a probe ends.
+__host__ __device__ inline int mt_find(const uint32_t* keys, const uint16_t* vals, uint32_t x) {
+  uint32_t h = mt_hash(x);
+  for (int n = 0; n < MT_H; ++n) {
+    const uint32_t k = keys[h];
+    if (k == x) return vals[h];
+    if (k == MT_EMPTY) return -1;
+    h = (h + 1) & (MT_H - 1);
+  }
+  return -1;
+}
+
+// ---------------------------------------------------------------------------
+// device
+// ---------------------------------------------------------------------------
+struct MtTab {                            // one table: a seat's records in up to MT_MAX_SEG pieces
+  const uint4* p[MT_MAX_SEG];             // 16-byte aligned
+  int64_t n[MT_MAX_SEG];                  // records
+  int64_t* out;                           // the joint table [ndec][3][3][3] the seat's rows go to
+  int32_t nseg, seat;
+};
+struct MtArgs {
+  const uint32_t* keys;                   // [2][MT_H]
+  const uint16_t* vals;                   // [2][MT_H]
+  const int32_t* rows;                    // [2][MT_MAX_ROWS]
+  const MtTab* tabs;
+  int64_t* partial;                       // [tables][nb][nvp]: bins, then matched, unmatched, clamped
+  int64_t* info;                          // [tables][4]
+  int32_t nb, nvp;
+  int32_t nrows[2];
+};
+
+__device__ inline int wave_sum(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ inline void lds_add(int64_t* p, int64_t v) {
+  if (v) atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
+}
+
+// One record (sid >= 0) into the bins.  SL: val = fix(a), the count goes to action k.  RL:
+// val[0] = r in half units, val[1] = t, both to k.
+template <int KIND>
+__device__ inline void mt_accum(int64_t* bins, int sid, int k, const int64_t val[3]) {
+  constexpr int NF = KIND == NFSP_MEM_SL ? 2 : 3;
+  int64_t* b = bins + sid * 3 * NF;
+  lds_add(b + k * NF + 0, 1);
+  if (KIND == NFSP_MEM_SL) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) lds_add(b + j * NF + 1, val[j]);
+  } else {
+    lds_add(b + k * NF + 1, val[0]);
+    lds_add(b + k * NF + 2, val[1]);
+  }
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(MT_WG) k_memtab(MtArgs A) {
+  extern __shared__ int64_t mt_lds[];
+  constexpr int NF = KIND == NFSP_MEM_SL ? 2 : 3;
+  constexpr int RQ = KIND == NFSP_MEM_SL ? 1 : 2;      // 16-byte words per record
+  const MtTab& T = A.tabs[blockIdx.y];
+  const int seat = T.seat;
+  const int nv = A.nrows[seat] * 9 * NF;
+  int64_t* bins = mt_lds;                              // [nv]
+  int64_t* ctr = bins + nv;                            // matched, unmatched, clamped
+  uint32_t* hk = reinterpret_cast<uint32_t*>(ctr + 4);
+  uint16_t* hv = reinterpret_cast<uint16_t*>(hk + MT_H);
+  for (int v = threadIdx.x; v < nv + 4; v += MT_WG) bins[v] = 0;
+  for (int h = threadIdx.x; h < MT_H; h += MT_WG) {
+    hk[h] = A.keys[seat * MT_H + h];
+    hv[h] = A.vals[seat * MT_H + h];
+  }
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t gw = (int64_t)blockIdx.x * (MT_WG / 64) + wave, nw = (int64_t)gridDim.x * (MT_WG / 64);
+  int matched = 0, unmatched = 0, clamped = 0;
+  for (int s = 0; s < T.nseg; ++s) {
+    const uint4* __restrict__ p = T.p[s];
+    const int64_t n = T.n[s];
+    // a wave takes 64 * MT_U consecutive records per turn: the bound is the wave's, not the lane's
+    for (int64_t base = gw * (64 * MT_U); base < n; base += nw * (64 * MT_U)) {
+      uint4 rec[MT_U];
+#pragma unroll
+      for (int u = 0; u < MT_U; ++u) {
+        const int64_t k = base + u * 64 + lane;
+        rec[u] = k < n ? p[k * RQ] : make_uint4(MT_EMPTY, 0, 3, 0);    // neither a key nor an action
+      }
+#pragma unroll
+      for (int u = 0; u < MT_U; ++u) {
+        const bool valid = base + u * 64 + lane < n;
+        int sid = valid ? mt_find(hk, hv, rec[u].x) : -1;
+        int k = 0;
+        int64_t val[3] = {0, 0, 0};
+        if (KIND == NFSP_MEM_SL) {
+          if (sid >= 0) {
+            const float a0 = __uint_as_float(rec[u].y), a1 = __uint_as_float(rec[u].z), a2 = __uint_as_float(rec[u].w);
+            k = nfsp::argmax3(a0, a1, a2);
+            val[0] = mt_fix(a0, clamped);
+            val[1] = mt_fix(a1, clamped);
+            val[2] = mt_fix(a2, clamped);
+          }
+        } else {
+          k = (int)(rec[u].z & 0xFFu);
+          if (k > 2) sid = -1;                          // not a stored argmax: no bin
+          val[0] = (int8_t)(rec[u].z >> 16);
+          val[1] = (rec[u].z >> 8) & 1u;
+        }
+        matched += sid >= 0;
+        unmatched += valid && sid < 0;
+        if (sid >= 0) mt_accum<KIND>(bins, sid, k, val);
+      }
+    }
+  }
+  matched = wave_sum(matched);
+  unmatched = wave_sum(unmatched);
+  clamped = wave_sum(clamped);
+  if (lane == 0) {
+    lds_add(ctr + 0, matched);
+    lds_add(ctr + 1, unmatched);
+    lds_add(ctr + 2, clamped);
+  }
+  __syncthreads();
+  int64_t* out = A.partial + ((int64_t)blockIdx.y * A.nb + blockIdx.x) * A.nvp;
+  for (int v = threadIdx.x; v < nv; v += MT_WG) out[v] = bins[v];
+  if (threadIdx.x < 3) out[A.nvp - 3 + threadIdx.x] = ctr[threadIdx.x];
+}
+
+// The partials of table blockIdx.y -> the seat's rows of the joint table (every value of every
+// such row is written; field 2 of an M_SL table is 0) and its info.  A workgroup owns 64
+// consecutive values; its 16 waves each add every 16th block's partial (512-byte rows, so the
+// loads coalesce) and wave 0 adds the 16 sums.  One workgroup per table looping over all of its
+// partials measured 0.4 ms at C3 size: 20 times the read of the records.
+__global__ void __launch_bounds__(MT_WG) k_memtab_sum(MtArgs A, int kind) {
+  __shared__ int64_t red[MT_WG / 64][64];
+  const MtTab& T = A.tabs[blockIdx.y];
+  const int seat = T.seat, NF = kind == NFSP_MEM_SL ? 2 : 3;
+  const int nv = A.nrows[seat] * 9 * NF;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int j = blockIdx.x * 64 + lane;                    // [0, nv): a bin; [nv, nv + 3): the info
+  const bool valid = j < nv + 3;
+  const int64_t* part = A.partial + (int64_t)blockIdx.y * A.nb * A.nvp + (j < nv ? j : valid ? A.nvp - 3 + (j - nv) : 0);
+  int64_t s = 0;
+  if (valid)
+    for (int b = wave; b < A.nb; b += MT_WG / 64) s += part[(int64_t)b * A.nvp];
+  red[wave][lane] = s;
+  __syncthreads();
+  if (wave == 0 && valid) {
+    for (int w = 1; w < MT_WG / 64; ++w) s += red[w][lane];
+    if (j < nv) {
+      const int sid = j / (3 * NF), k = (j / NF) % 3, f = j % NF;
+      int64_t* o = T.out + ((int64_t)A.rows[seat * MT_MAX_ROWS + sid / 3] * 3 + sid % 3) * 9 + k * 3;
+      o[f] = s;
+      if (NF == 2 && f == 1) o[2] = 0;
+    } else {
+      A.info[blockIdx.y * 4 + 1 + (j - nv)] = s;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// host: per-device tables and workspace, the launch
+// ---------------------------------------------------------------------------
+struct MtDev {
+  uint32_t* keys = nullptr;
+  uint16_t* vals = nullptr;
+  int32_t* rows = nullptr;
+};
+struct MtWork {
+  char* buf = nullptr;
+  size_t cap = 0;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+};
+std::mutex g_mu;                          // a call holds it from its first launch to its last copy
+std::map<std::pair<int, int>, MtDev> g_dev;
+std::map<int, MtWork> g_work;
+thread_local double g_last_ms = 0.0;
+
+int mt_device(int dev, int game, const MtHost& M, MtDev* out) {
+  auto it = g_dev.find({dev, game});
+  if (it == g_dev.end()) {
+    MtDev D;
+    NFSP_HIP(hipMalloc((void**)&D.keys, sizeof(M.keys)));
+    NFSP_HIP(hipMalloc((void**)&D.vals, sizeof(M.vals)));
+    NFSP_HIP(hipMalloc((void**)&D.rows, sizeof(M.rows)));
+    NFSP_HIP(hipMemcpy(D.keys, M.keys, sizeof(M.keys), hipMemcpyHostToDevice));
+    NFSP_HIP(hipMemcpy(D.vals, M.vals, sizeof(M.vals), hipMemcpyHostToDevice));
+    NFSP_HIP(hipMemcpy(D.rows, M.rows, sizeof(M.rows), hipMemcpyHostToDevice));
+    it = g_dev.emplace(std::make_pair(dev, game), D).first;
+  }
+  *out = it->second;
+  return NFSP_OK;
+}
+
+// The tables of `tabs` (their `out` set) on `st`; info[t] filled; synchronises st.
+int mt_run(hipStream_t st, int game, int kind, std::vector<MtTab>& tabs, nfsp_memtab_info* info) {
+  const int nt = (int)tabs.size();
+  if (nt == 0) return NFSP_OK;
+  const MtHost* M = nullptr;
+  int rc = mt_host(game, &M);
+  if (rc != NFSP_OK) return rc;
+  int64_t maxn = 0;
+  std::vector<int64_t> total(nt, 0);
+  for (int t = 0; t < nt; ++t) {
+    for (int s = 0; s < tabs[t].nseg; ++s) total[t] += tabs[t].n[s];
+    NFSP_REQUIRE(total[t] < (1ll << 31), "memory table: 2^31 records or more in one table");
+    maxn = total[t] > maxn ? total[t] : maxn;
+  }
+  const int NF = kind == NFSP_MEM_SL ? 2 : 3;
+  const int nrmax = M->nrows[0] > M->nrows[1] ? M->nrows[0] : M->nrows[1];
+  const int nvp = nrmax * 9 * NF + 3;
+  const size_t lds = sizeof(int64_t) * ((size_t)(nvp - 3) + 4) + MT_H * (sizeof(uint32_t) + sizeof(uint16_t));
+  NFSP_REQUIRE(lds <= (size_t)MT_LDS_MAX, "memory table: the bins do not fit the workgroup's LDS");
+  int64_t nb = (maxn + (int64_t)MT_WG * MT_U * 2 - 1) / ((int64_t)MT_WG * MT_U * 2);
+  const int64_t cap = MT_BLOCKS / nt > 1 ? MT_BLOCKS / nt : 1;
+  nb = nb < 1 ? 1 : nb > cap ? cap : nb;
+
+  int dev = 0;
+  NFSP_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(g_mu);
+  MtDev D;
+  if ((rc = mt_device(dev, game, *M, &D)) != NFSP_OK) return rc;
+  MtWork& W = g_work[dev];
+  const size_t b_tabs = (sizeof(MtTab) * nt + 15) & ~(size_t)15, b_info = sizeof(int64_t) * 4 * nt;
+  const size_t need = b_tabs + b_info + sizeof(int64_t) * (size_t)nt * nb * nvp;
+  if (W.cap < need) {
+    if (W.buf) NFSP_HIP(hipFree(W.buf));
+    W.buf = nullptr;
+    W.cap = 0;
+    NFSP_HIP(hipMalloc((void**)&W.buf, need));
+    W.cap = need;
+  }
+  for (hipEvent_t& ev : W.ev)
+    if (!ev) NFSP_HIP(hipEventCreate(&ev));
+  MtArgs A{};
+  A.keys = D.keys;
+  A.vals = D.vals;
+  A.rows = D.rows;
+  A.tabs = reinterpret_cast<const MtTab*>(W.buf);
+  A.info = reinterpret_cast<int64_t*>(W.buf + b_tabs);
+  A.partial = reinterpret_cast<int64_t*>(W.buf + b_tabs + b_info);
+  A.nb = (int32_t)nb;
+  A.nvp = nvp;
+  A.nrows[0] = M->nrows[0];
+  A.nrows[1] = M->nrows[1];
+  NFSP_HIP(hipMemcpyAsync(W.buf, tabs.data(), sizeof(MtTab) * nt, hipMemcpyHostToDevice, st));
+  NFSP_HIP(hipEventRecord(W.ev[0], st));
+  const dim3 grid((unsigned)nb, (unsigned)nt);
+  if (kind == NFSP_MEM_SL) k_memtab<NFSP_MEM_SL><<<grid, MT_WG, lds, st>>>(A);
+  else k_memtab<NFSP_MEM_RL><<<grid, MT_WG, lds, st>>>(A);
+  NFSP_LAUNCHED("k_memtab");
+  k_memtab_sum<<<dim3((unsigned)((nvp + 63) / 64), (unsigned)nt), MT_WG, 0, st>>>(A, kind);
+  NFSP_LAUNCHED("k_memtab_sum");
+  NFSP_HIP(hipEventRecord(W.ev[1], st));
+  std::vector<int64_t> h((size_t)4 * nt);
+  NFSP_HIP(hipMemcpyAsync(h.data(), A.info, b_info, hipMemcpyDeviceToHost, st));
+  NFSP_HIP(hipStreamSynchronize(st));
+  float ms = 0.f;
+  NFSP_HIP(hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
+  g_last_ms = ms;
+  for (int t = 0; t < nt; ++t)
+    if (info) info[t] = nfsp_memtab_info{total[t], h[4 * t + 1], h[4 * t + 2], h[4 * t + 3]};
+  return NFSP_OK;
+}
+
+int mt_seg(MtTab& T, const void* p, int64_t n) {
+  if (n <= 0) return NFSP_OK;
+  NFSP_REQUIRE(T.nseg < MT_MAX_SEG, "memory table: too many segments");
+  T.p[T.nseg] = static_cast<const uint4*>(p);
+  T.n[T.nseg++] = n;
+  return NFSP_OK;
+}
+
+// agent a's table of an engine at a step boundary (h: its EngineDev)
+int mt_engine_tab(nfsp_engine* e, const EngineDev& h, int kind, int a, int64_t* out, MtTab* T) {
+  *T = MtTab{};
+  T->seat = a;
+  T->out = out;
+  if (kind == NFSP_MEM_SL) return mt_seg(*T, e->M.sl + a * e->M.sl_cap, h.sl_count[a]);
+  const RlPieces pc = rl_live_pieces(e, h, a);
+  for (int k = 0; k < pc.n; ++k) {
+    int rc = mt_seg(*T, e->M.rl + a * e->M.log_cap + pc.row[k], pc.len[k]);
+    if (rc != NFSP_OK) return rc;
+  }
+  return NFSP_OK;
+}
+
+bool kind_ok(int kind) { return kind == NFSP_MEM_SL || kind == NFSP_MEM_RL; }
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------
+extern "C" int nfsp_memtab_lookup(int game, int seat, uint32_t obs) {
+  const MtHost* M = nullptr;
+  if (mt_host(game, &M) != NFSP_OK || (seat != 0 && seat != 1)) return -1;
+  const int sid = mt_find(M->keys[seat], M->vals[seat], obs);
+  return sid < 0 ? -1 : M->rows[seat][sid / 3] * 3 + sid % 3;
+}
+
+extern "C" int64_t nfsp_memtab_fix(float x) {
+  int clamped = 0;
+  return mt_fix(x, clamped);
+}
+
+extern "C" int nfsp_memtab_last_ms(double* ms) {
+  NFSP_REQUIRE(ms, "null argument");
+  *ms = g_last_ms;
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_memory_table(nfsp_ctx* ctx, int game, int kind, int seat, const nfsp_mem_segment* segs, int nsegs,
+                                 int64_t* dev_out, nfsp_memtab_info* info) {
+  NFSP_REQUIRE(ctx && dev_out && (segs || nsegs == 0), "null argument");
+  NFSP_REQUIRE(kind_ok(kind) && (seat == 0 || seat == 1), "memory table: bad kind or seat");
+  NFSP_REQUIRE(nsegs >= 0 && nsegs <= NFSP_MEMTAB_MAX_SEGMENTS, "memory table: too many segments");
+  std::vector<MtTab> tabs(1);
+  tabs[0].seat = seat;
+  tabs[0].out = dev_out;
+  int64_t total = 0;
+  for (int s = 0; s < nsegs; ++s) {
+    NFSP_REQUIRE(segs[s].n >= 0 && (segs[s].dev_recs || segs[s].n == 0), "memory table: bad segment");
+    NFSP_REQUIRE(((uintptr_t)segs[s].dev_recs & 15u) == 0, "memory table: records must be 16-byte aligned");
+    NFSP_REQUIRE(segs[s].n < (1ll << 31) && (total += segs[s].n) < (1ll << 31),
+                 "memory table: 2^31 records or more in one table");
+    int rc = mt_seg(tabs[0], segs[s].dev_recs, segs[s].n);
+    if (rc != NFSP_OK) return rc;
+  }
+  return mt_run(ctx->stream, game, kind, tabs, info);
+}
+
+extern "C" int nfsp_engine_memory_table(nfsp_engine* e, int kind, int64_t* dev_out, nfsp_memtab_info info[2]) {
+  NFSP_REQUIRE(e && dev_out, "null argument");
+  NFSP_REQUIRE(kind_ok(kind), "memory table: bad kind");
+  EngineDev h;
+  int rc = engine_quiesce(e, "nfsp_engine_memory_table", &h);
+  if (rc != NFSP_OK) return rc;
+  std::vector<MtTab> tabs(2);
+  for (int a = 0; a < 2; ++a)
+    if ((rc = mt_engine_tab(e, h, kind, a, dev_out, &tabs[a])) != NFSP_OK) return rc;
+  return mt_run(e->ctx->stream, e->ctx->game, kind, tabs, info);
+}
+
+extern "C" int nfsp_group_memory_tables(nfsp_group* g, int kind, int64_t* dev_out, nfsp_memtab_info* info) {
+  NFSP_REQUIRE(g && dev_out, "null argument");
+  NFSP_REQUIRE(kind_ok(kind), "memory table: bad kind");
+  GroupState G;
+  std::vector<EngineDev> h;
+  int rc = group_quiesce(g, "nfsp_group_memory_tables", &G, &h);
+  if (rc != NFSP_OK) return rc;
+  const MtHost* M = nullptr;
+  if ((rc = mt_host(G.ctx->game, &M)) != NFSP_OK) return rc;
+  std::vector<MtTab> tabs((size_t)2 * G.R);
+  for (int r = 0; r < G.R; ++r)
+    for (int a = 0; a < 2; ++a)
+      if ((rc = mt_engine_tab(G.eng[r], h[r], kind, a, dev_out + (int64_t)r * M->ndec * 27, &tabs[2 * r + a])) != NFSP_OK)
+        return rc;
+  return mt_run(G.ctx->stream, G.ctx->game, kind, tabs, info);
+}

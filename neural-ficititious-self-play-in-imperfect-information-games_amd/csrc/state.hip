@@ -710,6 +710,38 @@ int group_read(const GroupState& G, std::vector<EngineDev>* h, uint64_t* total) 
 }
 }  // namespace
 
+// ---- for the other readers of the memories in place (memtab.hip)
+namespace nfsp {
+namespace eng {
+int engine_quiesce(nfsp_engine* e, const char* what, EngineDev* h) {
+  int rc = boundary_check(e, what);
+  if (rc != NFSP_OK) return rc;
+  if ((rc = engine_sync(e)) != NFSP_OK) return rc;
+  return read_st(e, h);
+}
+
+int group_quiesce(nfsp_group* g, const char* what, GroupState* G, std::vector<EngineDev>* h) {
+  int rc = group_state(g, G);
+  if (rc != NFSP_OK) return rc;
+  if ((rc = group_boundary(*G, what)) != NFSP_OK) return rc;
+  if ((rc = group_sync(*G)) != NFSP_OK) return rc;
+  uint64_t total = 0;
+  return group_read(*G, h, &total);
+}
+
+RlPieces rl_live_pieces(const nfsp_engine* e, const EngineDev& h, int a) {
+  const Pieces p = rl_pieces(h.rl_total[a], rl_live(h, e->cfg, a), e->M.log_cap);
+  RlPieces out;
+  out.n = p.n;
+  for (int k = 0; k < p.n; ++k) {
+    out.row[k] = p.row[k];
+    out.len[k] = p.len[k];
+  }
+  return out;
+}
+}  // namespace eng
+}  // namespace nfsp
+
 extern "C" int nfsp_group_state_bytes(nfsp_group* g, int64_t* out) {
   NFSP_REQUIRE(g && out, "null argument");
   GroupState G;

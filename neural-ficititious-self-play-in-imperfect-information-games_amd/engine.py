@@ -275,6 +275,34 @@ class SelfPlayEngine:
         opp = _opponents(self.ctx, self, 0, eta, tree)
         return ev.best_response(self.ctx, opp[0], opp[1], values, tree)
 
+    # -- the memories as tables ------------------------------------------
+    def memory_table(self, kind: int):
+        """``(evaluation.MemoryTable, [info of agent 0, of agent 1])`` of M_SL
+        (``native.MEM_SL``) or M_RL (``native.MEM_RL``), both agents in one launch on the packed
+        records where they lie (nfsp_engine_memory_table; step boundaries only)."""
+        from . import evaluation as ev
+        tree = ev.GameTree(self.ctx.game)
+        out = torch.empty((tree.ndec, 3, 3, 3), dtype=torch.int64, device=self.dev)
+        info = (native.MemtabInfo * 2)()
+        native.check(self.L.nfsp_engine_memory_table(self.h, int(kind), native.P(out.data_ptr()), info),
+                     "nfsp_engine_memory_table")
+        return ev.MemoryTable(tree, kind, out), [info[0].to_dict(), info[1].to_dict()]
+
+    def memory_report(self) -> dict:
+        """What the memories hold against what the nets make of them, all exact:
+        ``exploitability_ar`` (the AR nets, as ``exploitability()``), ``exploitability_sl_argmax``
+        / ``_sl_mass`` (M_SL's two tables, ``MemoryTable.policy``: sampling and BR quality without
+        function approximation), ``fit_gap_*`` = the nets' minus the tables' (what the 64-unit net
+        costs), ``sl_empty_sets`` (information sets without an M_SL record), ``rl_empty_actions``
+        ((information set, legal action) pairs without an M_RL record), ``ar_mass_l1`` (the mean
+        L1 distance between the AR nets' executed policy and the "mass" table, weighted by the
+        records per set) and both calls' infos per agent."""
+        from . import evaluation as ev
+        tree = ev.GameTree(self.ctx.game)
+        sl, si = self.memory_table(native.MEM_SL)
+        rl, ri = self.memory_table(native.MEM_RL)
+        return ev.memory_reports(self.ctx, [self], [sl], [rl], [(si, ri)], tree)[0]
+
     # -- checkpoints (checkpoint.py, DESIGN.md §10) ----------------------------------
     def save(self, path):
         """Save the engine at a step boundary (nfsp_engine_save_state); returns the bytes written."""
@@ -487,6 +515,32 @@ class EngineGroup:
         p1 = [e.policy(1, NET_AR, mode) for e in self.replicas]
         res = evaluation.evaluate_batch(self.ctx, [(a, b) for a in p0 for b in p1])
         return np.array([r["value0"] for r in res]).reshape(self.R, self.R)
+
+    def memory_tables(self, kind: int) -> list:
+        """Every replica's ``SelfPlayEngine.memory_table(kind)`` in one launch
+        (nfsp_group_memory_tables): ``[(MemoryTable, [info 0, info 1])]`` by replica."""
+        from . import evaluation as ev
+        tree = ev.GameTree(self.ctx.game)
+        out = torch.empty((self.R, tree.ndec, 3, 3, 3), dtype=torch.int64, device=self.replicas[0].dev)
+        info = (native.MemtabInfo * (2 * self.R))()
+        native.check(self.L.nfsp_group_memory_tables(self.h, int(kind), native.P(out.data_ptr()), info),
+                     "nfsp_group_memory_tables")
+        raw = out.cpu().numpy()
+        return [(ev.MemoryTable(tree, kind, raw[r]), [info[2 * r].to_dict(), info[2 * r + 1].to_dict()])
+                for r in range(self.R)]
+
+    def memory_report_all(self) -> list:
+        """``SelfPlayEngine.memory_report`` of every replica: one table launch per memory, and
+        one ``evaluate_batch`` per 64 replicas."""
+        from . import evaluation as ev
+        tree = ev.GameTree(self.ctx.game)
+        sl, rl = self.memory_tables(native.MEM_SL), self.memory_tables(native.MEM_RL)
+        out = []
+        for r0 in range(0, self.R, 64):
+            rs = range(r0, min(r0 + 64, self.R))
+            out += ev.memory_reports(self.ctx, [self.replicas[r] for r in rs], [sl[r][0] for r in rs],
+                                     [rl[r][0] for r in rs], [(sl[r][1], rl[r][1]) for r in rs], tree)
+        return out
 
     # -- checkpoints (checkpoint.py, DESIGN.md §10) ----------------------------------
     def save(self, path):

@@ -23,6 +23,10 @@ learned BR net deviates, and by how much.
 family anchors Kuhn.  ``XfpSolver`` runs full-width fictitious play on it (``nfsp_xfp_*``,
 csrc/xfp.hip), n runs over eta and the weighting at once: the curve of the algorithm NFSP
 approximates, with an exact best response and exact averaging.
+
+``MemoryTable`` is a memory counted per information set on the device (``nfsp_memory_table``,
+csrc/memtab.hip): M_SL as the tabular average strategy the AR net is a fit of, M_RL as what the
+BR net had to learn from; ``memory_reports`` scores the former beside the nets.
 """
 from __future__ import annotations
 
@@ -257,6 +261,125 @@ def best_response(ctx, seat0: Policy, seat1: Policy, values: bool = False, tree:
         native.P(q.data_ptr()) if values else None, native.P(reach.data_ptr()) if values else None),
         "nfsp_best_response_table")
     return (beta, q, reach) if values else beta
+
+
+class MemoryTable:
+    """A memory counted per information set (``nfsp_memory_table``): ``raw`` is the int64 array
+    ``[ndec, 3 ranks, 3 actions, 3 fields]`` over the rows of ``tree``.
+
+    ``kind`` ``native.MEM_SL``: field 0 the records whose argmax is the action, field 1 the sum of
+    the stored action vectors' component in 2^-24 units.  ``native.MEM_RL``: field 0 the records
+    whose stored argmax is the action, field 1 the sum of their rewards in half chips, field 2
+    how many of them are terminal.
+
+    ``counts[ndec, 3, 3]`` is field 0 and ``n[ndec, 3]`` the records per information set."""
+
+    def __init__(self, tree: GameTree, kind: int, raw):
+        self.tree = tree
+        self.kind = int(kind)
+        if hasattr(raw, "cpu"):
+            raw = raw.cpu().numpy()
+        self.raw = np.array(raw, np.int64).reshape(tree.ndec, 3, 3, 3)
+        self.counts = self.raw[..., 0]
+        self.n = self.counts.sum(axis=2)
+
+    def policy(self, how: str = "argmax") -> np.ndarray:
+        """The memory as a behavioural strategy, float64 ``[ndec, 3, 3]`` for ``Policy.table``:
+        "argmax" normalises the counts (the textbook NFSP average), "mass" the summed action
+        vectors (the exact minimiser of the AR net's cross-entropy).  A row without records (for
+        "mass": whose sum is 0) is ``tree.uniform()``'s row."""
+        if how not in ("argmax", "mass"):
+            raise ValueError('how must be "argmax" or "mass"')
+        if self.kind != native.MEM_SL and how == "mass":
+            raise ValueError('"mass" is defined for M_SL tables only')
+        w = self.raw[..., 0 if how == "argmax" else 1].astype(np.float64)
+        tot = w.sum(axis=2)
+        out = self.tree.uniform()
+        nz = tot != 0
+        out[nz] = w[nz] / tot[nz][:, None]
+        return out
+
+    def _rl(self):
+        if self.kind != native.MEM_RL:
+            raise AttributeError("mean_r / terminal belong to M_RL tables")
+
+    @property
+    def mean_r(self) -> np.ndarray:
+        """M_RL: the mean stored reward in chips per (row, rank, action); NaN without records."""
+        self._rl()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.counts > 0, self.raw[..., 1] / (2.0 * self.counts), np.nan)
+
+    @property
+    def terminal(self) -> np.ndarray:
+        """M_RL: the terminal records per (row, rank, action)."""
+        self._rl()
+        return self.raw[..., 2]
+
+
+def memory_table(ctx, kind: int, seat: int, records, out=None, tree: GameTree | None = None):
+    """``nfsp_memory_table``: packed device records (``SlRec`` 16 B / ``RlRec`` 32 B) of ``seat``
+    counted into the seat's rows of ``out``, an int64 device tensor ``[ndec, 3, 3, 3]`` (zeros
+    when not given; the other seat's rows are left as they are).  ``records``: one segment or a
+    list of them, each a contiguous device tensor of whole records or ``(device address, n)``.
+    Returns ``(out, info)``; ``MemoryTable(tree, kind, out)`` reads it."""
+    import torch
+    tree = tree or GameTree(ctx.game)
+    size = 16 if kind == native.MEM_SL else 32
+    if isinstance(records, torch.Tensor) or (isinstance(records, tuple) and isinstance(records[0], int)):
+        records = [records]
+    segs = []
+    for r in records:
+        if isinstance(r, torch.Tensor):
+            nbytes = r.numel() * r.element_size()
+            if not r.is_contiguous() or nbytes % size:
+                raise ValueError("a segment must be a contiguous tensor of whole records")
+            segs.append(native.MemSegment(native.P(r.data_ptr()), nbytes // size))
+        else:
+            segs.append(native.MemSegment(native.P(int(r[0])), int(r[1])))
+    if out is None:
+        out = torch.zeros((tree.ndec, 3, 3, 3), dtype=torch.int64, device="cuda")
+    arr = (native.MemSegment * max(len(segs), 1))(*segs)
+    info = native.MemtabInfo()
+    native.check(ctx.L.nfsp_memory_table(ctx.h, tree.game, int(kind), int(seat), arr, len(segs),
+                                         native.P(out.data_ptr()), C.byref(info)), "nfsp_memory_table")
+    return out, info.to_dict()
+
+
+def memory_reports(ctx, engines, sl_tables, rl_tables, infos, tree: GameTree | None = None) -> list:
+    """``SelfPlayEngine.memory_report`` of every engine from its tables: the AR pair and the two
+    M_SL tables of all of them scored in one ``evaluate_batch`` call."""
+    tree = tree or GameTree(ctx.game)
+    from .engine import NET_AR
+    tabs = [(sl.policy("argmax"), sl.policy("mass")) for sl in sl_tables]
+    pairs = []
+    for e, (am, ms) in zip(engines, tabs):
+        pa, pm = Policy.table(am), Policy.table(ms)
+        pairs += [(e.policy(0, NET_AR), e.policy(1, NET_AR)), (pa, pa), (pm, pm)]
+    res = evaluate_batch(ctx, pairs)
+    legal = np.ones((tree.ndec, 3, 3), bool)
+    legal[~tree.legal, :, 2] = False
+    out = []
+    for k, e in enumerate(engines):
+        sl, rl = sl_tables[k], rl_tables[k]
+        ar, am, ms = (res[3 * k + j]["exploitability"] for j in range(3))
+        mass = tree.remap(tabs[k][1])
+        num = den = 0.0
+        for seat in (0, 1):
+            net = policy_table(ctx, e.policy(seat, NET_AR), tree).cpu().numpy()
+            rows = tree.seat == seat
+            w = sl.n[rows].astype(np.float64)
+            num += float((w * np.abs(net[rows] - mass[rows]).sum(axis=2)).sum())
+            den += float(w.sum())
+        out.append({
+            "exploitability_ar": ar, "exploitability_sl_argmax": am, "exploitability_sl_mass": ms,
+            # what the net adds to the strategy it is a fit of (> 0: the net is more exploitable)
+            "fit_gap_argmax": ar - am, "fit_gap_mass": ar - ms,
+            "sl_empty_sets": int((sl.n == 0).sum()),
+            "rl_empty_actions": int(((rl.counts == 0) & legal).sum()),
+            "ar_mass_l1": num / den if den > 0 else float("nan"),
+            "sl_info": infos[k][0], "rl_info": infos[k][1]})
+    return out
 
 
 class XfpSolver:

@@ -96,6 +96,19 @@ class XfpCfg(C.Structure):
     _fields_ = [("eta", C.c_double), ("weight", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MemSegment(C.Structure):
+    """``nfsp_mem_segment``: n packed records (SlRec 16 B / RlRec 32 B) at a device address"""
+    _fields_ = [("dev_recs", P), ("n", I64)]
+
+
+class MemtabInfo(C.Structure):
+    """``nfsp_memtab_info``: what one table call read"""
+    _fields_ = [("records", I64), ("matched", I64), ("unmatched", I64), ("clamped", I64)]
+
+    def to_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 PP = C.POINTER(P)
 # name -> (restype, argtypes); must list every symbol include/nfsp.h declares
 SIGNATURES = {
@@ -195,6 +208,12 @@ SIGNATURES = {
     "nfsp_state_check": (I32, [P, I64, C.POINTER(StateInfo)]),
     "nfsp_state_cfg": (I32, [P, I64, I32, C.POINTER(EngineCfg), C.POINTER(C.c_int32)]),
     "nfsp_state_digest": (I32, [P, I64, C.POINTER(U64)]),
+    "nfsp_memtab_lookup": (I32, [I32, I32, C.c_uint32]),
+    "nfsp_memtab_fix": (I64, [F32]),
+    "nfsp_memory_table": (I32, [P, I32, I32, I32, C.POINTER(MemSegment), I32, P, C.POINTER(MemtabInfo)]),
+    "nfsp_engine_memory_table": (I32, [P, I32, P, C.POINTER(MemtabInfo)]),
+    "nfsp_group_memory_tables": (I32, [P, I32, P, C.POINTER(MemtabInfo)]),
+    "nfsp_memtab_last_ms": (I32, [C.POINTER(F64)]),
 }
 # int (*nfsp_exchange_fn)(void* user, float* dev_sum, int64_t n)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, P, P, I64)
@@ -209,6 +228,10 @@ CFR_LAUNCH_ITERS = 1024
 XFP_WEIGHT_UNIFORM, XFP_WEIGHT_LINEAR = 0, 1
 XFP_LAUNCH_ITERS = 1024
 XFP_MAX_RUNS = 1024
+# the memories as tables (NFSP_MEM_*, NFSP_MEMTAB_*)
+MEM_SL, MEM_RL = 0, 1
+MEMTAB_FIX_SHIFT = 24
+MEMTAB_MAX_SEGMENTS = 8
 
 _LIB = None
 
