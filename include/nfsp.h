@@ -49,7 +49,8 @@ extern "C" {
 /* MLP output activation / loss (agent/agent.py:103,106,112,115) */
 #define NFSP_ACT_RELU 0        /* BR / target-BR head, Huber loss */
 #define NFSP_ACT_SOFTMAX 1     /* AR head, categorical cross-entropy */
-#define NFSP_ACT_LINEAR 2      /* BR head under NFSP_EXT_LINEAR_Q (engine only) */
+#define NFSP_ACT_LINEAR 2      /* BR head under NFSP_EXT_LINEAR_Q (the engine, nfsp_mlp_forward and
+                                  nfsp_head_tables; no nfsp_mlp_fit) */
 
 /* Reference quirks, reproduced by default (SURVEY.md §7 hard part (b)). */
 #define NFSP_QUIRK_TERMINAL_BOOTSTRAP 1u  /* `t_batch[k] is True` never holds: terminal
@@ -183,7 +184,8 @@ int nfsp_env_export(nfsp_ctx* ctx, void* dev_out /*[n,64] bytes*/);
 
 /* ---------------------------------------------------------------- networks */
 /* model.predict(x) (agent/agent.py:126,143,219,230) for B rows; bit-identical to the
- * oracle's fixed summation order for 0/1 inputs. */
+ * oracle's fixed summation order for 0/1 inputs.  act: any NFSP_ACT_*; LINEAR is the ReLU head's
+ * sums without the output activation. */
 int nfsp_mlp_forward(nfsp_ctx* ctx, const float* dev_w, int hidden, int act,
                      const float* dev_x /*[B,30]*/, float* dev_y /*[B,3]*/, int64_t B);
 /* model.fit(x, y, epochs, batch_size) with plain SGD (agent/agent.py:243,261): for each
@@ -770,6 +772,47 @@ int nfsp_group_memory_tables(nfsp_group* g, int kind, int64_t* dev_out /*[R][nde
 /* The two kernels' time in this thread's last table call (HIP events around them): how
  * profiles/memtab/ was measured. */
 int nfsp_memtab_last_ms(double* ms);
+
+/* ---- what the BR net is fitted to, and what it holds (csrc/memtab.hip k_memtab's third kind,
+ *      csrc/head_tables.hip k_head_tables) ----
+ * update_best_response_network (agent/agent.py:219-241) fits the BR net to one TD value per
+ * sampled M_RL tuple: v = r + gamma * max Q_target(s2), or r for a terminal tuple when
+ * NFSP_QUIRK_TERMINAL_BOOTSTRAP is off, written at the tuple's argmax(a).  The reference never
+ * sees these values outside a minibatch.  NFSP_MEM_TD counts them per information set over ALL
+ * live records where they lie, with k_br_targets' arithmetic operation for operation (the same
+ * forward, fwd_lds, of the target net in LDS; r as float, the product and the sum in double, one
+ * rounding to float), keyed as NFSP_MEM_RL by the stored s and the stored argmax k:
+ *   [k][0] records whose stored argmax is k; [k][1] the sum of fix(v); [k][2] the sum of
+ *   fix(max Q_target(s2)) over the records that bootstrap (a terminal-treated record adds 0).
+ * fix, the saturation and `clamped` are the memory tables' (every fix of a matched record that
+ * saturates counts); integers only, so the bits do not depend on the order of accumulation.  s2 may
+ * be any 30-bit word (a terminal observation is no decision row).  The head of the target net is
+ * ReLU, or linear with NFSP_EXT_LINEAR_Q in `quirks`; no other bit but TERMINAL_BOOTSTRAP is read.
+ * Two caveats the table does not hide: under NFSP_QUIRK_ALIAS_RL the key is the hand's LAST s
+ * (DESIGN.md §3), and under NFSP_QUIRK_ROW0_TARGET the net is fitted to one of these values per
+ * 128 sampled rows (agent/agent.py:240-241) -- the table states what is stored, whatever the quirks. */
+#define NFSP_MEM_TD 2
+typedef struct { const float* dev_target_w; double gamma; uint32_t quirks, reserved; } nfsp_td_args;   /* reserved: 0 */
+/* Raw form, as nfsp_memory_table: RlRec segments of `seat` against the packed target net. */
+int nfsp_td_table(nfsp_ctx* ctx, int game, int seat, const nfsp_mem_segment* segs, int nsegs,
+                  const nfsp_td_args* td, int64_t* dev_out, nfsp_memtab_info* info);
+/* An engine's live M_RL records, both agents in one launch, each against its own target net
+ * (NET_TARGET) with cfg.gamma and cfg.quirks; requires what nfsp_engine_memory_table requires. */
+int nfsp_engine_td_table(nfsp_engine* e, int64_t* dev_out /*[ndec][3][3][3]*/, nfsp_memtab_info info[2]);
+/* Every replica's in ONE launch: gamma, quirks and the target net ride in each table's device
+ * job, so the replicas of a heterogeneous group (nfsp_group_create_v) keep their own. */
+int nfsp_group_td_tables(nfsp_group* g, int64_t* dev_out /*[R][ndec][3][3][3]*/,
+                         nfsp_memtab_info* info /*[R][2]*/);
+/* The raw head outputs of n packed nets at every (row, rank) of nfsp_tree_export's rows, into
+ * dev_out[n][ndec][3 ranks][3] (f32, device): what a BR net holds as Q values, where
+ * nfsp_policy_table only has its one-hot argmax.  All three outputs are written, an illegal
+ * raise's too; the remap is the caller's.  dev_w: a host array of n device pointers; act[k]:
+ * NFSP_ACT_RELU, _LINEAR or _SOFTMAX of net k.  One workgroup per net, the net in LDS and one
+ * observation per lane through fwd_lds: the bits the rollout acts on and k_br_targets bootstraps
+ * from (agent/agent.py:126,219,230).  game must be the ctx's.  At most 64 nets per launch; the
+ * host loops beyond.  Synchronises the ctx stream. */
+int nfsp_head_tables(nfsp_ctx* ctx, int game, const float* const* dev_w, const int* act, int n,
+                     float* dev_out /*[n][ndec][3][3]*/);
 
 #ifdef __cplusplus
 }

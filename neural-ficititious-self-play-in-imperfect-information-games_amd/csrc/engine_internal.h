@@ -1,6 +1,7 @@
 // Internals shared by rollout.hip (rollout, insert), engine.hip (lifecycle, introspection),
 // learner.hip (the learner's kernels and launchers), engine_update.hip (one engine's learner
-// call), group.hip (engine groups), state.hip and memtab.hip (the memories as tables).
+// call), group.hip (engine groups), state.hip, memtab.hip (the memories as tables) and
+// head_tables.hip (the nets' head read-out).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -13,6 +13,13 @@
 //
 // One launch serves any number of tables (a seat of an engine or of a group's replica each)
 // through a device job table, as the chains' ChainJob does.
+//
+// The third kind, NFSP_MEM_TD (nfsp_td_table), counts what the BR net is fitted to: per M_RL
+// record k_br_targets' value r + gamma max Q_target(s2), by the stored s and argmax.  The target
+// net lies in LDS beside the hash and the bins (fwd_lds' layout) and every lane forwards its
+// record's s2 -- lanes without a record or an information set forward x = 0, fwd_lds ballots --
+// and adds fix(v) and fix(max Q).  gamma, quirks and the net ride in the table's job, so the
+// replicas of a heterogeneous group go through one launch.
 #include <math.h>
 
 #include <map>
@@ -34,6 +41,8 @@ constexpr int MT_MAX_ROWS = 128;        // decision rows of one seat (Leduc: 65)
 constexpr int MT_MAX_SEG = 8;
 constexpr int MT_WG = 1024;             // 16 waves
 constexpr int MT_U = 4;                 // records per lane in flight
+constexpr int TD_U = 1;                 // NFSP_MEM_TD: one, so that fwd_lds_n<9>'s gathers stay in registers
+                                        //   (124 VGPRs at 1,024 lanes, no scratch: DESIGN.md §9)
 constexpr int MT_BLOCKS = 512;          // 2 workgroups per CU of an MI355X
 constexpr int MT_LDS_MAX = 64 * 1024;
 constexpr int64_t MT_SAT = 4294967295ll;   // 2^32 - 1
@@ -122,6 +131,9 @@ struct MtTab {                            // one table: a seat's records in up t
   int64_t n[MT_MAX_SEG];                  // records
   int64_t* out;                           // the joint table [ndec][3][3][3] the seat's rows go to
   int32_t nseg, seat;
+  const float* tw;                        // NFSP_MEM_TD: the target net (packed), gamma and the quirks
+  double gamma;
+  uint32_t quirks, pad;
 };
 struct MtArgs {
   const uint32_t* keys;                   // [2][MT_H]
@@ -144,7 +156,8 @@ __device__ inline void lds_add(int64_t* p, int64_t v) {
 }
 
 // One record (sid >= 0) into the bins.  SL: val = fix(a), the count goes to action k.  RL:
-// val[0] = r in half units, val[1] = t, both to k.
+// val[0] = r in half units, val[1] = t, both to k.  TD: val[0] = fix(v), val[1] = fix(max Q) of a
+// record that bootstraps, both to k.
 template <int KIND>
 __device__ inline void mt_accum(int64_t* bins, int sid, int k, const int64_t val[3]) {
   constexpr int NF = KIND == NFSP_MEM_SL ? 2 : 3;
@@ -159,15 +172,24 @@ __device__ inline void mt_accum(int64_t* bins, int sid, int k, const int64_t val
   }
 }
 
-template <int KIND>
+// k_br_targets' TD value (br_targets_body.inc): the product and the sum each rounded, as the
+// restatement of tests/tdtab_ref.py rounds them
+__device__ inline float td_value(float r, float qmax, double gamma, bool terminal) {
+#pragma clang fp contract(off)
+  return (float)(terminal ? (double)r : (double)r + gamma * (double)qmax);
+}
+
+template <int KIND, int U>
 __global__ void __launch_bounds__(MT_WG) k_memtab(MtArgs A) {
-  extern __shared__ int64_t mt_lds[];
+  extern __shared__ __attribute__((aligned(16))) int64_t mt_lds[];
   constexpr int NF = KIND == NFSP_MEM_SL ? 2 : 3;
   constexpr int RQ = KIND == NFSP_MEM_SL ? 1 : 2;      // 16-byte words per record
+  constexpr int NETQ = KIND == NFSP_MEM_TD ? NET_LDS / 2 : 0;   // TD: the target net comes first
   const MtTab& T = A.tabs[blockIdx.y];
   const int seat = T.seat;
   const int nv = A.nrows[seat] * 9 * NF;
-  int64_t* bins = mt_lds;                              // [nv]
+  float* sw = reinterpret_cast<float*>(mt_lds);        // [NET_LDS], fwd_lds' layout and bank map
+  int64_t* bins = mt_lds + NETQ;                       // [nv]
   int64_t* ctr = bins + nv;                            // matched, unmatched, clamped
   uint32_t* hk = reinterpret_cast<uint32_t*>(ctr + 4);
   uint16_t* hv = reinterpret_cast<uint16_t*>(hk + MT_H);
@@ -176,6 +198,10 @@ __global__ void __launch_bounds__(MT_WG) k_memtab(MtArgs A) {
     hk[h] = A.keys[seat * MT_H + h];
     hv[h] = A.vals[seat * MT_H + h];
   }
+  if (KIND == NFSP_MEM_TD) stage_net_lds(sw, T.tw, threadIdx.x, MT_WG);
+  const double gamma = T.gamma;                        // TD; uniform over the workgroup, as act
+  const unsigned quirks = T.quirks;
+  const int act = br_act(quirks);
   __syncthreads();
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -184,16 +210,16 @@ __global__ void __launch_bounds__(MT_WG) k_memtab(MtArgs A) {
   for (int s = 0; s < T.nseg; ++s) {
     const uint4* __restrict__ p = T.p[s];
     const int64_t n = T.n[s];
-    // a wave takes 64 * MT_U consecutive records per turn: the bound is the wave's, not the lane's
-    for (int64_t base = gw * (64 * MT_U); base < n; base += nw * (64 * MT_U)) {
-      uint4 rec[MT_U];
+    // a wave takes 64 * U consecutive records per turn: the bound is the wave's, not the lane's
+    for (int64_t base = gw * (64 * U); base < n; base += nw * (64 * U)) {
+      uint4 rec[U];
 #pragma unroll
-      for (int u = 0; u < MT_U; ++u) {
+      for (int u = 0; u < U; ++u) {
         const int64_t k = base + u * 64 + lane;
         rec[u] = k < n ? p[k * RQ] : make_uint4(MT_EMPTY, 0, 3, 0);    // neither a key nor an action
       }
 #pragma unroll
-      for (int u = 0; u < MT_U; ++u) {
+      for (int u = 0; u < U; ++u) {
         const bool valid = base + u * 64 + lane < n;
         int sid = valid ? mt_find(hk, hv, rec[u].x) : -1;
         int k = 0;
@@ -209,8 +235,22 @@ __global__ void __launch_bounds__(MT_WG) k_memtab(MtArgs A) {
         } else {
           k = (int)(rec[u].z & 0xFFu);
           if (k > 2) sid = -1;                          // not a stored argmax: no bin
-          val[0] = (int8_t)(rec[u].z >> 16);
-          val[1] = (rec[u].z >> 8) & 1u;
+          if (KIND == NFSP_MEM_RL) {
+            val[0] = (int8_t)(rec[u].z >> 16);
+            val[1] = (rec[u].z >> 8) & 1u;
+          } else {
+            // every lane of the wave forwards (fwd_lds ballots): one without a record or a bin
+            // forwards x = 0 and drops the result.  s2 is any 30-bit word, fwd_lds exact for it
+            float y[3];
+            fwd_lds(sw, sid >= 0 ? rec[u].y : 0u, act, y);
+            if (sid >= 0) {
+              const float qmax = fmaxf(fmaxf(y[0], y[1]), y[2]);
+              const float r = (float)(int8_t)((rec[u].z >> 16) & 0xFFu) * 0.5f;
+              const bool terminal = !(quirks & NFSP_QUIRK_TERMINAL_BOOTSTRAP) && ((rec[u].z >> 8) & 1u);
+              val[0] = mt_fix(td_value(r, qmax, gamma, terminal), clamped);
+              val[1] = terminal ? 0 : mt_fix(qmax, clamped);
+            }
+          }
         }
         matched += sid >= 0;
         unmatched += valid && sid < 0;
@@ -315,9 +355,12 @@ int mt_run(hipStream_t st, int game, int kind, std::vector<MtTab>& tabs, nfsp_me
   const int NF = kind == NFSP_MEM_SL ? 2 : 3;
   const int nrmax = M->nrows[0] > M->nrows[1] ? M->nrows[0] : M->nrows[1];
   const int nvp = nrmax * 9 * NF + 3;
-  const size_t lds = sizeof(int64_t) * ((size_t)(nvp - 3) + 4) + MT_H * (sizeof(uint32_t) + sizeof(uint16_t));
+  const bool td = kind == NFSP_MEM_TD;
+  const size_t lds = sizeof(int64_t) * ((size_t)(nvp - 3) + 4) + MT_H * (sizeof(uint32_t) + sizeof(uint16_t)) +
+                     (td ? sizeof(float) * NET_LDS : 0);
   NFSP_REQUIRE(lds <= (size_t)MT_LDS_MAX, "memory table: the bins do not fit the workgroup's LDS");
-  int64_t nb = (maxn + (int64_t)MT_WG * MT_U * 2 - 1) / ((int64_t)MT_WG * MT_U * 2);
+  const int64_t turn = (int64_t)MT_WG * (td ? TD_U : MT_U);      // two turns of a workgroup per block
+  int64_t nb = (maxn + turn * 2 - 1) / (turn * 2);
   const int64_t cap = MT_BLOCKS / nt > 1 ? MT_BLOCKS / nt : 1;
   nb = nb < 1 ? 1 : nb > cap ? cap : nb;
 
@@ -352,8 +395,9 @@ int mt_run(hipStream_t st, int game, int kind, std::vector<MtTab>& tabs, nfsp_me
   NFSP_HIP(hipMemcpyAsync(W.buf, tabs.data(), sizeof(MtTab) * nt, hipMemcpyHostToDevice, st));
   NFSP_HIP(hipEventRecord(W.ev[0], st));
   const dim3 grid((unsigned)nb, (unsigned)nt);
-  if (kind == NFSP_MEM_SL) k_memtab<NFSP_MEM_SL><<<grid, MT_WG, lds, st>>>(A);
-  else k_memtab<NFSP_MEM_RL><<<grid, MT_WG, lds, st>>>(A);
+  if (kind == NFSP_MEM_SL) k_memtab<NFSP_MEM_SL, MT_U><<<grid, MT_WG, lds, st>>>(A);
+  else if (kind == NFSP_MEM_RL) k_memtab<NFSP_MEM_RL, MT_U><<<grid, MT_WG, lds, st>>>(A);
+  else k_memtab<NFSP_MEM_TD, TD_U><<<grid, MT_WG, lds, st>>>(A);
   NFSP_LAUNCHED("k_memtab");
   k_memtab_sum<<<dim3((unsigned)((nvp + 63) / 64), (unsigned)nt), MT_WG, 0, st>>>(A, kind);
   NFSP_LAUNCHED("k_memtab_sum");
@@ -377,11 +421,17 @@ int mt_seg(MtTab& T, const void* p, int64_t n) {
   return NFSP_OK;
 }
 
-// agent a's table of an engine at a step boundary (h: its EngineDev)
+// agent a's table of an engine at a step boundary (h: its EngineDev); TD: with the agent's own
+// target net, gamma and quirks
 int mt_engine_tab(nfsp_engine* e, const EngineDev& h, int kind, int a, int64_t* out, MtTab* T) {
   *T = MtTab{};
   T->seat = a;
   T->out = out;
+  if (kind == NFSP_MEM_TD) {
+    T->tw = e->w + (a * 3 + 2) * nfsp::nn::NP;       // NET_TARGET
+    T->gamma = e->cfg.gamma;
+    T->quirks = e->cfg.quirks;
+  }
   if (kind == NFSP_MEM_SL) return mt_seg(*T, e->M.sl + a * e->M.sl_cap, h.sl_count[a]);
   const RlPieces pc = rl_live_pieces(e, h, a);
   for (int k = 0; k < pc.n; ++k) {
@@ -416,14 +466,22 @@ extern "C" int nfsp_memtab_last_ms(double* ms) {
   return NFSP_OK;
 }
 
-extern "C" int nfsp_memory_table(nfsp_ctx* ctx, int game, int kind, int seat, const nfsp_mem_segment* segs, int nsegs,
-                                 int64_t* dev_out, nfsp_memtab_info* info) {
+namespace {
+
+// the raw forms: one seat's table of the caller's segments (td: NFSP_MEM_TD's arguments)
+int mt_raw(nfsp_ctx* ctx, int game, int kind, int seat, const nfsp_mem_segment* segs, int nsegs, const nfsp_td_args* td,
+           int64_t* dev_out, nfsp_memtab_info* info) {
   NFSP_REQUIRE(ctx && dev_out && (segs || nsegs == 0), "null argument");
-  NFSP_REQUIRE(kind_ok(kind) && (seat == 0 || seat == 1), "memory table: bad kind or seat");
+  NFSP_REQUIRE(seat == 0 || seat == 1, "memory table: bad kind or seat");
   NFSP_REQUIRE(nsegs >= 0 && nsegs <= NFSP_MEMTAB_MAX_SEGMENTS, "memory table: too many segments");
   std::vector<MtTab> tabs(1);
   tabs[0].seat = seat;
   tabs[0].out = dev_out;
+  if (td) {
+    tabs[0].tw = td->dev_target_w;
+    tabs[0].gamma = td->gamma;
+    tabs[0].quirks = td->quirks;
+  }
   int64_t total = 0;
   for (int s = 0; s < nsegs; ++s) {
     NFSP_REQUIRE(segs[s].n >= 0 && (segs[s].dev_recs || segs[s].n == 0), "memory table: bad segment");
@@ -436,11 +494,9 @@ extern "C" int nfsp_memory_table(nfsp_ctx* ctx, int game, int kind, int seat, co
   return mt_run(ctx->stream, game, kind, tabs, info);
 }
 
-extern "C" int nfsp_engine_memory_table(nfsp_engine* e, int kind, int64_t* dev_out, nfsp_memtab_info info[2]) {
-  NFSP_REQUIRE(e && dev_out, "null argument");
-  NFSP_REQUIRE(kind_ok(kind), "memory table: bad kind");
+int mt_engine(nfsp_engine* e, const char* what, int kind, int64_t* dev_out, nfsp_memtab_info info[2]) {
   EngineDev h;
-  int rc = engine_quiesce(e, "nfsp_engine_memory_table", &h);
+  int rc = engine_quiesce(e, what, &h);
   if (rc != NFSP_OK) return rc;
   std::vector<MtTab> tabs(2);
   for (int a = 0; a < 2; ++a)
@@ -448,12 +504,10 @@ extern "C" int nfsp_engine_memory_table(nfsp_engine* e, int kind, int64_t* dev_o
   return mt_run(e->ctx->stream, e->ctx->game, kind, tabs, info);
 }
 
-extern "C" int nfsp_group_memory_tables(nfsp_group* g, int kind, int64_t* dev_out, nfsp_memtab_info* info) {
-  NFSP_REQUIRE(g && dev_out, "null argument");
-  NFSP_REQUIRE(kind_ok(kind), "memory table: bad kind");
+int mt_group(nfsp_group* g, const char* what, int kind, int64_t* dev_out, nfsp_memtab_info* info) {
   GroupState G;
   std::vector<EngineDev> h;
-  int rc = group_quiesce(g, "nfsp_group_memory_tables", &G, &h);
+  int rc = group_quiesce(g, what, &G, &h);
   if (rc != NFSP_OK) return rc;
   const MtHost* M = nullptr;
   if ((rc = mt_host(G.ctx->game, &M)) != NFSP_OK) return rc;
@@ -463,4 +517,42 @@ extern "C" int nfsp_group_memory_tables(nfsp_group* g, int kind, int64_t* dev_ou
       if ((rc = mt_engine_tab(G.eng[r], h[r], kind, a, dev_out + (int64_t)r * M->ndec * 27, &tabs[2 * r + a])) != NFSP_OK)
         return rc;
   return mt_run(G.ctx->stream, G.ctx->game, kind, tabs, info);
+}
+
+}  // namespace
+
+extern "C" int nfsp_memory_table(nfsp_ctx* ctx, int game, int kind, int seat, const nfsp_mem_segment* segs, int nsegs,
+                                 int64_t* dev_out, nfsp_memtab_info* info) {
+  NFSP_REQUIRE(kind_ok(kind), "memory table: bad kind or seat");
+  return mt_raw(ctx, game, kind, seat, segs, nsegs, nullptr, dev_out, info);
+}
+
+extern "C" int nfsp_engine_memory_table(nfsp_engine* e, int kind, int64_t* dev_out, nfsp_memtab_info info[2]) {
+  NFSP_REQUIRE(e && dev_out, "null argument");
+  NFSP_REQUIRE(kind_ok(kind), "memory table: bad kind");
+  return mt_engine(e, "nfsp_engine_memory_table", kind, dev_out, info);
+}
+
+extern "C" int nfsp_group_memory_tables(nfsp_group* g, int kind, int64_t* dev_out, nfsp_memtab_info* info) {
+  NFSP_REQUIRE(g && dev_out, "null argument");
+  NFSP_REQUIRE(kind_ok(kind), "memory table: bad kind");
+  return mt_group(g, "nfsp_group_memory_tables", kind, dev_out, info);
+}
+
+extern "C" int nfsp_td_table(nfsp_ctx* ctx, int game, int seat, const nfsp_mem_segment* segs, int nsegs,
+                             const nfsp_td_args* td, int64_t* dev_out, nfsp_memtab_info* info) {
+  NFSP_REQUIRE(td && td->dev_target_w, "null argument");
+  NFSP_REQUIRE(td->reserved == 0, "nfsp_td_args.reserved must be 0");
+  NFSP_REQUIRE(((uintptr_t)td->dev_target_w & 3u) == 0, "TD table: the target net must be 4-byte aligned");
+  return mt_raw(ctx, game, NFSP_MEM_TD, seat, segs, nsegs, td, dev_out, info);
+}
+
+extern "C" int nfsp_engine_td_table(nfsp_engine* e, int64_t* dev_out, nfsp_memtab_info info[2]) {
+  NFSP_REQUIRE(e && dev_out, "null argument");
+  return mt_engine(e, "nfsp_engine_td_table", NFSP_MEM_TD, dev_out, info);
+}
+
+extern "C" int nfsp_group_td_tables(nfsp_group* g, int64_t* dev_out, nfsp_memtab_info* info) {
+  NFSP_REQUIRE(g && dev_out, "null argument");
+  return mt_group(g, "nfsp_group_td_tables", NFSP_MEM_TD, dev_out, info);
 }

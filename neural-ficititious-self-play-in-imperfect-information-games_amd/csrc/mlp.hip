@@ -51,6 +51,10 @@ __global__ void __launch_bounds__(256) k_mlp_forward(const float* __restrict__ w
     y[row * 3 + 0] = o0 > 0.f ? o0 : 0.f;
     y[row * 3 + 1] = o1 > 0.f ? o1 : 0.f;
     y[row * 3 + 2] = o2 > 0.f ? o2 : 0.f;
+  } else if (act == NFSP_ACT_LINEAR) {
+    y[row * 3 + 0] = o0;
+    y[row * 3 + 1] = o1;
+    y[row * 3 + 2] = o2;
   } else {
     const float m = fmaxf(fmaxf(o0, o1), o2);
     const float e0 = expf(o0 - m), e1 = expf(o1 - m), e2 = expf(o2 - m);
@@ -151,7 +155,7 @@ extern "C" int nfsp_mlp_forward(nfsp_ctx* c, const float* w, int hidden, int act
                                 float* y, int64_t B) {
   NFSP_REQUIRE(c && w && x && y, "null argument");
   NFSP_REQUIRE(hidden == H, "only hidden == 64 is built");
-  NFSP_REQUIRE(act == NFSP_ACT_RELU || act == NFSP_ACT_SOFTMAX, "bad act");
+  NFSP_REQUIRE(act == NFSP_ACT_RELU || act == NFSP_ACT_SOFTMAX || act == NFSP_ACT_LINEAR, "bad act");
   if (B <= 0) return NFSP_OK;
   k_mlp_forward<<<nfsp_blocks(B, 256), 256, 0, c->stream>>>(w, act, x, y, B);
   NFSP_LAUNCHED("k_mlp_forward");

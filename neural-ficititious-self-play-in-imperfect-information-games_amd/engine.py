@@ -303,6 +303,32 @@ class SelfPlayEngine:
         rl, ri = self.memory_table(native.MEM_RL)
         return ev.memory_reports(self.ctx, [self], [sl], [rl], [(si, ri)], tree)[0]
 
+    def td_table(self):
+        """``(evaluation.MemoryTable of kind native.MEM_TD, [info of agent 0, of agent 1])``: the TD
+        values r + gamma max Q_target(s2) the BR nets are fitted to, per (information set, stored
+        action) over the live M_RL records where they lie, each agent against its own target net
+        with ``cfg.gamma`` and ``cfg.quirks`` (nfsp_engine_td_table; step boundaries only).  Under
+        ``QUIRK_ALIAS_RL`` a record's key is its hand's LAST s."""
+        from . import evaluation as ev
+        tree = ev.GameTree(self.ctx.game)
+        out = torch.empty((tree.ndec, 3, 3, 3), dtype=torch.int64, device=self.dev)
+        info = (native.MemtabInfo * 2)()
+        native.check(self.L.nfsp_engine_td_table(self.h, native.P(out.data_ptr()), info), "nfsp_engine_td_table")
+        return ev.MemoryTable(tree, native.MEM_TD, out), [info[0].to_dict(), info[1].to_dict()]
+
+    def q_report(self, eta: float | None = None) -> list:
+        """The BR half of ``memory_report``, per agent i (``evaluation.q_report_from`` has the keys):
+        the Q values the BR net holds (``evaluation.head_tables``) and the TD values M_RL holds for
+        it (``td_table``) against the exact action values q / reach of ``best_response_table(eta,
+        values=True)`` -- the opponent is the other seat's AR policy, or with ``eta`` its per-hand
+        mixture, as ``br_gap(eta=)`` builds it.  ``td_rmse_exact`` is the data against the truth,
+        ``fit_rmse_td`` the net against its data.  Under ``QUIRK_ALIAS_RL`` a record's key is its
+        hand's LAST s, and under ``QUIRK_ROW0_TARGET`` the net is fitted to one TD value per 128
+        sampled rows: the report states what is stored and what the net holds."""
+        from . import evaluation as ev
+        td, info = self.td_table()
+        return ev.q_reports(self.ctx, [self], [td], [info], eta)[0]
+
     # -- checkpoints (checkpoint.py, DESIGN.md §10) ----------------------------------
     def save(self, path):
         """Save the engine at a step boundary (nfsp_engine_save_state); returns the bytes written."""
@@ -541,6 +567,25 @@ class EngineGroup:
             out += ev.memory_reports(self.ctx, [self.replicas[r] for r in rs], [sl[r][0] for r in rs],
                                      [rl[r][0] for r in rs], [(sl[r][1], rl[r][1]) for r in rs], tree)
         return out
+
+    def td_tables(self) -> list:
+        """Every replica's ``SelfPlayEngine.td_table()`` in one launch (nfsp_group_td_tables), each
+        with its own gamma, quirks and target nets: ``[(MemoryTable, [info 0, info 1])]``."""
+        from . import evaluation as ev
+        tree = ev.GameTree(self.ctx.game)
+        out = torch.empty((self.R, tree.ndec, 3, 3, 3), dtype=torch.int64, device=self.replicas[0].dev)
+        info = (native.MemtabInfo * (2 * self.R))()
+        native.check(self.L.nfsp_group_td_tables(self.h, native.P(out.data_ptr()), info), "nfsp_group_td_tables")
+        raw = out.cpu().numpy()
+        return [(ev.MemoryTable(tree, native.MEM_TD, raw[r]), [info[2 * r].to_dict(), info[2 * r + 1].to_dict()])
+                for r in range(self.R)]
+
+    def q_report_all(self, eta: float | None = None) -> list:
+        """``SelfPlayEngine.q_report`` of every replica: one TD launch and one head launch (per 32
+        replicas) for all of them."""
+        from . import evaluation as ev
+        tds = self.td_tables()
+        return ev.q_reports(self.ctx, self.replicas, [t for t, _ in tds], [i for _, i in tds], eta)
 
     # -- checkpoints (checkpoint.py, DESIGN.md §10) ----------------------------------
     def save(self, path):

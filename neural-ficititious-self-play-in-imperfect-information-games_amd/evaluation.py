@@ -27,6 +27,12 @@ approximates, with an exact best response and exact averaging.
 ``MemoryTable`` is a memory counted per information set on the device (``nfsp_memory_table``,
 csrc/memtab.hip): M_SL as the tabular average strategy the AR net is a fit of, M_RL as what the
 BR net had to learn from; ``memory_reports`` scores the former beside the nets.
+
+``head_tables`` (``nfsp_head_tables``) reads out the Q values a BR net holds where ``policy_table``
+only has its one-hot argmax, ``td_table`` (``nfsp_td_table``) counts the TD values the net is
+fitted to per (information set, action) over M_RL where it lies, and ``q_report_from`` splits the
+BR net's error against ``best_response``'s exact action values in two: what the data say against
+the truth, and what the net makes of its data.
 """
 from __future__ import annotations
 
@@ -272,6 +278,10 @@ class MemoryTable:
     whose stored argmax is the action, field 1 the sum of their rewards in half chips, field 2
     how many of them are terminal.
 
+    ``native.MEM_TD`` (``td_table``): field 0 as ``MEM_RL``, field 1 the sum of the records' TD
+    values v = r + gamma max Q_target(s2) and field 2 the sum of max Q_target(s2) over the records
+    that bootstrap, both in 2^-24 units.
+
     ``counts[ndec, 3, 3]`` is field 0 and ``n[ndec, 3]`` the records per information set."""
 
     def __init__(self, tree: GameTree, kind: int, raw):
@@ -316,16 +326,27 @@ class MemoryTable:
         self._rl()
         return self.raw[..., 2]
 
+    def _td_mean(self, field):
+        if self.kind != native.MEM_TD:
+            raise AttributeError("mean_v / mean_bootstrap belong to TD tables")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.counts > 0, self.raw[..., field] / (2.0**native.MEMTAB_FIX_SHIFT * self.counts), np.nan)
 
-def memory_table(ctx, kind: int, seat: int, records, out=None, tree: GameTree | None = None):
-    """``nfsp_memory_table``: packed device records (``SlRec`` 16 B / ``RlRec`` 32 B) of ``seat``
-    counted into the seat's rows of ``out``, an int64 device tensor ``[ndec, 3, 3, 3]`` (zeros
-    when not given; the other seat's rows are left as they are).  ``records``: one segment or a
-    list of them, each a contiguous device tensor of whole records or ``(device address, n)``.
-    Returns ``(out, info)``; ``MemoryTable(tree, kind, out)`` reads it."""
+    @property
+    def mean_v(self) -> np.ndarray:
+        """TD: the mean TD value in chips per (row, rank, stored action); NaN without records."""
+        return self._td_mean(1)
+
+    @property
+    def mean_bootstrap(self) -> np.ndarray:
+        """TD: the mean of max Q_target(s2) per (row, rank, stored action), a record that does not
+        bootstrap counting as 0; NaN without records."""
+        return self._td_mean(2)
+
+
+def _segments(records, size):
+    """``records`` of ``memory_table`` / ``td_table`` as (a ``MemSegment`` array, its length)."""
     import torch
-    tree = tree or GameTree(ctx.game)
-    size = 16 if kind == native.MEM_SL else 32
     if isinstance(records, torch.Tensor) or (isinstance(records, tuple) and isinstance(records[0], int)):
         records = [records]
     segs = []
@@ -337,13 +358,164 @@ def memory_table(ctx, kind: int, seat: int, records, out=None, tree: GameTree | 
             segs.append(native.MemSegment(native.P(r.data_ptr()), nbytes // size))
         else:
             segs.append(native.MemSegment(native.P(int(r[0])), int(r[1])))
+    return (native.MemSegment * max(len(segs), 1))(*segs), len(segs)
+
+
+def memory_table(ctx, kind: int, seat: int, records, out=None, tree: GameTree | None = None):
+    """``nfsp_memory_table``: packed device records (``SlRec`` 16 B / ``RlRec`` 32 B) of ``seat``
+    counted into the seat's rows of ``out``, an int64 device tensor ``[ndec, 3, 3, 3]`` (zeros
+    when not given; the other seat's rows are left as they are).  ``records``: one segment or a
+    list of them, each a contiguous device tensor of whole records or ``(device address, n)``.
+    Returns ``(out, info)``; ``MemoryTable(tree, kind, out)`` reads it."""
+    import torch
+    tree = tree or GameTree(ctx.game)
+    arr, nsegs = _segments(records, 16 if kind == native.MEM_SL else 32)
     if out is None:
         out = torch.zeros((tree.ndec, 3, 3, 3), dtype=torch.int64, device="cuda")
-    arr = (native.MemSegment * max(len(segs), 1))(*segs)
     info = native.MemtabInfo()
-    native.check(ctx.L.nfsp_memory_table(ctx.h, tree.game, int(kind), int(seat), arr, len(segs),
+    native.check(ctx.L.nfsp_memory_table(ctx.h, tree.game, int(kind), int(seat), arr, nsegs,
                                          native.P(out.data_ptr()), C.byref(info)), "nfsp_memory_table")
     return out, info.to_dict()
+
+
+def td_table(ctx, seat: int, records, target_w, gamma: float, quirks: int, out=None, tree: GameTree | None = None):
+    """``nfsp_td_table``: the TD values the BR net is fitted to (agent/agent.py:219-241), counted
+    over packed ``RlRec`` device records of ``seat`` into the seat's rows of ``out`` (as
+    ``memory_table``).  Per record v = r + gamma max Q_target(s2), or r where the record is terminal
+    and ``QUIRK_TERMINAL_BOOTSTRAP`` is off, with ``k_br_targets``' arithmetic; ``target_w`` is the
+    packed target net (array, tensor or device address), its head linear with ``EXT_LINEAR_Q`` in
+    ``quirks``.  The key is the stored s and the stored argmax: under ``QUIRK_ALIAS_RL`` the hand's
+    LAST s.  Returns ``(out, info)``; ``MemoryTable(tree, native.MEM_TD, out)`` reads it."""
+    import torch
+    tree = tree or GameTree(ctx.game)
+    arr, nsegs = _segments(records, 32)
+    w, addr = Policy._dev(target_w, torch.float32, 30 * 64 + 64 + 64 * 3 + 3)
+    if out is None:
+        out = torch.zeros((tree.ndec, 3, 3, 3), dtype=torch.int64, device="cuda")
+    td = native.TdArgs(native.P(w.data_ptr() if addr is None else addr), float(gamma), int(quirks), 0)
+    info = native.MemtabInfo()
+    native.check(ctx.L.nfsp_td_table(ctx.h, tree.game, int(seat), arr, nsegs, C.byref(td), native.P(out.data_ptr()),
+                                     C.byref(info)), "nfsp_td_table")
+    return out, info.to_dict()
+
+
+def head_tables(ctx, nets, acts, tree: GameTree | None = None):
+    """``nfsp_head_tables``: the raw head outputs of packed nets (arrays, tensors or device
+    addresses) at every row and rank, a float32 device tensor ``[n, ndec, 3, 3]`` -- for a BR net
+    the Q values it holds, with the bits the rollout acts on.  ``acts[k]``: ``native.ACT_RELU``,
+    ``ACT_LINEAR`` or ``ACT_SOFTMAX``.  All three outputs are there, an illegal raise's too."""
+    import torch
+    tree = tree or GameTree(ctx.game)
+    n = len(nets)
+    if len(acts) != n:
+        raise ValueError("one act per net")
+    keep = [Policy._dev(w, torch.float32, 30 * 64 + 64 + 64 * 3 + 3) for w in nets]
+    ptrs = (native.P * max(n, 1))(*[t.data_ptr() if p is None else p for t, p in keep])
+    act = (native.I32 * max(n, 1))(*[int(a) for a in acts])
+    out = torch.empty((n, tree.ndec, 3, 3), dtype=torch.float32, device="cuda")
+    native.check(ctx.L.nfsp_head_tables(ctx.h, tree.game, ptrs, act, n, native.P(out.data_ptr())), "nfsp_head_tables")
+    return out
+
+
+def _rms(err, weight):
+    den = float(weight.sum())
+    return float(np.sqrt((weight * err**2).sum() / den)) if den > 0 else float("nan")
+
+
+def q_report_from(tree: GameTree, seat: int, beta, q, reach, head, td, linear: bool, gamma: float = 1.0,
+                  info=None) -> dict:
+    """The BR half of ``memory_report`` for agent ``seat``, pure host arithmetic.
+
+    ``beta``, ``q``, ``reach``: ``best_response(values=True)`` against the opponent the agent
+    faces; ``head[ndec, 3, 3]``: the agent's BR net's raw outputs (``head_tables``); ``td``: its TD
+    table (a ``MemoryTable`` of kind ``MEM_TD`` or the raw array); ``linear``: whether the head is
+    linear (echoed); ``gamma``: the TD table's.  Over the rows where the seat acts, with
+    qx = q / reach (the exact expected chips of each legal action where reach > 0: what the Q net is
+    to learn) and w = reach / sum reach:
+
+    * ``q_rmse_exact``   sqrt(sum_sets w sum_legal (Q_net - qx)^2 / sum_sets w nlegal);
+    * ``greedy_mismatch_share``  the w-share of reached sets where the head's executed action
+      (first maximum, an illegal raise becomes call) is not ``beta``'s;
+    * ``neg_value_actions``  reached (set, legal action) pairs with qx < 0;
+    * ``relu_blind_share``  the w-share of reached sets whose best exact action is not fold and has
+      qx <= 0: a ReLU head can at best tie there, and the first maximum folds (reported for a
+      linear head too);
+    * ``td_pairs`` / ``td_empty_actions``  legal pairs with / without records;
+    * ``td_rmse_exact``  the count-weighted RMS of mean_v - qx over pairs with records and
+      reach > 0: the data against the truth;
+    * ``fit_rmse_td``    the count-weighted RMS of Q_net - mean_v over pairs with records: the net
+      against its data;
+    * ``mean_bootstrap_share``  sum field 2 x gamma / sum |field 1| over the legal pairs (NaN
+      without TD mass);
+    * ``linear``, and ``info`` when given.
+
+    RMS values without a pair to average are NaN.  Records stored at an illegal raise are in the
+    table but in none of these figures.  Two caveats: under ``QUIRK_ALIAS_RL`` a record's key is its
+    hand's LAST s, and under ``QUIRK_ROW0_TARGET`` the net is fitted to one TD value per 128 sampled
+    rows; the report states what is stored and what the net holds, whatever the quirks."""
+    def host(x):
+        return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+    beta = host(beta).astype(np.float64).reshape(tree.ndec, 3, 3)
+    q = host(q).astype(np.float64).reshape(tree.ndec, 3, 3)
+    reach = host(reach).astype(np.float64).reshape(tree.ndec, 3)
+    head = host(head).astype(np.float64).reshape(tree.ndec, 3, 3)
+    if not isinstance(td, MemoryTable):
+        td = MemoryTable(tree, native.MEM_TD, td)
+    mine = (tree.seat == seat)[:, None]
+    legal = np.ones((tree.ndec, 3, 3), bool)
+    legal[~tree.legal, :, 2] = False
+    legal &= mine[:, :, None]
+    reached = mine & (reach > 0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        qx = np.where(reached[:, :, None], q / reach[:, :, None], np.nan)
+    tot = float(reach[reached].sum())
+    w = np.where(reached, reach / tot, 0.0) if tot > 0 else np.zeros_like(reach)
+    pair = legal & reached[:, :, None]
+    err = np.where(pair, head - np.where(pair, qx, 0.0), 0.0)
+    with np.errstate(invalid="ignore"):
+        greedy = np.argmax(head, axis=2)                           # first maximum, a NaN is the maximum
+    greedy = np.where((greedy == 2) & ~tree.legal[:, None], 1, greedy)
+    best = np.argmax(beta, axis=2)
+    qbest = np.take_along_axis(np.where(reached[:, :, None], qx, 0.0), best[:, :, None], axis=2)[:, :, 0]
+    cnt = np.where(legal, td.counts, 0).astype(np.float64)
+    has = cnt > 0
+    with np.errstate(invalid="ignore"):
+        mv = np.where(has, td.mean_v, 0.0)
+    both = has & pair
+    f1 = td.raw[..., 1][legal].astype(np.float64)
+    f2 = td.raw[..., 2][legal].astype(np.float64)
+    mass = float(np.abs(f1).sum())
+    out = {
+        "q_rmse_exact": _rms(err, w[:, :, None] * pair),
+        "greedy_mismatch_share": float((w * (greedy != best))[reached].sum()),
+        "neg_value_actions": int((pair & (np.where(pair, qx, 0.0) < 0)).sum()),
+        "relu_blind_share": float((w * ((best != 0) & (qbest <= 0)))[reached].sum()),
+        "td_pairs": int(has.sum()),
+        "td_empty_actions": int((legal & ~has).sum()),
+        "td_rmse_exact": _rms(np.where(both, mv - np.where(both, qx, 0.0), 0.0), cnt * both),
+        "fit_rmse_td": _rms(np.where(has, head - mv, 0.0), cnt),
+        "mean_bootstrap_share": float(f2.sum()) * float(gamma) / mass if mass > 0 else float("nan"),
+        "linear": bool(linear)}
+    if info is not None:
+        out["info"] = info
+    return out
+
+
+def q_reports(ctx, engines, td_tables, infos, eta=None, tree: GameTree | None = None) -> list:
+    """``SelfPlayEngine.q_report`` of every engine from its TD table: one ``head_tables`` launch for
+    all of their BR nets (per 64), one ``best_response`` per engine."""
+    from .engine import NET_BR, _opponents
+    tree = tree or GameTree(ctx.game)
+    lin = [bool(e.cfg.quirks & native.EXT_LINEAR_Q) for e in engines]
+    head = head_tables(ctx, [e._wptr(a, NET_BR) for e in engines for a in (0, 1)],
+                       [native.ACT_LINEAR if l else native.ACT_RELU for l in lin for _ in (0, 1)], tree).cpu().numpy()
+    out = []
+    for k, e in enumerate(engines):
+        opp = _opponents(ctx, e, 0, eta, tree)
+        beta, q, reach = (t.cpu().numpy() for t in best_response(ctx, opp[0], opp[1], True, tree))
+        out.append([q_report_from(tree, a, beta, q, reach, head[2 * k + a], td_tables[k], lin[k],
+                                  float(e.cfg.gamma), infos[k][a]) for a in (0, 1)])
+    return out
 
 
 def memory_reports(ctx, engines, sl_tables, rl_tables, infos, tree: GameTree | None = None) -> list:

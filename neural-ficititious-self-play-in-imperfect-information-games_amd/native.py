@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("NFSP_LIB", os.path.join(HERE, "libnfsp.so"))
 OK, EINVAL, EHIP, ENOMEM = 0, -1, -2, -3
 GAME_LEDUC = 0
 GAME_KUHN = 1     # the Kuhn swap-in (include/nfsp.h NFSP_GAME_KUHN)
-ACT_RELU, ACT_SOFTMAX = 0, 1
+ACT_RELU, ACT_SOFTMAX, ACT_LINEAR = 0, 1, 2
 QUIRK_TERMINAL_BOOTSTRAP, QUIRK_ROW0_TARGET, QUIRK_ALIAS_RL = 1, 2, 4
 QUIRKS_REFERENCE = 7
 # textbook-NFSP extensions (include/nfsp.h NFSP_EXT_*; not the reference's algorithm)
@@ -107,6 +107,11 @@ class MemtabInfo(C.Structure):
 
     def to_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class TdArgs(C.Structure):
+    """``nfsp_td_args``: the target net, gamma and quirks a TD table is counted with"""
+    _fields_ = [("dev_target_w", P), ("gamma", F64), ("quirks", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 PP = C.POINTER(P)
@@ -214,6 +219,10 @@ SIGNATURES = {
     "nfsp_engine_memory_table": (I32, [P, I32, P, C.POINTER(MemtabInfo)]),
     "nfsp_group_memory_tables": (I32, [P, I32, P, C.POINTER(MemtabInfo)]),
     "nfsp_memtab_last_ms": (I32, [C.POINTER(F64)]),
+    "nfsp_td_table": (I32, [P, I32, I32, C.POINTER(MemSegment), I32, C.POINTER(TdArgs), P, C.POINTER(MemtabInfo)]),
+    "nfsp_engine_td_table": (I32, [P, P, C.POINTER(MemtabInfo)]),
+    "nfsp_group_td_tables": (I32, [P, P, C.POINTER(MemtabInfo)]),
+    "nfsp_head_tables": (I32, [P, I32, PP, C.POINTER(I32), I32, P]),
 }
 # int (*nfsp_exchange_fn)(void* user, float* dev_sum, int64_t n)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, P, P, I64)
@@ -229,7 +238,7 @@ XFP_WEIGHT_UNIFORM, XFP_WEIGHT_LINEAR = 0, 1
 XFP_LAUNCH_ITERS = 1024
 XFP_MAX_RUNS = 1024
 # the memories as tables (NFSP_MEM_*, NFSP_MEMTAB_*)
-MEM_SL, MEM_RL = 0, 1
+MEM_SL, MEM_RL, MEM_TD = 0, 1, 2
 MEMTAB_FIX_SHIFT = 24
 MEMTAB_MAX_SEGMENTS = 8
 

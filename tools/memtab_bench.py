@@ -15,6 +15,9 @@ not from HBM -- as the state digest's beside them (nfsp_engine_state_digest_time
   b  synthetic M_SL records at the same n with keys uniform over a seat's sets and all in one
      set: the two ends of the contention on the LDS bins.  (profiles/memtab/schemes_c3.json is
      this part run while two more aggregation schemes were compiled in)
+     With --td (profiles/qreport/): also the TD table (nfsp_engine_td_table: a forward of the target
+     net per record inside k_memtab) beside the M_RL table on the same state, and one q_report();
+     part b is skipped.  --quirks picks the reference's quirks or NFSP_TEXTBOOK_MSE_DECAY.
   c  the c3_r16 group (16 replicas x 65,536 lanes, each M_RL 200k + M_SL 2M): the group form
      against 16 engine-form calls."""
 import argparse
@@ -52,8 +55,9 @@ def rate(t, nbytes):
 def part_a(pkg, args, torch):
     import numpy as np
     nat, ev = pkg.native, pkg.evaluation
+    quirks = nat.QUIRKS_REFERENCE if args.quirks == "reference" else nat.TEXTBOOK_MSE_DECAY
     eng = pkg.engine.SelfPlayEngine(n_lanes=args.lanes, slices=args.slices, slice_lag=2 if args.slices > 1 else 1,
-                                    rl_capacity=args.rl_capacity, sl_capacity=args.sl_capacity)
+                                    rl_capacity=args.rl_capacity, sl_capacity=args.sl_capacity, quirks=quirks)
     steps, step_ms = 0, None
     while steps < args.max_steps:
         torch.cuda.synchronize()
@@ -65,10 +69,23 @@ def part_a(pkg, args, torch):
         if steps >= 2 and min(eng.stats()["sl_size"]) >= args.sl_capacity:
             break
     st = eng.stats()
-    out = {"steps": steps, "step_ms": step_ms, "rl_size": st["rl_size"], "sl_size": st["sl_size"]}
+    out = {"steps": steps, "step_ms": step_ms, "rl_size": st["rl_size"], "sl_size": st["sl_size"], "quirks": args.quirks}
     for kind, name, rec, n in ((nat.MEM_SL, "sl", 16, sum(st["sl_size"])), (nat.MEM_RL, "rl", 32, sum(st["rl_size"]))):
         out[name] = rate(timed(pkg, lambda: eng.memory_table(kind), args.repeats), rec * n)
         # M_RL: the kernel reads the first 16 bytes of each 32-byte record; the bytes are the records'
+    if args.td:
+        out["td"] = rate(timed(pkg, lambda: eng.td_table(), args.repeats), 32 * sum(st["rl_size"]))
+        out["td_over_rl"] = out["td"]["ms_best"] / out["rl"]["ms_best"]
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        rep = eng.q_report()
+        out["q_report_ms"] = (time.perf_counter() - t) * 1e3
+        out["q_report_over_step"] = out["q_report_ms"] / step_ms
+        out["q_report"] = [{k: v for k, v in r.items() if k != "info"} for r in rep]
+        out["exploitability"] = eng.exploitability()["exploitability"]
+        out["br_gap"] = [g["gap"] for g in eng.br_gap()]
+        eng.close()
+        return out
     d0, first, _ = eng.state_digest_timed()
     runs = []
     for _ in range(args.repeats):
@@ -159,6 +176,9 @@ def main():
     ap.add_argument("--max-steps", type=int, default=12)
     ap.add_argument("--replicas", type=int, default=16)
     ap.add_argument("--group-steps", type=int, default=3)
+    ap.add_argument("--td", action="store_true", help="part a: the TD table beside the M_RL table, and one q_report()")
+    ap.add_argument("--quirks", default="reference", choices=["reference", "textbook"],
+                    help="part a: NFSP_QUIRKS_REFERENCE or NFSP_TEXTBOOK_MSE_DECAY")
     args = ap.parse_args()
     import torch
     import __graft_entry__
