@@ -1,15 +1,17 @@
 // The batched NFSP self-play engine as an object: its lifecycle (allocation from the sizes of
 // engine_cfg.h, destruction), nfsp_engine_step, and introspection (stats, the memories in the
-// reference's layout, the debug views, the loss log, the timings).  The rollout path is
+// reference's layout, the debug views, the loss log, the timings), and the engine brought to
+// rest with the view of its memories (engine_rest, engine_view: mem_view.h).  The rollout path is
 // rollout.hip, the learner call engine_update.hip; the data path of a step is described at the
 // head of rollout.hip.  Declarations and the semantics contract: include/nfsp.h (nfsp_engine_*).
 #include <math.h>
 
 #include <cmath>
+#include <string>
 #include <utility>
 #include <vector>
 
-#include "engine_internal.h"
+#include "mem_view.h"
 
 namespace nn = nfsp::nn;
 using namespace nfsp::eng;
@@ -234,6 +236,33 @@ int engine_create(nfsp_ctx* ctx, const nfsp_engine_cfg* cfg, bool own_streams, n
     return nfsp::hip_fail(r, "nfsp_engine_create: init state");
   }
   *out = e;
+  return NFSP_OK;
+}
+
+// mem_view.h: the engine at a step boundary, its streams idle
+int engine_rest(nfsp_engine* e, const char* what, bool for_load) {
+  const char* why = nullptr;
+  if (e->pending_update || e->xchg_pending)
+    why = for_load ? "a rollout or an exchange is pending" : "a rollout awaits nfsp_engine_update, or an exchange is pending";
+  else if (!for_load && e->xchg_every > 0 && e->xchg_calls % e->xchg_every != 0)
+    why = "the exchange is due only after further learner calls";
+  else if (!for_load && e->rollouts % (uint64_t)e->slices != 0) why = "the step's slices are not all played";
+  if (why) return nfsp::fail(NFSP_EINVAL, std::string(what) + ": not at a step boundary (" + why + ")");
+  NFSP_HIP(hipStreamSynchronize(e->ctx->stream));
+  for (hipStream_t st : {e->s_ar, e->s_br[0], e->s_br[1]})
+    if (st) NFSP_HIP(hipStreamSynchronize(st));
+  return NFSP_OK;
+}
+
+int engine_view(nfsp_engine* e, const char* what, MemView* v) {
+  int rc = engine_rest(e, what);
+  if (rc != NFSP_OK) return rc;
+  EngineDev h;
+  NFSP_HIP(hipMemcpyAsync(&h, e->st, sizeof(h), hipMemcpyDeviceToHost, e->ctx->stream));
+  NFSP_HIP(hipStreamSynchronize(e->ctx->stream));
+  if ((rc = st_check(h, e->cfg, "engine state")) != NFSP_OK) return rc;
+  if ((uint64_t)h.rollouts != e->rollouts) return nfsp::fail(NFSP_EINVAL, "engine state: the device's rollout count differs from the host's");
+  *v = mem_view(e, h);
   return NFSP_OK;
 }
 }  // namespace eng

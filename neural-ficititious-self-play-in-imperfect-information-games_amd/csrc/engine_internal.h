@@ -1,7 +1,8 @@
 // Internals shared by rollout.hip (rollout, insert), engine.hip (lifecycle, introspection),
 // learner.hip (the learner's kernels and launchers), engine_update.hip (one engine's learner
 // call), group.hip (engine groups), state.hip, memtab.hip (the memories as tables) and
-// head_tables.hip (the nets' head read-out).
+// head_tables.hip (the nets' head read-out).  What reads or writes the memories where they lie
+// goes through mem_view.h, which builds on this header.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -345,21 +346,8 @@ struct GroupState {
   unsigned* w0_valid;
   int64_t* calls;
   int xchg_every;
-  hipStream_t streams[6];      // the group's learner streams (nullptr: not created)
-  int n_streams;
 };
 int group_state(nfsp_group* g, GroupState* out);
-// What reads the memories where they lie shares with the digest (state.hip): the engine (group)
-// at a step boundary with its streams idle -- anything else is NFSP_EINVAL naming `what` -- its
-// EngineDev read back, and an agent's live M_RL records as the at most two pieces (first row,
-// rows) of its circular log, oldest first.
-int engine_quiesce(nfsp_engine* e, const char* what, EngineDev* h);
-int group_quiesce(nfsp_group* g, const char* what, GroupState* G, std::vector<EngineDev>* h);
-struct RlPieces {
-  int n = 0;
-  int64_t row[2], len[2];
-};
-RlPieces rl_live_pieces(const nfsp_engine* e, const EngineDev& h, int a);
 
 // RAII bracket: records start/stop events around launches on `stream` when timing is on
 struct KTimer {

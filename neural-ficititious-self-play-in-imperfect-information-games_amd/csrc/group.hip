@@ -1,5 +1,6 @@
 // Engine groups (nfsp_group_*): R replicas stepped together, their chains in shared launches.
-// Host code only: the group object, its cfg rules, exchange, scheduling knobs and trace, and
+// Host code only: the group object, its cfg rules, exchange, scheduling knobs and trace, the
+// group brought to rest with its replicas' views (group_rest, group_view: mem_view.h), and
 // the group's learner call (group_update), which plans the BR work with group_plan.h and
 // launches learner.hip's kernels through its launchers (learner_internal.h) -- or, opted in
 // (sched.br_persist), the persistent BR kernel through br_persist.h, at five marked call sites.
@@ -10,6 +11,7 @@
 #include <string>
 
 #include "br_persist.h"
+#include "mem_view.h"
 
 namespace nn = nfsp::nn;
 namespace plan = nfsp::plan;
@@ -58,13 +60,18 @@ struct nfsp_group {
   std::vector<int32_t> trace;
 };
 
+// every stream the group enqueues on, idle
+static int group_sync(const nfsp_group* g) {
+  if (g->ctx) NFSP_HIP(hipStreamSynchronize(g->ctx->stream));
+  for (hipStream_t st : {g->s_ar, g->s_br, g->s_brp[0], g->s_brp[1], g->s_brp[2]})
+    if (st) NFSP_HIP(hipStreamSynchronize(st));
+  static_assert(GROUP_BR_STREAMS == 4, "group_sync names every BR stream");
+  return NFSP_OK;
+}
+
 extern "C" int nfsp_group_destroy(nfsp_group* g) {
   if (!g) return NFSP_OK;
-  if (g->ctx) (void)hipStreamSynchronize(g->ctx->stream);
-  for (hipStream_t st : {g->s_ar, g->s_br})
-    if (st) (void)hipStreamSynchronize(st);
-  for (hipStream_t st : g->s_brp)
-    if (st) (void)hipStreamSynchronize(st);
+  (void)group_sync(g);
   for (nfsp_engine* e : g->eng) nfsp_engine_destroy(e);
   for (int p = 0; p < 2; ++p) {
     if (g->h_tab[p]) (void)hipHostFree(g->h_tab[p]);
@@ -228,18 +235,28 @@ namespace nfsp {
 namespace eng {
 int group_state(nfsp_group* g, GroupState* out) {
   NFSP_REQUIRE(g && out, "null argument");
-  *out = GroupState{};
-  out->ctx = g->ctx;
-  out->R = g->R;
-  out->flags = g->flags;
-  out->eng = g->eng.data();
-  out->w0 = g->w0;
-  out->w0_valid = &g->w0_valid;
-  out->calls = &g->calls;
-  out->xchg_every = g->xchg_every;
-  out->streams[out->n_streams++] = g->s_ar;
-  out->streams[out->n_streams++] = g->s_br;
-  for (hipStream_t st : g->s_brp) out->streams[out->n_streams++] = st;
+  *out = GroupState{g->ctx, g->R, g->flags, g->eng.data(), g->w0, &g->w0_valid, &g->calls, g->xchg_every};
+  return NFSP_OK;
+}
+
+// mem_view.h: the group at a step boundary, its streams idle
+int group_rest(nfsp_group* g, const char* what, bool for_load) {
+  for (const nfsp_engine* e : g->eng)
+    if (e->pending_update ||
+        (!for_load && (e->rollouts % (uint64_t)e->slices != 0 || e->rollouts != g->eng[0]->rollouts)))
+      return nfsp::fail(NFSP_EINVAL, std::string(what) + ": not at a step boundary");
+  if (!for_load && g->xchg_every > 0 && g->calls % g->xchg_every != 0)
+    return nfsp::fail(NFSP_EINVAL, std::string(what) + ": not at a step boundary (the exchange is due only after further learner calls)");
+  return group_sync(g);
+}
+
+int group_view(nfsp_group* g, const char* what, GroupState* G, std::vector<MemView>* v) {
+  int rc = group_state(g, G);
+  if (rc != NFSP_OK) return rc;
+  if ((rc = group_rest(g, what)) != NFSP_OK) return rc;
+  v->resize(g->R);
+  for (int r = 0; r < g->R; ++r)
+    if ((rc = engine_view(g->eng[r], what, &(*v)[r])) != NFSP_OK) return rc;
   return NFSP_OK;
 }
 }  // namespace eng
@@ -717,12 +734,8 @@ extern "C" int nfsp_group_get_sched(nfsp_group* g, nfsp_group_sched* out) {
 
 extern "C" int nfsp_group_check(nfsp_group* g) {
   NFSP_REQUIRE(g, "null argument");
-  NFSP_HIP(hipStreamSynchronize(g->ctx->stream));
-  for (hipStream_t st : {g->s_ar, g->s_br})
-    if (st) NFSP_HIP(hipStreamSynchronize(st));
-  for (hipStream_t st : g->s_brp)
-    if (st) NFSP_HIP(hipStreamSynchronize(st));
-  return brp_flags_take(g->h_err);   // br_persist.h
+  const int rc = group_sync(g);
+  return rc != NFSP_OK ? rc : brp_flags_take(g->h_err);   // br_persist.h
 }
 
 extern "C" int nfsp_group_rounds(nfsp_group* g, int64_t* out) {

@@ -47,7 +47,7 @@ inline int part_begin(int p, int R, int nbs) { return p * R / nbs; }
 // cap 0: one round per segment index, every job's k-th segment in round k.
 // A round lasts as long as its longest piece, so with whole segments the round structure waits
 // for the longest segment of every round: a sliced group's BR stream ran 1.9 ms per slice
-// against 1.2 ms for its busiest job (tools/group_timeline.py).  Pieces of a segment resume
+// against 1.2 ms for its busiest job (tools/group_timeline.py).  A segment's pieces resume
 // from the weights in memory: the same SGD steps, bit for bit.
 // Partitions: each runs its own rounds over its own replicas' jobs (on its own stream), so a
 // round waits only for the longest piece among its partition's jobs.  Each job's pieces and

@@ -12,7 +12,9 @@
 // so every order of accumulation gives the same bits.
 //
 // One launch serves any number of tables (a seat of an engine or of a group's replica each)
-// through a device job table, as the chains' ChainJob does.
+// through a device job table, as the chains' ChainJob does.  The engine and group forms open with
+// engine_view / group_view (mem_view.h) and take an agent's segments from that view, as the
+// state digest does.
 //
 // The third kind, NFSP_MEM_TD (nfsp_td_table), counts what the BR net is fitted to: per M_RL
 // record k_br_targets' value r + gamma max Q_target(s2), by the stored s and argmax.  The target
@@ -27,8 +29,8 @@
 #include <string>
 #include <vector>
 
-#include "engine_internal.h"
 #include "exploit_tree.h"
+#include "mem_view.h"
 
 using namespace nfsp::eng;
 
@@ -421,9 +423,9 @@ int mt_seg(MtTab& T, const void* p, int64_t n) {
   return NFSP_OK;
 }
 
-// agent a's table of an engine at a step boundary (h: its EngineDev); TD: with the agent's own
-// target net, gamma and quirks
-int mt_engine_tab(nfsp_engine* e, const EngineDev& h, int kind, int a, int64_t* out, MtTab* T) {
+// agent a's table of an engine at a step boundary (A: the agent's view, mem_view.h); TD: with the
+// agent's own target net, gamma and quirks
+int mt_engine_tab(nfsp_engine* e, const AgentView& A, int kind, int a, int64_t* out, MtTab* T) {
   *T = MtTab{};
   T->seat = a;
   T->out = out;
@@ -432,10 +434,9 @@ int mt_engine_tab(nfsp_engine* e, const EngineDev& h, int kind, int a, int64_t* 
     T->gamma = e->cfg.gamma;
     T->quirks = e->cfg.quirks;
   }
-  if (kind == NFSP_MEM_SL) return mt_seg(*T, e->M.sl + a * e->M.sl_cap, h.sl_count[a]);
-  const RlPieces pc = rl_live_pieces(e, h, a);
-  for (int k = 0; k < pc.n; ++k) {
-    int rc = mt_seg(*T, e->M.rl + a * e->M.log_cap + pc.row[k], pc.len[k]);
+  if (kind == NFSP_MEM_SL) return mt_seg(*T, A.sl, A.sl_n);
+  for (int k = 0; k < A.n_rl; ++k) {
+    int rc = mt_seg(*T, A.rl[k], A.rl_n[k]);
     if (rc != NFSP_OK) return rc;
   }
   return NFSP_OK;
@@ -495,26 +496,26 @@ int mt_raw(nfsp_ctx* ctx, int game, int kind, int seat, const nfsp_mem_segment* 
 }
 
 int mt_engine(nfsp_engine* e, const char* what, int kind, int64_t* dev_out, nfsp_memtab_info info[2]) {
-  EngineDev h;
-  int rc = engine_quiesce(e, what, &h);
+  MemView v;
+  int rc = engine_view(e, what, &v);
   if (rc != NFSP_OK) return rc;
   std::vector<MtTab> tabs(2);
   for (int a = 0; a < 2; ++a)
-    if ((rc = mt_engine_tab(e, h, kind, a, dev_out, &tabs[a])) != NFSP_OK) return rc;
+    if ((rc = mt_engine_tab(e, v.agent[a], kind, a, dev_out, &tabs[a])) != NFSP_OK) return rc;
   return mt_run(e->ctx->stream, e->ctx->game, kind, tabs, info);
 }
 
 int mt_group(nfsp_group* g, const char* what, int kind, int64_t* dev_out, nfsp_memtab_info* info) {
   GroupState G;
-  std::vector<EngineDev> h;
-  int rc = group_quiesce(g, what, &G, &h);
+  std::vector<MemView> v;
+  int rc = group_view(g, what, &G, &v);
   if (rc != NFSP_OK) return rc;
   const MtHost* M = nullptr;
   if ((rc = mt_host(G.ctx->game, &M)) != NFSP_OK) return rc;
   std::vector<MtTab> tabs((size_t)2 * G.R);
   for (int r = 0; r < G.R; ++r)
     for (int a = 0; a < 2; ++a)
-      if ((rc = mt_engine_tab(G.eng[r], h[r], kind, a, dev_out + (int64_t)r * M->ndec * 27, &tabs[2 * r + a])) != NFSP_OK)
+      if ((rc = mt_engine_tab(G.eng[r], v[r].agent[a], kind, a, dev_out + (int64_t)r * M->ndec * 27, &tabs[2 * r + a])) != NFSP_OK)
         return rc;
   return mt_run(G.ctx->stream, G.ctx->game, kind, tabs, info);
 }

@@ -25,12 +25,16 @@
 //
 // k_state_digest reads the restored state where it lies, through a table of at most 12
 // segments: a load proves that every byte landed without reading any of it back.
+//
+// Which records are live and where they lie is mem_view.h's: the entry points open with
+// engine_view / group_view (at rest, with the view of the memories), and the digest, the writer,
+// the loader and the size checks walk its segments.  Only the C ABI is called from other files.
 #include <cstddef>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "engine_internal.h"
+#include "mem_view.h"
 #include "state_blob.h"
 
 namespace nn = nfsp::nn;
@@ -200,23 +204,6 @@ constexpr uint64_t ST_ROLLOUTS_WORD = offsetof(EngineDev, rollouts) / 8;
 
 inline uint64_t header_bytes(uint32_t n_sections) { return sizeof(BlobHeader) + sizeof(BlobSection) * (uint64_t)n_sections; }
 
-// live M_RL records and stored M_SL rows of agent a in an EngineDev
-inline int64_t rl_live(const EngineDev& h, const nfsp_engine_cfg& c, int a) {
-  return h.rl_total[a] < c.rl_capacity ? h.rl_total[a] : c.rl_capacity;
-}
-
-// an EngineDev that this cfg can have produced at a step boundary (bounds every size derived
-// from it: copies and digest segments stay inside the memories)
-int st_check(const EngineDev& h, const nfsp_engine_cfg& c, const char* what) {
-  for (int a = 0; a < 2; ++a) {
-    const bool ok = h.rl_total[a] >= 0 && h.sl_total[a] >= 0 && h.sl_count[a] >= 0 &&
-                    h.sl_count[a] <= c.sl_capacity && h.sl_count[a] <= h.sl_total[a];
-    if (!ok) return nfsp::fail(NFSP_EINVAL, std::string(what) + ": memory counters out of range");
-  }
-  if (h.rollouts < 0 || h.hands < 0) return nfsp::fail(NFSP_EINVAL, std::string(what) + ": negative hand count");
-  return NFSP_OK;
-}
-
 HostRec host_rec(const nfsp_engine* e) {
   HostRec r;
   memset(&r, 0, sizeof(r));
@@ -308,9 +295,9 @@ int blob_parse(const void* buf, int64_t n, BlobView* v) {
     int rc = st_check(st, c, "state blob");
     if (rc != NFSP_OK) return rc;
     if (hr.g < 0 || st.rollouts != hr.g) return bad("hand counters disagree");
-    const uint64_t rl = (uint64_t)(rl_live(st, c, 0) + rl_live(st, c, 1)) * sizeof(RlRec);
-    const uint64_t sl = (uint64_t)(st.sl_count[0] + st.sl_count[1]) * sizeof(SlRec);
-    if (v->sec[k0 + 3].bytes != rl || v->sec[k0 + 4].bytes != sl) return bad("memory sections do not match the counters");
+    const MemTotals m = mem_totals(st, c.rl_capacity);
+    if (v->sec[k0 + 3].bytes != (uint64_t)m.rl * sizeof(RlRec) || v->sec[k0 + 4].bytes != (uint64_t)m.sl * sizeof(SlRec))
+      return bad("memory sections do not match the counters");
   }
   if (h.kind == KIND_GROUP) {
     GroupRec gr;
@@ -345,62 +332,19 @@ void fill_info(const BlobView& v, nfsp_state_info* info) {
 // ---------------------------------------------------------------------------
 // engine <-> payload
 // ---------------------------------------------------------------------------
-// the engine's streams, idle
-int engine_sync(nfsp_engine* e) {
-  NFSP_HIP(hipStreamSynchronize(e->ctx->stream));
-  for (hipStream_t st : {e->s_ar, e->s_br[0], e->s_br[1]})
-    if (st) NFSP_HIP(hipStreamSynchronize(st));
-  return NFSP_OK;
+uint64_t engine_payload_bytes(const MemView& v) {
+  return sizeof(HostRec) + sizeof(EngineDev) + NETS_BYTES + v.total.bytes();
 }
-
-int boundary_check(const nfsp_engine* e, const char* what) {
-  if (e->pending_update || e->xchg_pending)
-    return nfsp::fail(NFSP_EINVAL, std::string(what) + ": not at a step boundary (a rollout awaits nfsp_engine_update, or an exchange is pending)");
-  if (e->xchg_every > 0 && e->xchg_calls % e->xchg_every != 0)
-    return nfsp::fail(NFSP_EINVAL, std::string(what) + ": not at a step boundary (the exchange is due only after further learner calls)");
-  if (e->rollouts % (uint64_t)e->slices != 0)
-    return nfsp::fail(NFSP_EINVAL, std::string(what) + ": not at a step boundary (the step's slices are not all played)");
-  return NFSP_OK;
-}
-
-int read_st(nfsp_engine* e, EngineDev* h) {
-  NFSP_HIP(hipMemcpyAsync(h, e->st, sizeof(*h), hipMemcpyDeviceToHost, e->ctx->stream));
-  NFSP_HIP(hipStreamSynchronize(e->ctx->stream));
-  int rc = st_check(*h, e->cfg, "engine state");
-  if (rc != NFSP_OK) return rc;
-  if ((uint64_t)h->rollouts != e->rollouts) return nfsp::fail(NFSP_EINVAL, "engine state: the device's rollout count differs from the host's");
-  return NFSP_OK;
-}
-
-// an agent's live M_RL records as (first row, rows) pieces of its circular log, oldest first
-struct Pieces {
-  int n = 0;
-  int64_t row[2], len[2];
-};
-Pieces rl_pieces(int64_t rl_total, int64_t live, int64_t log_cap) {
-  Pieces p;
-  if (live <= 0) return p;
-  const int64_t r0 = (rl_total - live) % log_cap;
-  const int64_t l0 = live < log_cap - r0 ? live : log_cap - r0;
-  p.row[p.n] = r0;
-  p.len[p.n++] = l0;
-  if (l0 < live) {
-    p.row[p.n] = 0;
-    p.len[p.n++] = live - l0;
-  }
-  return p;
-}
-
-uint64_t engine_payload_bytes(const nfsp_engine* e, const EngineDev& h) {
-  return sizeof(HostRec) + sizeof(EngineDev) + NETS_BYTES +
-         (uint64_t)(rl_live(h, e->cfg, 0) + rl_live(h, e->cfg, 1)) * sizeof(RlRec) +
-         (uint64_t)(h.sl_count[0] + h.sl_count[1]) * sizeof(SlRec);
+uint64_t group_bytes(const std::vector<MemView>& v) {
+  uint64_t total = header_bytes(1 + ENGINE_SECTIONS * (uint32_t)v.size()) + GROUP_BYTES;
+  for (const MemView& m : v) total += engine_payload_bytes(m);
+  return total;
 }
 
 // Digest of the engine's payload as it would be saved now, its first word at payload index
 // `base`: the HOST section (and the canonical `rollouts` word of ST) on the host, everything
-// else by the kernel, in place.  Adds into out.
-int engine_digest(nfsp_engine* e, const EngineDev& h, uint64_t base, uint64_t out[2], float* ms = nullptr,
+// else by the kernel, in place, along the view's segments.  Adds into out.
+int engine_digest(nfsp_engine* e, const MemView& v, uint64_t base, uint64_t out[2], float* ms = nullptr,
                   uint64_t* bytes = nullptr) {
   const HostRec hr = host_rec(e);
   digest_words(out, &hr, sizeof(hr) / 8, base);
@@ -413,26 +357,41 @@ int engine_digest(nfsp_engine* e, const EngineDev& h, uint64_t base, uint64_t ou
   const uint64_t st_first = at;
   add(e->st, sizeof(EngineDev) / 8);
   add(e->w, NETS_BYTES / 8);
-  for (int a = 0; a < 2; ++a) {
-    const Pieces p = rl_pieces(h.rl_total[a], rl_live(h, e->cfg, a), e->M.log_cap);
-    for (int k = 0; k < p.n; ++k) add(e->M.rl + a * e->M.log_cap + p.row[k], (uint64_t)p.len[k] * (sizeof(RlRec) / 8));
-  }
-  for (int a = 0; a < 2; ++a) add(e->M.sl + a * e->M.sl_cap, (uint64_t)h.sl_count[a] * (sizeof(SlRec) / 8));
+  for (const AgentView& A : v.agent)
+    for (int k = 0; k < A.n_rl; ++k) add(A.rl[k], (uint64_t)A.rl_n[k] * (sizeof(RlRec) / 8));
+  for (const AgentView& A : v.agent) add(A.sl, (uint64_t)A.sl_n * (sizeof(SlRec) / 8));
   static_assert(2 + 4 + 2 <= DIGEST_MAX_SEG, "segment table");
   if (bytes) *bytes = (at - base) * 8;
   int rc = digest_run(e, T, out, ms);
   if (rc != NFSP_OK) return rc;
   // ST.rollouts counts slices on the device and hands per lane in the payload
   uint64_t dev[2] = {0, 0}, canon[2] = {0, 0};
-  digest_add(dev[0], dev[1], (uint64_t)h.rollouts, st_first + ST_ROLLOUTS_WORD);
+  digest_add(dev[0], dev[1], (uint64_t)v.st.rollouts, st_first + ST_ROLLOUTS_WORD);
   digest_add(canon[0], canon[1], (uint64_t)hr.g, st_first + ST_ROLLOUTS_WORD);
   out[0] += canon[0] - dev[0];
   out[1] += canon[1] - dev[1];
   return NFSP_OK;
 }
 
-// the engine's five sections at `at` of the blob (streams idle, h = its EngineDev)
-int engine_write(nfsp_engine* e, const EngineDev& h, unsigned char* buf, uint64_t* at, BlobSection* sec, uint32_t rep) {
+// The blob's two memory sections along the view's segments, saved from them or (load: the
+// sections are only read) loaded into them: RL, each agent's records oldest first, then SL.
+int copy_memories(const MemView& v, unsigned char* rl, unsigned char* sl, bool load) {
+  auto copy = [load](unsigned char*& host, void* dev, size_t nb) {
+    if (nb) NFSP_HIP(load ? hipMemcpy(dev, host, nb, hipMemcpyHostToDevice) : hipMemcpy(host, dev, nb, hipMemcpyDeviceToHost));
+    host += nb;
+    return (int)NFSP_OK;
+  };
+  int rc = NFSP_OK;
+  for (const AgentView& A : v.agent)
+    for (int k = 0; k < A.n_rl; ++k)
+      if ((rc = copy(rl, A.rl[k], (size_t)A.rl_n[k] * sizeof(RlRec))) != NFSP_OK) return rc;
+  for (const AgentView& A : v.agent)
+    if ((rc = copy(sl, A.sl, (size_t)A.sl_n * sizeof(SlRec))) != NFSP_OK) return rc;
+  return NFSP_OK;
+}
+
+// the engine's five sections at `at` of the blob (the engine at rest, v = its view)
+int engine_write(nfsp_engine* e, const MemView& v, unsigned char* buf, uint64_t* at, BlobSection* sec, uint32_t rep) {
   auto begin = [&](int k, uint32_t kind, uint64_t bytes) {
     sec[k] = BlobSection{kind, rep, *at, bytes};
     unsigned char* p = buf + *at;
@@ -441,27 +400,13 @@ int engine_write(nfsp_engine* e, const EngineDev& h, unsigned char* buf, uint64_
   };
   const HostRec hr = host_rec(e);
   memcpy(begin(0, SEC_HOST, sizeof(hr)), &hr, sizeof(hr));
-  EngineDev st = h;
+  EngineDev st = v.st;
   st.rollouts = hr.g;
   memcpy(begin(1, SEC_ST, sizeof(st)), &st, sizeof(st));
   NFSP_HIP(hipMemcpy(begin(2, SEC_NETS, NETS_BYTES), e->w, NETS_BYTES, hipMemcpyDeviceToHost));
-  const int64_t live[2] = {rl_live(h, e->cfg, 0), rl_live(h, e->cfg, 1)};
-  unsigned char* p = begin(3, SEC_RL, (uint64_t)(live[0] + live[1]) * sizeof(RlRec));
-  for (int a = 0; a < 2; ++a) {
-    const Pieces pc = rl_pieces(h.rl_total[a], live[a], e->M.log_cap);
-    for (int k = 0; k < pc.n; ++k) {
-      const size_t nb = (size_t)pc.len[k] * sizeof(RlRec);
-      NFSP_HIP(hipMemcpy(p, e->M.rl + a * e->M.log_cap + pc.row[k], nb, hipMemcpyDeviceToHost));
-      p += nb;
-    }
-  }
-  p = begin(4, SEC_SL, (uint64_t)(h.sl_count[0] + h.sl_count[1]) * sizeof(SlRec));
-  for (int a = 0; a < 2; ++a) {
-    const size_t nb = (size_t)h.sl_count[a] * sizeof(SlRec);
-    if (nb) NFSP_HIP(hipMemcpy(p, e->M.sl + a * e->M.sl_cap, nb, hipMemcpyDeviceToHost));
-    p += nb;
-  }
-  return NFSP_OK;
+  unsigned char* rl = begin(3, SEC_RL, (uint64_t)v.total.rl * sizeof(RlRec));
+  unsigned char* sl = begin(4, SEC_SL, (uint64_t)v.total.sl * sizeof(SlRec));
+  return copy_memories(v, rl, sl, false);
 }
 
 void header_init(BlobHeader* h, uint32_t kind, uint32_t replicas, const nfsp_engine* e0) {
@@ -506,35 +451,22 @@ int compat_check(const nfsp_engine* e, const HostRec& hr, int replica = -1) {
 }
 
 // Replica payload k0.. of the blob into the engine (validated, compatible, streams idle).  The
-// target's own slicing: rollouts = g * slices, record k at row k % log_cap.
+// target's own slicing: rollouts = g * slices, and the blob's counters viewed in the target's
+// memories, so record k lands at row k % log_cap.
 int engine_restore(nfsp_engine* e, const BlobView& v, int k0) {
   HostRec hr;
   EngineDev st;
   memcpy(&hr, v.at(k0 + 0), sizeof(hr));
   memcpy(&st, v.at(k0 + 1), sizeof(st));
   hipStream_t s = e->ctx->stream;
-  const int64_t live[2] = {rl_live(st, e->cfg, 0), rl_live(st, e->cfg, 1)};
   const uint64_t rollouts = (uint64_t)hr.g * (uint64_t)e->slices;
   EngineDev dev = st;
   dev.rollouts = (int64_t)rollouts;
   // synchronous copies from the caller's (pageable) buffer; nothing else runs on the engine
   NFSP_HIP(hipMemcpy(e->st, &dev, sizeof(dev), hipMemcpyHostToDevice));
   NFSP_HIP(hipMemcpy(e->w, v.at(k0 + 2), NETS_BYTES, hipMemcpyHostToDevice));
-  const unsigned char* p = v.at(k0 + 3);
-  for (int a = 0; a < 2; ++a) {
-    const Pieces pc = rl_pieces(st.rl_total[a], live[a], e->M.log_cap);
-    for (int k = 0; k < pc.n; ++k) {
-      const size_t nb = (size_t)pc.len[k] * sizeof(RlRec);
-      NFSP_HIP(hipMemcpy(e->M.rl + a * e->M.log_cap + pc.row[k], p, nb, hipMemcpyHostToDevice));
-      p += nb;
-    }
-  }
-  p = v.at(k0 + 4);
-  for (int a = 0; a < 2; ++a) {
-    const size_t nb = (size_t)st.sl_count[a] * sizeof(SlRec);
-    if (nb) NFSP_HIP(hipMemcpy(e->M.sl + a * e->M.sl_cap, p, nb, hipMemcpyHostToDevice));
-    p += nb;
-  }
+  int rc = copy_memories(mem_view(e, st), const_cast<unsigned char*>(v.at(k0 + 3)), const_cast<unsigned char*>(v.at(k0 + 4)), true);
+  if (rc != NFSP_OK) return rc;
   // no res_head entry of an earlier life may match a restored learn_tag
   NFSP_HIP(hipMemsetAsync(e->LBs[0].res_head, 0, sizeof(unsigned long long) * 2 * (size_t)e->M.sl_cap, s));
   if (e->xchg_w0)                       // W0 = the restored AR nets (nfsp_engine_set_exchange's rule)
@@ -595,26 +527,22 @@ extern "C" int nfsp_state_digest(const void* payload, int64_t n, uint64_t out[2]
 
 extern "C" int nfsp_engine_state_digest(nfsp_engine* e, uint64_t out[2]) {
   NFSP_REQUIRE(e && out, "null argument");
-  int rc = boundary_check(e, "nfsp_engine_state_digest");
+  MemView v;
+  int rc = engine_view(e, "nfsp_engine_state_digest", &v);
   if (rc != NFSP_OK) return rc;
-  if ((rc = engine_sync(e)) != NFSP_OK) return rc;
-  EngineDev h;
-  if ((rc = read_st(e, &h)) != NFSP_OK) return rc;
   out[0] = out[1] = 0;
-  return engine_digest(e, h, 0, out);
+  return engine_digest(e, v, 0, out);
 }
 
 extern "C" int nfsp_engine_state_digest_timed(nfsp_engine* e, uint64_t out[2], double* ms, int64_t* bytes) {
   NFSP_REQUIRE(e && out && ms && bytes, "null argument");
-  int rc = boundary_check(e, "nfsp_engine_state_digest_timed");
+  MemView v;
+  int rc = engine_view(e, "nfsp_engine_state_digest_timed", &v);
   if (rc != NFSP_OK) return rc;
-  if ((rc = engine_sync(e)) != NFSP_OK) return rc;
-  EngineDev h;
-  if ((rc = read_st(e, &h)) != NFSP_OK) return rc;
   out[0] = out[1] = 0;
   float t = 0.f;
   uint64_t nb = 0;
-  if ((rc = engine_digest(e, h, 0, out, &t, &nb)) != NFSP_OK) return rc;
+  if ((rc = engine_digest(e, v, 0, out, &t, &nb)) != NFSP_OK) return rc;
   *ms = t;
   *bytes = (int64_t)(nb - sizeof(HostRec));     // what the kernel read
   return NFSP_OK;
@@ -623,31 +551,27 @@ extern "C" int nfsp_engine_state_digest_timed(nfsp_engine* e, uint64_t out[2], d
 extern "C" int nfsp_engine_state_bytes(nfsp_engine* e, int64_t* out) {
   NFSP_REQUIRE(e && out, "null argument");
   NFSP_REQUIRE(standalone(e), "a replica of an engine group is saved by nfsp_group_save_state");
-  int rc = boundary_check(e, "nfsp_engine_state_bytes");
+  MemView v;
+  int rc = engine_view(e, "nfsp_engine_state_bytes", &v);
   if (rc != NFSP_OK) return rc;
-  if ((rc = engine_sync(e)) != NFSP_OK) return rc;
-  EngineDev h;
-  if ((rc = read_st(e, &h)) != NFSP_OK) return rc;
-  *out = (int64_t)(header_bytes(ENGINE_SECTIONS) + engine_payload_bytes(e, h));
+  *out = (int64_t)(header_bytes(ENGINE_SECTIONS) + engine_payload_bytes(v));
   return NFSP_OK;
 }
 
 extern "C" int nfsp_engine_save_state(nfsp_engine* e, void* host_buf, int64_t cap, int64_t* written) {
   NFSP_REQUIRE(e && host_buf && written, "null argument");
   NFSP_REQUIRE(standalone(e), "a replica of an engine group is saved by nfsp_group_save_state");
-  int rc = boundary_check(e, "nfsp_engine_save_state");
+  MemView v;
+  int rc = engine_view(e, "nfsp_engine_save_state", &v);
   if (rc != NFSP_OK) return rc;
-  if ((rc = engine_sync(e)) != NFSP_OK) return rc;
-  EngineDev h;
-  if ((rc = read_st(e, &h)) != NFSP_OK) return rc;
   BlobHeader hd;
   header_init(&hd, KIND_ENGINE, 1, e);
-  const uint64_t total = hd.payload_offset + engine_payload_bytes(e, h);
+  const uint64_t total = hd.payload_offset + engine_payload_bytes(v);
   NFSP_REQUIRE(cap >= 0 && (uint64_t)cap >= total, "nfsp_engine_save_state: the buffer is smaller than nfsp_engine_state_bytes");
   unsigned char* buf = static_cast<unsigned char*>(host_buf);
   std::vector<BlobSection> sec(hd.n_sections);
   uint64_t at = hd.payload_offset;
-  if ((rc = engine_write(e, h, buf, &at, sec.data(), 0)) != NFSP_OK) return rc;
+  if ((rc = engine_write(e, v, buf, &at, sec.data(), 0)) != NFSP_OK) return rc;
   header_finish(&hd, sec, buf, at);
   *written = (int64_t)at;
   return NFSP_OK;
@@ -664,108 +588,36 @@ extern "C" int nfsp_engine_load_state(nfsp_engine* e, const void* host_buf, int6
   HostRec hr;
   memcpy(&hr, v.at(0), sizeof(hr));
   if ((rc = compat_check(e, hr)) != NFSP_OK) return rc;
-  NFSP_REQUIRE(!e->pending_update && !e->xchg_pending,
-               "nfsp_engine_load_state: not at a step boundary (a rollout or an exchange is pending)");
-  if ((rc = engine_sync(e)) != NFSP_OK) return rc;
+  if ((rc = engine_rest(e, "nfsp_engine_load_state", true)) != NFSP_OK) return rc;
   if ((rc = engine_restore(e, v, 0)) != NFSP_OK) return rc;
   // the device now holds the blob's payload: prove it in place
-  EngineDev h;
-  if ((rc = read_st(e, &h)) != NFSP_OK) return rc;
+  MemView mv;
+  if ((rc = engine_view(e, "nfsp_engine_load_state", &mv)) != NFSP_OK) return rc;
   uint64_t d[2] = {0, 0};
-  if ((rc = engine_digest(e, h, 0, d)) != NFSP_OK) return rc;
+  if ((rc = engine_digest(e, mv, 0, d)) != NFSP_OK) return rc;
   if (d[0] != v.h.digest[0] || d[1] != v.h.digest[1])
     return nfsp::fail(NFSP_EHIP, "nfsp_engine_load_state: the device state's digest differs from the blob's after the copy");
   return NFSP_OK;
 }
 
 // ---- groups
-namespace {
-int group_boundary(const GroupState& G, const char* what) {
-  for (int r = 0; r < G.R; ++r) {
-    const nfsp_engine* e = G.eng[r];
-    if (e->pending_update || e->rollouts % (uint64_t)e->slices != 0 || e->rollouts != G.eng[0]->rollouts)
-      return nfsp::fail(NFSP_EINVAL, std::string(what) + ": not at a step boundary");
-  }
-  if (G.xchg_every > 0 && *G.calls % G.xchg_every != 0)
-    return nfsp::fail(NFSP_EINVAL, std::string(what) + ": not at a step boundary (the exchange is due only after further learner calls)");
-  return NFSP_OK;
-}
-
-int group_sync(const GroupState& G) {
-  NFSP_HIP(hipStreamSynchronize(G.ctx->stream));
-  for (int k = 0; k < G.n_streams; ++k)
-    if (G.streams[k]) NFSP_HIP(hipStreamSynchronize(G.streams[k]));
-  return NFSP_OK;
-}
-
-int group_read(const GroupState& G, std::vector<EngineDev>* h, uint64_t* total) {
-  h->resize(G.R);
-  *total = header_bytes(1 + ENGINE_SECTIONS * G.R) + GROUP_BYTES;
-  for (int r = 0; r < G.R; ++r) {
-    int rc = read_st(G.eng[r], &(*h)[r]);
-    if (rc != NFSP_OK) return rc;
-    *total += engine_payload_bytes(G.eng[r], (*h)[r]);
-  }
-  return NFSP_OK;
-}
-}  // namespace
-
-// ---- for the other readers of the memories in place (memtab.hip)
-namespace nfsp {
-namespace eng {
-int engine_quiesce(nfsp_engine* e, const char* what, EngineDev* h) {
-  int rc = boundary_check(e, what);
-  if (rc != NFSP_OK) return rc;
-  if ((rc = engine_sync(e)) != NFSP_OK) return rc;
-  return read_st(e, h);
-}
-
-int group_quiesce(nfsp_group* g, const char* what, GroupState* G, std::vector<EngineDev>* h) {
-  int rc = group_state(g, G);
-  if (rc != NFSP_OK) return rc;
-  if ((rc = group_boundary(*G, what)) != NFSP_OK) return rc;
-  if ((rc = group_sync(*G)) != NFSP_OK) return rc;
-  uint64_t total = 0;
-  return group_read(*G, h, &total);
-}
-
-RlPieces rl_live_pieces(const nfsp_engine* e, const EngineDev& h, int a) {
-  const Pieces p = rl_pieces(h.rl_total[a], rl_live(h, e->cfg, a), e->M.log_cap);
-  RlPieces out;
-  out.n = p.n;
-  for (int k = 0; k < p.n; ++k) {
-    out.row[k] = p.row[k];
-    out.len[k] = p.len[k];
-  }
-  return out;
-}
-}  // namespace eng
-}  // namespace nfsp
-
 extern "C" int nfsp_group_state_bytes(nfsp_group* g, int64_t* out) {
   NFSP_REQUIRE(g && out, "null argument");
   GroupState G;
-  int rc = group_state(g, &G);
+  std::vector<MemView> v;
+  int rc = group_view(g, "nfsp_group_state_bytes", &G, &v);
   if (rc != NFSP_OK) return rc;
-  if ((rc = group_boundary(G, "nfsp_group_state_bytes")) != NFSP_OK) return rc;
-  if ((rc = group_sync(G)) != NFSP_OK) return rc;
-  std::vector<EngineDev> h;
-  uint64_t total = 0;
-  if ((rc = group_read(G, &h, &total)) != NFSP_OK) return rc;
-  *out = (int64_t)total;
+  *out = (int64_t)group_bytes(v);
   return NFSP_OK;
 }
 
 extern "C" int nfsp_group_save_state(nfsp_group* g, void* host_buf, int64_t cap, int64_t* written) {
   NFSP_REQUIRE(g && host_buf && written, "null argument");
   GroupState G;
-  int rc = group_state(g, &G);
+  std::vector<MemView> v;
+  int rc = group_view(g, "nfsp_group_save_state", &G, &v);
   if (rc != NFSP_OK) return rc;
-  if ((rc = group_boundary(G, "nfsp_group_save_state")) != NFSP_OK) return rc;
-  if ((rc = group_sync(G)) != NFSP_OK) return rc;
-  std::vector<EngineDev> h;
-  uint64_t total = 0;
-  if ((rc = group_read(G, &h, &total)) != NFSP_OK) return rc;
+  const uint64_t total = group_bytes(v);
   NFSP_REQUIRE(cap >= 0 && (uint64_t)cap >= total, "nfsp_group_save_state: the buffer is smaller than nfsp_group_state_bytes");
   unsigned char* buf = static_cast<unsigned char*>(host_buf);
   BlobHeader hd;
@@ -789,7 +641,7 @@ extern "C" int nfsp_group_save_state(nfsp_group* g, void* host_buf, int64_t cap,
   }
   at += GROUP_BYTES;
   for (int r = 0; r < G.R; ++r)
-    if ((rc = engine_write(G.eng[r], h[r], buf, &at, sec.data() + 1 + ENGINE_SECTIONS * r, (uint32_t)r)) != NFSP_OK)
+    if ((rc = engine_write(G.eng[r], v[r], buf, &at, sec.data() + 1 + ENGINE_SECTIONS * r, (uint32_t)r)) != NFSP_OK)
       return rc;
   header_finish(&hd, sec, buf, at);
   *written = (int64_t)at;
@@ -811,9 +663,8 @@ extern "C" int nfsp_group_load_state(nfsp_group* g, const void* host_buf, int64_
     HostRec hr;
     memcpy(&hr, v.at(v.engine_sec(r)), sizeof(hr));
     if ((rc = compat_check(G.eng[r], hr, r)) != NFSP_OK) return rc;
-    NFSP_REQUIRE(!G.eng[r]->pending_update, "nfsp_group_load_state: not at a step boundary");
   }
-  if ((rc = group_sync(G)) != NFSP_OK) return rc;
+  if ((rc = group_rest(g, "nfsp_group_load_state", true)) != NFSP_OK) return rc;
   NFSP_HIP(hipMemcpy(G.w0, v.at(0) + sizeof(gr), sizeof(float) * 6 * nn::NP, hipMemcpyHostToDevice));
   for (int r = 0; r < G.R; ++r)
     if ((rc = engine_restore(G.eng[r], v, v.engine_sec(r))) != NFSP_OK) return rc;
@@ -828,10 +679,10 @@ extern "C" int nfsp_group_load_state(nfsp_group* g, const void* host_buf, int64_
   T.seg[0] = DigestSeg{reinterpret_cast<const uint64_t*>(G.w0), sizeof(float) * 6 * nn::NP / 8, sizeof(gr) / 8};
   if ((rc = digest_run(G.eng[0], T, d)) != NFSP_OK) return rc;
   for (int r = 0; r < G.R; ++r) {
-    EngineDev h;
-    if ((rc = read_st(G.eng[r], &h)) != NFSP_OK) return rc;
+    MemView mv;
+    if ((rc = engine_view(G.eng[r], "nfsp_group_load_state", &mv)) != NFSP_OK) return rc;
     const uint64_t base = (v.sec[v.engine_sec(r)].offset - v.h.payload_offset) / 8;
-    if ((rc = engine_digest(G.eng[r], h, base, d)) != NFSP_OK) return rc;
+    if ((rc = engine_digest(G.eng[r], mv, base, d)) != NFSP_OK) return rc;
   }
   if (d[0] != v.h.digest[0] || d[1] != v.h.digest[1])
     return nfsp::fail(NFSP_EHIP, "nfsp_group_load_state: the device state's digest differs from the blob's after the copy");

@@ -100,3 +100,37 @@ def rl_meta(n, rng, a):
 def bits_of(x30):
     """Observation words of fp32 0/1 rows [n, 30]."""
     return ((np.asarray(x30) != 0).astype(np.int64) << np.arange(30, dtype=np.int64)).sum(axis=1)
+
+
+# shared by the GPU tests of the tables (test_gpu_memtab.py, test_gpu_qreport.py, test_gpu_checkpoint.py)
+_CTX = {}
+_TREES = {}
+
+
+def game_id(pkg, game):
+    return pkg.native.GAME_KUHN if game == "kuhn" else pkg.native.GAME_LEDUC
+
+
+def ctx_of(pkg, game):
+    """(a context, the game's tree), one of each per game and session."""
+    if game not in _CTX:
+        _CTX[game] = pkg.native.Context(1, game=game_id(pkg, game))
+        _TREES[game] = pkg.evaluation.GameTree(game_id(pkg, game))
+    return _CTX[game], _TREES[game]
+
+
+def dev(words):
+    """Packed records (uint32 rows) on the device."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).cuda()
+
+
+def export_rl(m, rl_total, live):
+    """The live M_RL records of ``memories(agent)``'s fp32 export m, oldest first: record k of the
+    agent's rl_total lies at row k % log_cap.  (s words, s2 words, a [live, 3], stored meta words)."""
+    import torch
+    idx = torch.as_tensor((int(rl_total) - live + np.arange(live)) % m["log_cap"], device=m["rl_s"].device)
+    a = m["rl_a"][idx].cpu().numpy()
+    r2 = np.rint(m["rl_r"][idx].cpu().numpy().astype(np.float64) * 2).astype(np.int64)
+    meta = np.argmax(a, axis=1).astype(np.int64) | (m["rl_t"][idx].cpu().numpy().astype(np.int64) << 8) | ((r2 & 0xFF) << 16)
+    return bits_of(m["rl_s"][idx].cpu().numpy()), bits_of(m["rl_s2"][idx].cpu().numpy()), a, meta

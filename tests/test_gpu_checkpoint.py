@@ -297,3 +297,48 @@ def test_refusals_leave_the_engine_as_it_was(pkg, tmp_path):
     # and the good file still loads: back to the saved state
     e.load(good)
     assert e.state_digest() == before and np.array_equal(bits(nets(e)), bits(w_before))
+
+
+def test_the_readers_of_the_memories_agree(pkg):
+    """The digest, the checkpoint's writer and loader and the memory tables read one view of the
+    memories (csrc/mem_view.h): at every step boundary the blob's RL and SL sections, counted by
+    the raw table form, are the engine form's tables, and the device digest is the blob's --
+    before the log is full, after it has wrapped, and in an engine of another log_cap."""
+    import memtab_ref as mr
+    ck, ev = pkg.checkpoint, pkg.evaluation
+    ctx, tree = mr.ctx_of(pkg, "leduc")
+    kw = dict(n_lanes=256, rl_capacity=1024, sl_capacity=2048, eta=0.3, seed=77)
+
+    def agree(eng, blob):
+        p = ck.parse(blob)
+        assert eng.state_digest() == p["header"]["digest"]
+        for kind, key in ((mr.RL, "rl"), (mr.SL, "sl")):
+            out, infos = None, []
+            for seat in (0, 1):                 # the agent's slice of the section, oldest first
+                recs = p["engines"][0][key][seat].copy()
+                words = recs.view(np.uint32).reshape(-1, recs.dtype.itemsize // 4)
+                out, info = ev.memory_table(ctx, kind, seat, [mr.dev(words)] if len(words) else [], out=out, tree=tree)
+                assert info["records"] == len(recs)
+                infos.append(info)
+            t, tinfo = eng.memory_table(kind)
+            assert tinfo == infos
+            assert np.array_equal(t.raw, out.cpu().numpy())
+
+    e = pkg.engine.SelfPlayEngine(ctx, init_seed=3, slices=4, **kw)
+    log_cap = e.memories(0)["log_cap"]
+    assert log_cap == 1280
+    totals = []
+    for _ in range(6):
+        e.step()
+        blob = ck._blob(e)
+        agree(e, blob)
+        totals += e.stats()["rl_total"]
+    print(f"rl_total per boundary and agent {totals}")
+    assert min(totals) < kw["rl_capacity"] and max(totals) > log_cap
+    t = pkg.engine.SelfPlayEngine(ctx, init_seed=5, slices=1, **kw)
+    assert t.memories(0)["log_cap"] == 2048
+    ck.load_bytes(t, blob)
+    agree(t, blob)
+    assert t.state_digest() == e.state_digest()
+    t.close()
+    e.close()

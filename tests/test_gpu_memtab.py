@@ -6,27 +6,11 @@ import pytest
 import torch
 
 import memtab_ref as mr
+from memtab_ref import ctx_of, dev
 
 pytestmark = pytest.mark.gpu
 
 GAMES = ("leduc", "kuhn")
-_CTX = {}
-_TREES = {}
-
-
-def game_id(pkg, game):
-    return pkg.native.GAME_KUHN if game == "kuhn" else pkg.native.GAME_LEDUC
-
-
-def ctx_of(pkg, game):
-    if game not in _CTX:
-        _CTX[game] = pkg.native.Context(1, game=game_id(pkg, game))
-        _TREES[game] = pkg.evaluation.GameTree(game_id(pkg, game))
-    return _CTX[game], _TREES[game]
-
-
-def dev(words):
-    return torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).cuda()
 
 
 def synth(tree, seat, n, rng, keys=None):
@@ -200,12 +184,8 @@ def export_tables(eng, tree, st):
         raw, info = mr.table(tree, p, mr.SL, mr.bits_of(m["sl_s"][:n].cpu().numpy()), a=m["sl_a"][:n].cpu().numpy())
         raws[mr.SL] += raw
         infos[mr.SL].append(info)
-        live = int(st["rl_size"][p])
-        idx = torch.as_tensor((int(st["rl_total"][p]) - live + np.arange(live)) % m["log_cap"], device=m["rl_s"].device)
-        a = m["rl_a"][idx].cpu().numpy()
-        r2 = np.rint(m["rl_r"][idx].cpu().numpy().astype(np.float64) * 2).astype(np.int64)
-        meta = np.argmax(a, axis=1).astype(np.int64) | (m["rl_t"][idx].cpu().numpy().astype(np.int64) << 8) | ((r2 & 0xFF) << 16)
-        raw, info = mr.table(tree, p, mr.RL, mr.bits_of(m["rl_s"][idx].cpu().numpy()), meta=meta)
+        s, _, _, meta = mr.export_rl(m, st["rl_total"][p], int(st["rl_size"][p]))
+        raw, info = mr.table(tree, p, mr.RL, s, meta=meta)
         raws[mr.RL] += raw
         infos[mr.RL].append(info)
     return raws, infos

@@ -8,6 +8,7 @@ import torch
 
 import memtab_ref as mr
 import tdtab_ref as tr
+from memtab_ref import ctx_of, dev
 
 pytestmark = pytest.mark.gpu
 
@@ -15,23 +16,6 @@ GAMES = ("leduc", "kuhn")
 TB, LIN = tr.TERMINAL_BOOTSTRAP, tr.EXT_LINEAR_Q
 QUIRKS = (0, TB, LIN, LIN | TB)
 GAMMAS = (0.0, 0.95, 1.0)
-_CTX = {}
-_TREES = {}
-
-
-def game_id(pkg, game):
-    return pkg.native.GAME_KUHN if game == "kuhn" else pkg.native.GAME_LEDUC
-
-
-def ctx_of(pkg, game):
-    if game not in _CTX:
-        _CTX[game] = pkg.native.Context(1, game=game_id(pkg, game))
-        _TREES[game] = pkg.evaluation.GameTree(game_id(pkg, game))
-    return _CTX[game], _TREES[game]
-
-
-def dev(words):
-    return torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).cuda()
 
 
 def net(pkg, seed, scale=1.0):
@@ -284,15 +268,10 @@ def export_td(eng, tree, st, ctx):
     raw, infos = np.zeros((tree.ndec, 3, 3, 3), np.int64), []
     for p in (0, 1):
         m = eng.memories(p)
-        live = int(st["rl_size"][p])
-        idx = torch.as_tensor((int(st["rl_total"][p]) - live + np.arange(live)) % m["log_cap"], device=m["rl_s"].device)
-        a = m["rl_a"][idx].cpu().numpy()
-        r2 = np.rint(m["rl_r"][idx].cpu().numpy().astype(np.float64) * 2).astype(np.int64)
-        meta = np.argmax(a, axis=1).astype(np.int64) | (m["rl_t"][idx].cpu().numpy().astype(np.int64) << 8) | ((r2 & 0xFF) << 16)
-        s2 = mr.bits_of(m["rl_s2"][idx].cpu().numpy())
+        s, s2, _, meta = mr.export_rl(m, st["rl_total"][p], int(st["rl_size"][p]))
         q = int(eng.cfg.quirks)
         qt = tr.forward(ctx, eng.get_weights(p, 2), tr.head_act(q), s2)
-        one, info = tr.table(tree, p, mr.bits_of(m["rl_s"][idx].cpu().numpy()), meta, qt, float(eng.cfg.gamma), q)
+        one, info = tr.table(tree, p, s, meta, qt, float(eng.cfg.gamma), q)
         raw += one
         infos.append(info)
     return raw, infos
