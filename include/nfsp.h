@@ -814,6 +814,37 @@ int nfsp_group_td_tables(nfsp_group* g, int64_t* dev_out /*[R][ndec][3][3][3]*/,
 int nfsp_head_tables(nfsp_ctx* ctx, int game, const float* const* dev_w, const int* act, int n,
                      float* dev_out /*[n][ndec][3][3]*/);
 
+/* ---- tables that act (csrc/act_table.hip; csrc/rollout.hip k_rollout_t, k_rollout_gt) ----
+ * Any of an engine's four (agent, role) slots can be acted by a table over nfsp_tree_export's
+ * rows instead of its net: where Agent.play calls avg_strategy_model.predict (role 0) or
+ * best_response_model.predict (role 1) for seat `agent` (agent/agent.py:124-151), the rollout
+ * looks the seat's observation up (the memory tables' lookup, nfsp_memtab_lookup) and takes the
+ * row's three f32 values, bit for bit, as the vector the net would have output.  Nothing else of
+ * Agent.play changes: the epsilon draw and its counter, the epsilon-random vector,
+ * NFSP_EXT_SAMPLE_AR's sampling from the vector, the env's raise-to-call remap, the all-zero rule
+ * (a fold that leaves no RL record), the SL record (the vector raw, or one-hot under
+ * NFSP_EXT_SL_ONEHOT) and the action counters.  A row is an action vector, not necessarily a
+ * distribution.  Slots mix freely; an engine with no table launches the kernels it always did.
+ * Every decision of a hand is a row of the tree, so a lookup cannot miss; if one does, the vector
+ * is all-zero and the slot's miss counter counts it.
+ * Deviation (declared, beside the policy lag): a table is not snapshotted.  With cfg.slice_lag 2,
+ * and under nfsp_rollout_with, the table installed at the step boundary acts in every slice of
+ * the step, whatever weights or snapshot the rollout is given.
+ * The engine copies the table (the caller may free its own) and reads only the rows where seat
+ * `agent` acts; those are copied to the host once and must be finite (NFSP_EINVAL names the row).
+ * Setting requires what nfsp_engine_state_digest requires (a step boundary), else NFSP_EINVAL.
+ * A group replica's handle is refused by the engine's set call: use the group call, which rewrites
+ * the replicas' rollout table.  Tables are session settings, like timing and the loss log: they
+ * are in neither the state blob (format version 1 still) nor the digest, and nfsp_engine_load_state
+ * leaves them alone.  The agent's BR chain trains on M_RL as before.
+ * role: 0 = AR (avg_strategy_model), 1 = BR (best_response_model), as nfsp_engine_weights' net. */
+int nfsp_engine_set_act_table(nfsp_engine* e, int agent, int role,
+                              const float* dev_rows /* [ndec][3][3] f32, or NULL: the net acts again */);
+/* dev_rows: the engine's copy, NULL if none; misses: lookups of the slot that found no
+ * information set since its table was installed (synchronises).  Either may be NULL. */
+int nfsp_engine_get_act_table(nfsp_engine* e, int agent, int role, const float** dev_rows, int64_t* misses);
+int nfsp_group_set_act_table(nfsp_group* g, int replica, int agent, int role, const float* dev_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ namespace nfsp {
 namespace eng {
 
 constexpr int MAXREC = 6;          // records of one kind per lane per hand (<= 6 decisions)
+constexpr int ACT_MAX_ROWS = 65;   // decision rows of one seat a table that acts may have (Leduc: 65)
 // A net in LDS for fwd_lds (one observation per lane): W1 rows padded to W1S = 66 floats,
 // so the per-lane row gathers read 2 hidden units at a time (ds_read_b64, 8-byte aligned)
 // and rows i, i' of two lanes hit the bank pairs 2i + j, 2i' + j (mod 64): distinct for
@@ -306,6 +307,11 @@ struct nfsp_engine {
   std::vector<hipEvent_t> pool;
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> marks;
   uint64_t* digest_buf = nullptr;    // k_state_digest's per-workgroup partials (state.hip), on first use
+  // tables that act (nfsp_engine_set_act_table; act_table.hip), slot = agent * 2 + role: a session
+  // setting like timing, in neither the state blob nor the digest
+  float* act_tab[4] = {};            // the installed [ndec][3][3] table (the slot's act_buf), null: the net acts
+  float* act_buf[4] = {};            // the slot's device buffer, on first install
+  unsigned long long* act_miss = nullptr;   // [4] lookups that found no information set, on device
 };
 
 namespace nfsp {
@@ -325,7 +331,10 @@ int rollout_launch_with(nfsp_engine* e, const float* w, const double eps[2]);
 int step_pipelined(nfsp_engine* e);
 // engine groups: the replicas' rollout arguments as a device table (static), and every
 // replica's rollout through it in one launch per kernel
+// (*d_tab null: allocated; else rewritten in place -- nfsp_group_set_act_table, at rest)
 int group_rollout_table(nfsp_engine* const* eng, int R, void** d_tab);
+// nfsp_engine_set_act_table's work on an engine at rest (act_table.hip): a group replica's too
+int act_table_install(nfsp_engine* e, int agent, int role, const float* dev_rows, const char* what);
 // par: the snapshot parity the slice acts with (slice_lag 2), -1: the replicas' own nets
 int group_rollout_launch(nfsp_engine* const* eng, int R, const void* d_tab, int par);
 // slice_lag 2: every replica's nets and epsilon -> snapshot par (-1: both parities)

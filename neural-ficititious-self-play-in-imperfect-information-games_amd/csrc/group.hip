@@ -268,6 +268,17 @@ extern "C" int nfsp_group_engine(nfsp_group* g, int r, nfsp_engine** out) {
   return NFSP_OK;
 }
 
+// A replica's slot acted by a table (act_table.hip), at a step boundary of the group; the
+// replicas' rollout table is rewritten, the table pointers ride in the replica's row
+extern "C" int nfsp_group_set_act_table(nfsp_group* g, int replica, int agent, int role, const float* dev_rows) {
+  NFSP_REQUIRE(g, "null argument");
+  NFSP_REQUIRE(replica >= 0 && replica < g->R, "nfsp_group_set_act_table: bad replica");
+  int rc = group_rest(g, "nfsp_group_set_act_table");
+  if (rc != NFSP_OK) return rc;
+  if ((rc = act_table_install(g->eng[replica], agent, role, dev_rows, "nfsp_group_set_act_table")) != NFSP_OK) return rc;
+  return group_rollout_table(g->eng.data(), g->R, &g->d_roll);
+}
+
 // the group's exchange (k_group_xchg) on stream `s`
 static int group_xchg_launch(nfsp_group* g, hipStream_t s) {
   const unsigned nets = g->xchg_nets ? g->xchg_nets : NFSP_XCHG_AR;

@@ -31,15 +31,12 @@
 
 #include "exploit_tree.h"
 #include "mem_view.h"
+#include "memtab_lookup.h"
 
 using namespace nfsp::eng;
 
 namespace {
 
-constexpr int MT_H = 1024;              // hash slots per seat (Leduc: 195 keys)
-constexpr int MT_HSHIFT = 22;           // 32 - log2(MT_H)
-constexpr uint32_t MT_EMPTY = 0xFFFFFFFFu;   // no observation has bits 30, 31
-constexpr int MT_MAX_ROWS = 128;        // decision rows of one seat (Leduc: 65)
 constexpr int MT_MAX_SEG = 8;
 constexpr int MT_WG = 1024;             // 16 waves
 constexpr int MT_U = 4;                 // records per lane in flight
@@ -50,9 +47,6 @@ constexpr int MT_LDS_MAX = 64 * 1024;
 constexpr int64_t MT_SAT = 4294967295ll;   // 2^32 - 1
 
 static_assert(sizeof(SlRec) == 16 && sizeof(RlRec) == 32, "record layout");
-static_assert(1 << (32 - MT_HSHIFT) == MT_H, "hash width");
-
-__host__ __device__ inline uint32_t mt_hash(uint32_t x) { return (x * 0x9E3779B1u) >> MT_HSHIFT; }
 
 // fix(x) = rint(x * 2^24), ties to even; |x| >= 256 or not finite saturates (NaN: 0) and counts
 __host__ __device__ inline int64_t mt_fix(float x, int& clamped) {
@@ -64,16 +58,12 @@ __host__ __device__ inline int64_t mt_fix(float x, int& clamped) {
 }
 
 // ---------------------------------------------------------------------------
-// host: the lookup of a game
+// host: the lookup of a game (memtab_lookup.h)
 // ---------------------------------------------------------------------------
-struct MtHost {
-  int ndec = 0;
-  int nrows[2] = {0, 0};
-  int32_t rows[2][MT_MAX_ROWS];          // the seat's compact row -> decision row
-  uint32_t keys[2][MT_H];
-  uint16_t vals[2][MT_H];                // sid = 3 x compact row + rank
-};
+}  // namespace
 
+namespace nfsp {
+namespace eng {
 int mt_host(int game, const MtHost** out) {
   static std::mutex mu;
   static std::map<int, MtHost> cache;
@@ -112,18 +102,10 @@ int mt_host(int game, const MtHost** out) {
   *out = &it->second;
   return NFSP_OK;
 }
+}  // namespace eng
+}  // namespace nfsp
 
-// sid of (seat, obs), -1: none.  The table is at most a third full, so a probe ends.
-__host__ __device__ inline int mt_find(const uint32_t* keys, const uint16_t* vals, uint32_t x) {
-  uint32_t h = mt_hash(x);
-  for (int n = 0; n < MT_H; ++n) {
-    const uint32_t k = keys[h];
-    if (k == x) return vals[h];
-    if (k == MT_EMPTY) return -1;
-    h = (h + 1) & (MT_H - 1);
-  }
-  return -1;
-}
+namespace {
 
 // ---------------------------------------------------------------------------
 // device
@@ -309,11 +291,6 @@ __global__ void __launch_bounds__(MT_WG) k_memtab_sum(MtArgs A, int kind) {
 // ---------------------------------------------------------------------------
 // host: per-device tables and workspace, the launch
 // ---------------------------------------------------------------------------
-struct MtDev {
-  uint32_t* keys = nullptr;
-  uint16_t* vals = nullptr;
-  int32_t* rows = nullptr;
-};
 struct MtWork {
   char* buf = nullptr;
   size_t cap = 0;
@@ -339,6 +316,23 @@ int mt_device(int dev, int game, const MtHost& M, MtDev* out) {
   *out = it->second;
   return NFSP_OK;
 }
+
+}  // namespace
+
+namespace nfsp {
+namespace eng {
+int mt_lookup(int game, const MtHost** host, MtDev* dev) {
+  int rc = mt_host(game, host);
+  if (rc != NFSP_OK) return rc;
+  int d = 0;
+  NFSP_HIP(hipGetDevice(&d));
+  std::lock_guard<std::mutex> lk(g_mu);
+  return mt_device(d, game, **host, dev);
+}
+}  // namespace eng
+}  // namespace nfsp
+
+namespace {
 
 // The tables of `tabs` (their `out` set) on `st`; info[t] filled; synchronises st.
 int mt_run(hipStream_t st, int game, int kind, std::vector<MtTab>& tabs, nfsp_memtab_info* info) {

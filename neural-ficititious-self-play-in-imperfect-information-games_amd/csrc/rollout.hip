@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "memtab_lookup.h"
 
 using nfsp::Hand;
 using nfsp::u32x4;
@@ -51,6 +52,18 @@ struct RolloutArgs {
   Staging S;
 };
 
+// Tables that act (nfsp_engine_set_act_table): slot = seat * 2 + role (0 = AR, 1 = BR).  A slot
+// with rows set acts with that [ndec][3][3] table through memtab_lookup.h's lookup instead of
+// its net; the TAB variant of the rollout alone reads this.
+struct ActTabs {
+  const float* rows[4];     // the engine's copy per slot, null: the net acts
+  const uint32_t* keys;     // [2][MT_H]  the game's lookup on this device
+  const uint16_t* vals;     // [2][MT_H]
+  const int32_t* rowmap;    // [2][MT_MAX_ROWS] the seat's compact row -> decision row
+  unsigned long long* miss; // [4] lookups that found no information set
+  int32_t nrows[2];
+};
+
 // One replica's rollout / commit arguments in an engine group's device table.
 struct GroupRollout {
   RolloutArgs A;
@@ -58,9 +71,22 @@ struct GroupRollout {
   int nblk;
   float* snap;          // slice_lag 2: the replica's snapshots [2][2][3][NP] (else null)
   double* snap_eps;     //   and their epsilons [2][2], on device
+  ActTabs T;            // the replica's tables that act (k_rollout_gt)
 };
 
-__device__ __forceinline__ void rollout_body(const RolloutArgs& A, int bx) {
+// The TAB variant's LDS beside the four nets: both seats' keys (4 KB each) and values (2 KB each),
+// the seat's rows of each slot's table (ACT_MAX_ROWS x 9 f32) and the slots' miss counters:
+// 21,664 B on top of the 37.9 KB.  Reached from the TAB variant only, so k_rollout and
+// k_rollout_g hold none of it.
+constexpr int ACT_SLOT_F32 = ACT_MAX_ROWS * 9;
+constexpr int ACT_LDS_WORDS = 2 * MT_H + MT_H + 4 * ACT_SLOT_F32 + 4;
+__device__ __forceinline__ uint32_t* act_lds() {
+  __shared__ __attribute__((aligned(16))) uint32_t s_tab[ACT_LDS_WORDS];
+  return s_tab;
+}
+
+template <bool TAB>
+__device__ __forceinline__ void rollout_body(const RolloutArgs& A, const ActTabs* T, int bx) {
   __shared__ __attribute__((aligned(16))) float sw[4 * NET_LDS];
   __shared__ unsigned s_act[2][3];
   __shared__ int s_rew[2];
@@ -74,6 +100,37 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& A, int bx) {
   for (int e = tid; e < 4 * nn::H; e += blockDim.x) sw[(e / nn::H) * NET_LDS + ZROW + e % nn::H] = 0.f;
   if (tid < 6) s_act[tid / 3][tid % 3] = 0;
   if (tid < 2) s_rew[tid] = 0;
+  // TAB: the lookup of both seats and the installed slots' rows (the seat's, compact)
+  const uint32_t* tkeys = nullptr;
+  const uint16_t* tvals = nullptr;
+  const float* trows = nullptr;
+  unsigned* tmiss = nullptr;
+  unsigned thas = 0;                       // bit slot: the slot acts with a table
+  if constexpr (TAB) {
+    uint32_t* const lds = act_lds();
+    uint16_t* const lv = reinterpret_cast<uint16_t*>(lds + 2 * MT_H);
+    float* const lr = reinterpret_cast<float*>(lds + 3 * MT_H);
+    unsigned* const lm = lds + 3 * MT_H + 4 * ACT_SLOT_F32;
+    // a group replica without a table (k_rollout_gt) has no lookup either: nothing of T is read
+    if (T->rows[0] || T->rows[1] || T->rows[2] || T->rows[3])
+      for (int e = tid; e < 2 * MT_H; e += blockDim.x) {
+        lds[e] = T->keys[e];
+        lv[e] = T->vals[e];
+      }
+#pragma unroll
+    for (int slot = 0; slot < 4; ++slot) {
+      const float* src = T->rows[slot];
+      if (!src) continue;                  // uniform over the workgroup
+      thas |= 1u << slot;
+      const int seat = slot >> 1;
+      int nr = T->nrows[seat];
+      nr = nr < ACT_MAX_ROWS ? nr : ACT_MAX_ROWS;
+      for (int e = tid; e < nr * 9; e += blockDim.x)
+        lr[slot * ACT_SLOT_F32 + e] = src[(size_t)T->rowmap[seat * MT_MAX_ROWS + e / 9] * 9 + e % 9];
+    }
+    if (tid < 4) lm[tid] = 0;
+    tkeys = lds; tvals = lv; trows = lr; tmiss = lm;
+  }
   __syncthreads();
 
   const int L = bx * blockDim.x + tid;     // staging index (lane within the slice)
@@ -162,9 +219,27 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& A, int bx) {
           dec++;
           fwd = (double)nfsp::u01(ub.x) > (p ? eps1 : eps0);
         }
-        if (fwd) {
+        bool net = fwd;
+        if constexpr (TAB) {
+          // the net replaced by a lookup: the slot's row at (p, x), bit for bit.  Every decision
+          // of a hand is a row of the tree; an observation that is none acts with y = 0 (the
+          // all-zero rule: a fold) and is counted
+          const int slot = p * 2 + (br ? 1 : 0);
+          if (fwd && ((thas >> slot) & 1u)) {
+            net = false;
+            const int sid = mt_find(tkeys + p * MT_H, tvals + p * MT_H, x);
+            if (sid >= 0 && sid < ACT_SLOT_F32 / 3) {
+              const float* row = trows + slot * ACT_SLOT_F32 + sid * 3;
+              y[0] = row[0]; y[1] = row[1]; y[2] = row[2];
+            } else {
+              y[0] = y[1] = y[2] = 0.f;
+              atomicAdd(&tmiss[slot], 1u);
+            }
+          }
+        }
+        if (net) {
           fwd_lds(sw + (p * 2 + (br ? 1 : 0)) * NET_LDS, x, br ? br_act(A.quirks) : NFSP_ACT_SOFTMAX, y);
-        } else {                   // np.random.rand(1, 1, 3)
+        } else if (!fwd) {                   // np.random.rand(1, 1, 3)
           y[0] = nfsp::u01(ub.y); y[1] = nfsp::u01(ub.z); y[2] = nfsp::u01(ub.w);
         }
         if (!br && (A.quirks & NFSP_EXT_SAMPLE_AR)) {   // sample the average policy (textbook NFSP)
@@ -217,15 +292,23 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& A, int bx) {
     atomicAdd(&A.st->actions[tid / 3][tid % 3], (unsigned long long)s_act[tid / 3][tid % 3]);
   if (tid < 2 && s_rew[tid]) atomicAdd((unsigned long long*)&A.st->reward_half[tid],
                                        (unsigned long long)(long long)s_rew[tid]);
+  if constexpr (TAB) {
+    if (tid < 4 && tmiss[tid]) atomicAdd(&T->miss[tid], (unsigned long long)tmiss[tid]);
+  }
 }
 
 // One engine's rollout runs 512-lane workgroups (8 waves): a 65,536-lane slice then takes
 // 128 CUs instead of all 256.  Each rollout workgroup holds 38 KB of LDS (the four nets), so a
 // CU running one cannot take a chain workgroup (150 KB, chain3.h CHAIN_LDS); with every CU
 // holding one, a BR chain launched during the rollout waited for it to drain (~86 us, once
-// per slice on agent 0's BR stream: 1.3 ms per C3 step).
+// per slice on agent 0's BR stream: 1.3 ms per C3 step).  The table variant (k_rollout_t, launched
+// only while a slot of the engine has a table) holds 21.2 KB more, 59 KB: it cannot share a CU with
+// a chain workgroup either, so the same holds for it.
 constexpr int ROLLOUT_WG = 512;
-__global__ void __launch_bounds__(ROLLOUT_WG) k_rollout(RolloutArgs A) { rollout_body(A, blockIdx.x); }
+__global__ void __launch_bounds__(ROLLOUT_WG) k_rollout(RolloutArgs A) { rollout_body<false>(A, nullptr, blockIdx.x); }
+__global__ void __launch_bounds__(ROLLOUT_WG) k_rollout_t(RolloutArgs A, ActTabs T) {
+  rollout_body<true>(A, &T, blockIdx.x);
+}
 
 // engine groups: blockIdx.y = replica (the rollout index is the same for every replica)
 // par >= 0 (slice_lag 2): the replica acts with its snapshot `par` and that snapshot's epsilon
@@ -242,7 +325,26 @@ __global__ void __launch_bounds__(256) k_rollout_g(const GroupRollout* __restric
     A.eps_v[0] = T.snap_eps[2 * par + 0];
     A.eps_v[1] = T.snap_eps[2 * par + 1];
   }
-  rollout_body(A, blockIdx.x);
+  rollout_body<false>(A, nullptr, blockIdx.x);
+}
+
+// the same with the replicas' tables that act, launched while any replica has one; a replica
+// with none acts with its nets or its snapshot as in k_rollout_g.  A table is not snapshotted:
+// the one installed at the step boundary acts in every slice.
+__global__ void __launch_bounds__(256) k_rollout_gt(const GroupRollout* __restrict__ tab, uint32_t g_lo,
+                                                    uint32_t g_hi, uint32_t lane0, int par) {
+  const GroupRollout& T = tab[blockIdx.y];
+  RolloutArgs A = T.A;
+  A.g_lo = g_lo;
+  A.g_hi = g_hi;
+  A.lane0 = lane0;
+  if (par >= 0) {
+    A.w = T.snap + (size_t)par * 6 * nn::NP;
+    A.eps_by_value = 1;
+    A.eps_v[0] = T.snap_eps[2 * par + 0];
+    A.eps_v[1] = T.snap_eps[2 * par + 1];
+  }
+  rollout_body<true>(A, &T.T, blockIdx.x);
 }
 
 // slice_lag 2 in a group: replica blockIdx.y's nets and epsilon -> its snapshot `par` (-1: both
@@ -466,6 +568,28 @@ static RolloutArgs rollout_args(const nfsp_engine* e) {
   return A;
 }
 
+static bool act_any(const nfsp_engine* e) {
+  return e->act_tab[0] || e->act_tab[1] || e->act_tab[2] || e->act_tab[3];
+}
+
+// the engine's tables that act, with the game's lookup on this device (none set: all null)
+static int act_tabs(const nfsp_engine* e, ActTabs* T) {
+  *T = ActTabs{};
+  if (!act_any(e)) return NFSP_OK;
+  const MtHost* M = nullptr;
+  MtDev D;
+  const int rc = mt_lookup(e->ctx->game, &M, &D);
+  if (rc != NFSP_OK) return rc;
+  for (int k = 0; k < 4; ++k) T->rows[k] = e->act_tab[k];
+  T->keys = D.keys;
+  T->vals = D.vals;
+  T->rowmap = D.rows;
+  T->miss = e->act_miss;
+  T->nrows[0] = M->nrows[0];
+  T->nrows[1] = M->nrows[1];
+  return NFSP_OK;
+}
+
 int rollout_launch(nfsp_engine* e) { return rollout_launch_with(e, e->w, e->hs.epsilon); }
 
 int rollout_launch_with(nfsp_engine* e, const float* w, const double eps[2]) {
@@ -476,9 +600,13 @@ int rollout_launch_with(nfsp_engine* e, const float* w, const double eps[2]) {
   A.eps_by_value = 1;               // the schedule as the host computed it (= st->epsilon)
   A.eps_v[0] = eps[0];
   A.eps_v[1] = eps[1];
+  ActTabs T;
+  const int trc = act_tabs(e, &T);
+  if (trc != NFSP_OK) return trc;
   {
     KTimer kt(e, KT_ROLLOUT);
-    k_rollout<<<(e->N + ROLLOUT_WG - 1) / ROLLOUT_WG, ROLLOUT_WG, 0, s>>>(A);
+    if (act_any(e)) k_rollout_t<<<(e->N + ROLLOUT_WG - 1) / ROLLOUT_WG, ROLLOUT_WG, 0, s>>>(A, T);
+    else k_rollout<<<(e->N + ROLLOUT_WG - 1) / ROLLOUT_WG, ROLLOUT_WG, 0, s>>>(A);
   }
   NFSP_LAUNCHED("k_rollout");
   {
@@ -509,8 +637,10 @@ int group_rollout_table(nfsp_engine* const* eng, int R, void** d_tab) {
     h[r].nblk = eng[r]->nblk;
     h[r].snap = eng[r]->snap;
     h[r].snap_eps = eng[r]->snap_eps_dev;
+    const int rc = act_tabs(eng[r], &h[r].T);
+    if (rc != NFSP_OK) return rc;
   }
-  NFSP_HIP(hipMalloc(d_tab, sizeof(GroupRollout) * R));
+  if (!*d_tab) NFSP_HIP(hipMalloc(d_tab, sizeof(GroupRollout) * R));
   NFSP_HIP(hipMemcpy(*d_tab, h.data(), sizeof(GroupRollout) * R, hipMemcpyHostToDevice));
   return NFSP_OK;
 }
@@ -527,7 +657,10 @@ int group_rollout_launch(nfsp_engine* const* eng, int R, const void* d_tab, int 
   {
     KTimer kt(e0, KT_ROLLOUT);
     const RolloutArgs A0 = rollout_args(e0);   // slice and hand index, the same for every replica
-    k_rollout_g<<<dim3(e0->nblk, R), 256, 0, s>>>(tab, A0.g_lo, A0.g_hi, A0.lane0, par);
+    bool any = false;
+    for (int r = 0; r < R; ++r) any = any || act_any(eng[r]);
+    if (any) k_rollout_gt<<<dim3(e0->nblk, R), 256, 0, s>>>(tab, A0.g_lo, A0.g_hi, A0.lane0, par);
+    else k_rollout_g<<<dim3(e0->nblk, R), 256, 0, s>>>(tab, A0.g_lo, A0.g_hi, A0.lane0, par);
   }
   NFSP_LAUNCHED("k_rollout_g");
   {

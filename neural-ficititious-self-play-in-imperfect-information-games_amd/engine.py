@@ -275,6 +275,90 @@ class SelfPlayEngine:
         opp = _opponents(self.ctx, self, 0, eta, tree)
         return ev.best_response(self.ctx, opp[0], opp[1], values, tree)
 
+    # -- tables that act ---------------------------------------------------
+    def set_act_table(self, agent: int, role: int, rows):
+        """Slot (agent, role) -- role ``NET_AR`` or ``NET_BR`` -- acts with the table ``rows``
+        (float32 ``[ndec, 3, 3]`` over ``GameTree``'s rows, ``evaluation.act_rows`` of a policy
+        table; array or tensor) instead of its net, ``None``: the net acts again
+        (nfsp_engine_set_act_table; step boundaries only).  A row is the vector the net would have
+        output: everything downstream of the forward is unchanged.  The engine keeps a copy."""
+        if self._owner is not None:
+            raise native.NativeError("set_act_table: a replica of an EngineGroup (EngineGroup.set_act_table)")
+        t = _act_rows_dev(self, rows)
+        native.check(self.L.nfsp_engine_set_act_table(self.h, int(agent), int(role), native.ptr(t)),
+                     "nfsp_engine_set_act_table")
+
+    def act_table(self, agent: int, role: int):
+        """``(rows, misses)`` of slot (agent, role) (nfsp_engine_get_act_table): a float32 device
+        copy ``[ndec, 3, 3]`` of the installed table, ``None`` when the net acts, and the lookups
+        that found no information set since it was installed (0 with a complete table)."""
+        p, m = native.P(), native.I64()
+        native.check(self.L.nfsp_engine_get_act_table(self.h, int(agent), int(role), C.byref(p), C.byref(m)),
+                     "nfsp_engine_get_act_table")
+        if not p.value:
+            return None, m.value
+        from . import evaluation as ev
+        n = ev.GameTree(self.ctx.game).ndec * 9
+        return _wrap_device(p.value, n, torch.float32, self.dev, self).view(-1, 3, 3).clone(), m.value
+
+    def clear_act_tables(self):
+        """Every slot acts with its net again."""
+        for a in (0, 1):
+            for role in (NET_AR, NET_BR):
+                self._set_act_table(a, role, None)
+
+    def _set_act_table(self, agent, role, rows):
+        if self._owner is not None:
+            self._owner.set_act_table(self._owner.replicas.index(self), agent, role, rows)
+        else:
+            self.set_act_table(agent, role, rows)
+
+    def acting_policy(self, agent: int, role: int, ar_mode: int | None = None, tree=None) -> np.ndarray:
+        """What slot (agent, role) executes when it acts, a float64 table ``[ndec, 3, 3]``: its
+        installed table if it has one, else its net.  The AR role under ``ar_mode`` 0 is sampled
+        (``EXT_SAMPLE_AR``: action 0 with probability y0, 1 with y1, else 2, so a table's rows
+        are taken as they stand, clipped to [0, 1]), under 1 its argmax; the BR role is greedy.
+        ``ar_mode`` defaults to what the rollout does under ``cfg.quirks``."""
+        from . import evaluation as ev
+        tree = tree or ev.GameTree(self.ctx.game)
+        if ar_mode is None:
+            ar_mode = 0 if self.cfg.quirks & native.EXT_SAMPLE_AR else 1
+        rows, _ = self.act_table(agent, role)
+        if rows is None:
+            return ev.policy_table(self.ctx, self.policy(agent, role, ar_mode), tree).cpu().numpy()
+        y = rows.cpu().numpy().astype(np.float64)
+        if role == NET_AR and ar_mode == 0:
+            c0 = np.clip(y[..., 0], 0.0, 1.0)
+            c1 = np.clip(y[..., 0] + y[..., 1], c0, 1.0)
+            t = np.stack([c0, c1 - c0, 1.0 - c1], axis=-1)
+        else:
+            t = np.eye(3)[np.argmax(y, axis=-1)]            # the first maximum, as the env's argmax
+        return tree.remap(t)
+
+    def install_oracle_br(self, eta: float | None = None, ar_mode: int | None = None):
+        """Oracle-BR self-play (sampled FSP): both agents' BR role acts with the exact best
+        response (``evaluation.best_response``, one-hot rows) to the other seat's acting average
+        policy as it is now -- ``acting_policy`` of its AR role, ``ar_mode`` defaulting to the
+        executed one.  With ``eta`` the opponent is its per-hand mixture eta x BR + (1 - eta) x AR
+        (``evaluation.mix``), the BR part being its installed BR table if it has one, else its
+        greedy BR net.  Call it before every step to refresh; ``clear_act_tables`` undoes it.
+        The BR chains still train on M_RL.  Returns the installed joint table (float64, device)."""
+        from . import evaluation as ev
+        tree = ev.GameTree(self.ctx.game)
+        opp = []
+        for o in (0, 1):
+            ar = self.acting_policy(o, NET_AR, ar_mode, tree)
+            if eta is None:
+                opp.append(ev.Policy.table(ar))
+            else:
+                br = self.acting_policy(o, NET_BR, None, tree)
+                opp.append(ev.Policy.table(ev.mix(tree, [(eta, br), (1.0 - eta, ar)])))
+        beta = ev.best_response(self.ctx, opp[0], opp[1], False, tree)
+        rows = ev.act_rows(beta)
+        for a in (0, 1):
+            self._set_act_table(a, NET_BR, rows)
+        return beta
+
     # -- the memories as tables (DESIGN.md §9) ------------------------------------------
     def memory_table(self, kind: int):
         """``(evaluation.MemoryTable, [info of agent 0, of agent 1])`` of M_SL
@@ -542,6 +626,13 @@ class EngineGroup:
         res = evaluation.evaluate_batch(self.ctx, [(a, b) for a in p0 for b in p1])
         return np.array([r["value0"] for r in res]).reshape(self.R, self.R)
 
+    def set_act_table(self, replica: int, agent: int, role: int, rows):
+        """``SelfPlayEngine.set_act_table`` for replica ``replica`` (nfsp_group_set_act_table;
+        step boundaries of the group only).  The other replicas act as before."""
+        t = _act_rows_dev(self.replicas[replica], rows)
+        native.check(self.L.nfsp_group_set_act_table(self.h, int(replica), int(agent), int(role), native.ptr(t)),
+                     "nfsp_group_set_act_table")
+
     def memory_tables(self, kind: int) -> list:
         """Every replica's ``SelfPlayEngine.memory_table(kind)`` in one launch
         (nfsp_group_memory_tables): ``[(MemoryTable, [info 0, info 1])]`` by replica."""
@@ -659,11 +750,16 @@ def _opponents(ctx, e, ar_mode, eta, tree) -> list:
     from . import evaluation as ev
     opp = []
     for o in (0, 1):
+        # a slot that acts with a table (set_act_table) is scored as that table
+        tab = [e.act_table(o, role)[0] is not None for role in (NET_AR, NET_BR)]
         if eta is None:
-            opp.append(e.policy(o, NET_AR, ar_mode))
+            opp.append(ev.Policy.table(e.acting_policy(o, NET_AR, ar_mode, tree)) if tab[0]
+                       else e.policy(o, NET_AR, ar_mode))
         else:
-            ar = ev.policy_table(ctx, e.policy(o, NET_AR, ar_mode), tree).cpu().numpy()
-            br = ev.policy_table(ctx, e.policy(o, NET_BR), tree).cpu().numpy()
+            ar = (e.acting_policy(o, NET_AR, ar_mode, tree) if tab[0]
+                  else ev.policy_table(ctx, e.policy(o, NET_AR, ar_mode), tree).cpu().numpy())
+            br = (e.acting_policy(o, NET_BR, None, tree) if tab[1]
+                  else ev.policy_table(ctx, e.policy(o, NET_BR), tree).cpu().numpy())
             opp.append(ev.Policy.table(ev.mix(tree, [(eta, br), (1.0 - eta, ar)])))
     return opp
 
@@ -685,6 +781,20 @@ def _br_gaps(ctx, engines, ar_mode, eta) -> list:
         out.append([{"br_exact": r0["br0"], "br_learned": r0["value0"], "gap": r0["br0"] - r0["value0"]},
                     {"br_exact": r1["br1"], "br_learned": -r1["value0"], "gap": r1["br1"] + r1["value0"]}])
     return out
+
+
+def _act_rows_dev(e, rows):
+    """``rows`` of a set_act_table call as a float32 device tensor of the game's size, or None."""
+    if rows is None:
+        return None
+    from . import evaluation as ev
+    t = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(rows))
+    if t.dtype != torch.float32:
+        raise TypeError("set_act_table: float32 rows (evaluation.act_rows converts a policy table)")
+    ndec = ev.GameTree(e.ctx.game).ndec
+    if t.numel() != ndec * 9:
+        raise ValueError(f"set_act_table: expected [{ndec}, 3, 3] rows, got {tuple(t.shape)}")
+    return t.to(e.dev).contiguous()
 
 
 def _wrap_device(addr, numel, dtype, device, owner=None) -> torch.Tensor:

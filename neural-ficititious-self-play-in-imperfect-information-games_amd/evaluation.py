@@ -417,6 +417,22 @@ def head_tables(ctx, nets, acts, tree: GameTree | None = None):
     return out
 
 
+def act_rows(table):
+    """A policy table (float64 ``[ndec, 3, 3]``: array or tensor, as ``policy_table``,
+    ``best_response``, ``mix`` and the solvers' averages give them) as the float32 rows a slot of
+    an engine acts with (``SelfPlayEngine.set_act_table``): one rounding per value, so exact for
+    one-hot rows.  A tensor stays on its device.  Values that are not finite, or not after the
+    rounding, are refused: a table acts as it stands, nothing downstream would catch them."""
+    import torch
+    t = table if isinstance(table, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(table))
+    if t.numel() % 9:
+        raise ValueError(f"a table has 9 values per row, got {t.numel()} values")
+    t = t.to(torch.float32).reshape(-1, 3, 3).contiguous()
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError("act_rows: the table has values that are not finite (as float32)")
+    return t
+
+
 def _rms(err, weight):
     den = float(weight.sum())
     return float(np.sqrt((weight * err**2).sum() / den)) if den > 0 else float("nan")

@@ -223,6 +223,10 @@ SIGNATURES = {
     "nfsp_engine_td_table": (I32, [P, P, C.POINTER(MemtabInfo)]),
     "nfsp_group_td_tables": (I32, [P, P, C.POINTER(MemtabInfo)]),
     "nfsp_head_tables": (I32, [P, I32, PP, C.POINTER(I32), I32, P]),
+    # tables that act: a slot's net (agent/agent.py:124-151's predict calls) replaced by a lookup
+    "nfsp_engine_set_act_table": (I32, [P, I32, I32, P]),
+    "nfsp_engine_get_act_table": (I32, [P, I32, I32, PP, C.POINTER(I64)]),
+    "nfsp_group_set_act_table": (I32, [P, I32, I32, I32, P]),
 }
 # int (*nfsp_exchange_fn)(void* user, float* dev_sum, int64_t n)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, P, P, I64)
