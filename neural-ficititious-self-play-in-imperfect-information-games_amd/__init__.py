@@ -13,7 +13,7 @@ def __getattr__(name):
     # heavy submodules (torch) load lazily so `native` can be probed without a GPU stack
     import importlib
     if name in ("leduc", "agent", "buffers", "selfplay", "engine", "observability", "pyrandom", "shards",
-                "reference_main", "checkpoint", "sweep", "evaluation"):
+                "reference_main", "checkpoint", "sweep", "evaluation", "diagnostics"):
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)
 

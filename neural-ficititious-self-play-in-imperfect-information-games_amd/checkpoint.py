@@ -17,7 +17,6 @@ import numpy as np
 
 from . import native
 
-NP = 30 * 64 + 64 + 64 * 3 + 3
 MAGIC = b"NFSPSTAT"
 VERSION = 1
 KIND_ENGINE, KIND_GROUP = 1, 2
@@ -128,7 +127,7 @@ def parse(data) -> dict:
         g = raw[:GROUP_DTYPE.itemsize].view(GROUP_DTYPE)[0]
         out["group"] = {"R": int(g["R"]), "flags": int(g["flags"]), "calls": int(g["calls"]),
                         "w0_valid": int(g["w0_valid"]),
-                        "w0": raw[GROUP_DTYPE.itemsize:].view("<f4").reshape(3, 2, NP)}
+                        "w0": raw[GROUP_DTYPE.itemsize:].view("<f4").reshape(3, 2, native.NP)}
         k = 1
     for r in range(int(hd["replicas"])):
         host = body(k, HOST_DTYPE)[0]
@@ -140,7 +139,7 @@ def parse(data) -> dict:
                "game": int(host["game"]), "g": int(host["g"]), "learn_tag": int(host["learn_tag"]),
                "iteration": host["iteration"].tolist(), "target_count": host["target_count"].tolist(),
                "target_syncs": host["target_syncs"].tolist(), "epsilon": host["epsilon"].tolist(),
-               "st": st, "nets": body(k + 2, "<f4").reshape(2, 3, NP),
+               "st": st, "nets": body(k + 2, "<f4").reshape(2, 3, native.NP),
                "rl": [rl[:n0], rl[n0:]], "sl": [sl[:c0], sl[c0:]]}
         out["engines"].append(eng)
         k += 5

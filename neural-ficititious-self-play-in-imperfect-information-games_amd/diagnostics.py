@@ -1,0 +1,132 @@
+"""Diagnostics of an engine: everything that needs both an engine and the exact evaluator.
+
+Functions over anything with a ``SelfPlayEngine``'s ``ctx``, ``cfg``, ``policy``, ``act_table`` and
+``_wptr`` (a replica of an ``EngineGroup`` is one); the engine's methods of the same names carry the
+documentation and delegate here.  ``opponents`` is the one statement of what seat o plays.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import evaluation as ev
+from . import native
+from .native import NET_AR, NET_BR
+
+
+def _ar_mode(e, ar_mode):
+    """``ar_mode``, None being what the rollout executes under ``cfg.quirks``."""
+    return ar_mode if ar_mode is not None else 0 if e.cfg.quirks & native.EXT_SAMPLE_AR else 1
+
+
+def acting_policy(e, agent: int, role: int, ar_mode: int | None = None, tree=None) -> np.ndarray:
+    """``SelfPlayEngine.acting_policy``: slot (agent, role)'s installed table as executed, else its net's."""
+    tree = tree or ev.GameTree.of(e.ctx.game)
+    ar_mode = _ar_mode(e, ar_mode)
+    rows, _ = e.act_table(agent, role)
+    if rows is None:
+        return ev.policy_table(e.ctx, e.policy(agent, role, ar_mode), tree).cpu().numpy()
+    y = rows.cpu().numpy().astype(np.float64)
+    if role == NET_AR and ar_mode == 0:
+        c0 = np.clip(y[..., 0], 0.0, 1.0)
+        c1 = np.clip(y[..., 0] + y[..., 1], c0, 1.0)
+        t = np.stack([c0, c1 - c0, 1.0 - c1], axis=-1)
+    else:
+        t = np.eye(3)[np.argmax(y, axis=-1)]            # the first maximum, as the env's argmax
+    return tree.remap(t)
+
+
+def opponents(e, ar_mode, eta, tree=None, tables: bool = False) -> list:
+    """[the policy agent 1 - o faces at seat o, o = 0, 1]: engine e's AR part there,
+    ``acting_policy(e, o, NET_AR, ar_mode)``, or with ``eta`` the per-hand mixture eta x BR part
+    (``acting_policy(e, o, NET_BR)``) + (1 - eta) x AR part it plays in self-play.  An AR slot
+    whose net acts is passed as the net itself (no launch) unless ``tables``."""
+    tree = tree or ev.GameTree.of(e.ctx.game)
+    opp = []
+    for o in (0, 1):
+        if eta is not None:
+            br, ar = acting_policy(e, o, NET_BR, None, tree), acting_policy(e, o, NET_AR, ar_mode, tree)
+            opp.append(ev.Policy.table(ev.mix(tree, [(eta, br), (1.0 - eta, ar)])))
+        elif tables or e.act_table(o, NET_AR)[0] is not None:
+            opp.append(ev.Policy.table(acting_policy(e, o, NET_AR, ar_mode, tree)))
+        else:
+            opp.append(e.policy(o, NET_AR, _ar_mode(e, ar_mode)))
+    return opp
+
+
+def br_gaps(ctx, engines, ar_mode, eta) -> list:
+    """``br_gap`` of each engine: per agent {br_exact, br_learned, gap}; one nfsp_evaluate_batch."""
+    pairs = []
+    for e in engines:
+        opp = opponents(e, ar_mode, eta)
+        pairs += [(e.policy(0, NET_BR), opp[1]), (opp[0], e.policy(1, NET_BR))]
+    res = ev.evaluate_batch(ctx, pairs)
+    out = []
+    for k in range(len(engines)):
+        r0, r1 = res[2 * k], res[2 * k + 1]
+        out.append([{"br_exact": r0["br0"], "br_learned": r0["value0"], "gap": r0["br0"] - r0["value0"]},
+                    {"br_exact": r1["br1"], "br_learned": -r1["value0"], "gap": r1["br1"] + r1["value0"]}])
+    return out
+
+
+def best_response_table(e, eta=None, values: bool = False):
+    """``SelfPlayEngine.best_response_table``: the exact best responses to ``opponents`` at AR mode 0."""
+    opp = opponents(e, 0, eta)
+    return ev.best_response(e.ctx, opp[0], opp[1], values)
+
+
+def oracle_br(e, eta=None, ar_mode=None):
+    """The table ``SelfPlayEngine.install_oracle_br`` installs: the exact best responses to what
+    the seats execute, ``ar_mode`` None being the rollout's under ``cfg.quirks``."""
+    opp = opponents(e, ar_mode, eta, tables=True)
+    return ev.best_response(e.ctx, opp[0], opp[1])
+
+
+def q_reports(ctx, engines, td_tables, infos, eta=None, tree=None) -> list:
+    """``SelfPlayEngine.q_report`` of every engine from its TD table: one ``head_tables`` launch for
+    all of their BR nets (per 64), one ``best_response`` per engine."""
+    tree = tree or ev.GameTree.of(ctx.game)
+    lin = [bool(e.cfg.quirks & native.EXT_LINEAR_Q) for e in engines]
+    head = ev.head_tables(ctx, [e._wptr(a, NET_BR) for e in engines for a in (0, 1)],
+                          [native.ACT_LINEAR if l else native.ACT_RELU for l in lin for _ in (0, 1)], tree).cpu().numpy()
+    out = []
+    for k, e in enumerate(engines):
+        beta, q, reach = (t.cpu().numpy() for t in best_response_table(e, eta, True))
+        out.append([ev.q_report_from(tree, a, beta, q, reach, head[2 * k + a], td_tables[k], lin[k],
+                                     float(e.cfg.gamma), infos[k][a]) for a in (0, 1)])
+    return out
+
+
+def memory_reports(ctx, engines, sl_tables, rl_tables, infos, tree=None) -> list:
+    """``SelfPlayEngine.memory_report`` of every engine from its tables: the AR pair and the two
+    M_SL tables of all of them scored in one ``evaluate_batch`` call.  The nets are scored, also
+    where a table acts for one."""
+    tree = tree or ev.GameTree.of(ctx.game)
+    tabs = [(sl.policy("argmax"), sl.policy("mass")) for sl in sl_tables]
+    pairs = []
+    for e, (am, ms) in zip(engines, tabs):
+        pa, pm = ev.Policy.table(am), ev.Policy.table(ms)
+        pairs += [(e.policy(0, NET_AR), e.policy(1, NET_AR)), (pa, pa), (pm, pm)]
+    res = ev.evaluate_batch(ctx, pairs)
+    legal = np.ones((tree.ndec, 3, 3), bool)
+    legal[~tree.legal, :, 2] = False
+    out = []
+    for k, e in enumerate(engines):
+        sl, rl = sl_tables[k], rl_tables[k]
+        ar, am, ms = (res[3 * k + j]["exploitability"] for j in range(3))
+        mass = tree.remap(tabs[k][1])
+        num = den = 0.0
+        for seat in (0, 1):
+            net = ev.policy_table(ctx, e.policy(seat, NET_AR), tree).cpu().numpy()
+            rows = tree.seat == seat
+            w = sl.n[rows].astype(np.float64)
+            num += float((w * np.abs(net[rows] - mass[rows]).sum(axis=2)).sum())
+            den += float(w.sum())
+        out.append({
+            "exploitability_ar": ar, "exploitability_sl_argmax": am, "exploitability_sl_mass": ms,
+            # what the net adds to the strategy it is a fit of (> 0: the net is more exploitable)
+            "fit_gap_argmax": ar - am, "fit_gap_mass": ar - ms,
+            "sl_empty_sets": int((sl.n == 0).sum()),
+            "rl_empty_actions": int(((rl.counts == 0) & legal).sum()),
+            "ar_mass_l1": num / den if den > 0 else float("nan"),
+            "sl_info": infos[k][0], "rl_info": infos[k][1]})
+    return out

@@ -19,10 +19,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import checkpoint, native
-
-NP = 30 * 64 + 64 + 64 * 3 + 3
-NET_AR, NET_BR, NET_TARGET = 0, 1, 2
+from . import checkpoint, diagnostics, evaluation, native
+from .evaluation import exploitability, exploitability_batch  # noqa: F401  (engine.exploitability is public API)
+from .native import NET_AR, NET_BR, NET_TARGET, NP
 
 PRESETS = {
     "reference": dict(n_lanes=1, rl_capacity=40_000, sl_capacity=40_000),
@@ -50,7 +49,26 @@ def make_cfg(L, **cfg) -> native.EngineCfg:
     return c
 
 
-class SelfPlayEngine:
+def _timings(obj, fn) -> dict:
+    ms = (native.F64 * len(obj.KERNELS))()
+    n = (native.I64 * len(obj.KERNELS))()
+    native.check(getattr(obj.L, fn)(obj.h, ms, n), "get_timings")
+    return {k: (ms[i], n[i]) for i, k in enumerate(obj.KERNELS)}
+
+
+def _count_tables(obj, dev, fn, R, kind, *head) -> list:
+    """``[(evaluation.MemoryTable of ``kind``, [info of agent 0, of agent 1])]`` of R engines: one
+    launch of ``fn`` (nfsp_{engine,group}_{memory,td}_table[s]), ``head`` its arguments before the output."""
+    tree = evaluation.GameTree.of(obj.ctx.game)
+    out = torch.empty((R, tree.ndec, 3, 3, 3), dtype=torch.int64, device=dev)
+    info = (native.MemtabInfo * (2 * R))()
+    native.check(getattr(obj.L, fn)(obj.h, *head, native.P(out.data_ptr()), info), fn)
+    raw = out.cpu().numpy()
+    return [(evaluation.MemoryTable(tree, kind, raw[r]), [info[2 * r].to_dict(), info[2 * r + 1].to_dict()])
+            for r in range(R)]
+
+
+class SelfPlayEngine(native.Handle):
     def __init__(self, ctx: native.Context | None = None, init_seed: int = 0, game: int = native.GAME_LEDUC,
                  _borrow=None, **cfg):
         self.ctx = ctx if ctx is not None else native.Context(1, game=game)
@@ -89,7 +107,7 @@ class SelfPlayEngine:
 
     def weights_tensor(self, agent, net) -> torch.Tensor:
         """A torch view (no copy) of the device weights of (agent, net)."""
-        return _wrap_device(self._wptr(agent, net), NP, torch.float32, self.dev, self)
+        return native.wrap_device(self._wptr(agent, net), NP, torch.float32, self.dev, self)
 
     def get_weights(self, agent, net) -> np.ndarray:
         return self.weights_tensor(agent, net).cpu().numpy().copy()
@@ -130,10 +148,7 @@ class SelfPlayEngine:
 
     def timings(self) -> dict:
         """{kernel: (total ms, launches)} since the last call (HIP events, ctx stream)."""
-        ms = (native.F64 * len(self.KERNELS))()
-        n = (native.I64 * len(self.KERNELS))()
-        native.check(self.L.nfsp_engine_get_timings(self.h, ms, n), "get_timings")
-        return {k: (ms[i], n[i]) for i, k in enumerate(self.KERNELS)}
+        return _timings(self, "nfsp_engine_get_timings")
 
     # -- inspection (tests) -------------------------------------------------------
     def memories(self, agent):
@@ -147,18 +162,18 @@ class SelfPlayEngine:
         d = self.dev
         out = dict(
             log_cap=n,
-            rl_s=_wrap_device(rl.s, n * 30, torch.float32, d, self).view(n, 30),
-            rl_a=_wrap_device(rl.a, n * 3, torch.float32, d, self).view(n, 3),
-            rl_r=_wrap_device(rl.r, n, torch.float32, d, self),
-            rl_s2=_wrap_device(rl.s2, n * 30, torch.float32, d, self).view(n, 30),
-            rl_t=_wrap_device(rl.t, n, torch.uint8, d, self),
-            sl_s=_wrap_device(sl.s, sl.cap * 30, torch.float32, d, self).view(sl.cap, 30),
-            sl_a=_wrap_device(sl.a, sl.cap * 3, torch.float32, d, self).view(sl.cap, 3),
+            rl_s=native.wrap_device(rl.s, n * 30, torch.float32, d, self).view(n, 30),
+            rl_a=native.wrap_device(rl.a, n * 3, torch.float32, d, self).view(n, 3),
+            rl_r=native.wrap_device(rl.r, n, torch.float32, d, self),
+            rl_s2=native.wrap_device(rl.s2, n * 30, torch.float32, d, self).view(n, 30),
+            rl_t=native.wrap_device(rl.t, n, torch.uint8, d, self),
+            sl_s=native.wrap_device(sl.s, sl.cap * 30, torch.float32, d, self).view(sl.cap, 30),
+            sl_a=native.wrap_device(sl.a, sl.cap * 3, torch.float32, d, self).view(sl.cap, 3),
         )
         pc = 4 * self.slice_lanes
-        out["pend_x"] = _wrap_device(px.value, pc, torch.int32, d, self)
-        out["pend_a"] = _wrap_device(pa.value, pc * 3, torch.float32, d, self).view(pc, 3)
-        out["pend_pos"] = _wrap_device(pp.value, pc, torch.int64, d, self)
+        out["pend_x"] = native.wrap_device(px.value, pc, torch.int32, d, self)
+        out["pend_a"] = native.wrap_device(pa.value, pc * 3, torch.float32, d, self).view(pc, 3)
+        out["pend_pos"] = native.wrap_device(pp.value, pc, torch.int64, d, self)
         return out
 
     def last_update(self, agent, role):
@@ -166,8 +181,8 @@ class SelfPlayEngine:
         native.check(self.L.nfsp_engine_last_update(self.h, agent, role, C.byref(rows),
                                                      C.byref(perms)), "last_update")
         B, E = self.cfg.batch, self.cfg.epochs
-        return (_wrap_device(rows.value, B, torch.int64, self.dev).cpu().numpy(),
-                _wrap_device(perms.value, E * B, torch.int32, self.dev).view(E, B).cpu().numpy())
+        return (native.wrap_device(rows.value, B, torch.int64, self.dev).cpu().numpy(),
+                native.wrap_device(perms.value, E * B, torch.int32, self.dev).view(E, B).cpu().numpy())
 
     @property
     def slice_lanes(self) -> int:
@@ -187,7 +202,7 @@ class SelfPlayEngine:
         p = native.P()
         native.check(self.L.nfsp_engine_lane_counts(self.h, C.byref(p)), "lane_counts")
         torch.cuda.synchronize(self.dev)
-        c = _wrap_device(p.value, self.slice_lanes, torch.int32, self.dev).cpu().numpy()
+        c = native.wrap_device(p.value, self.slice_lanes, torch.int32, self.dev).cpu().numpy()
         c = c.astype(np.int64) & 0xFFFF
         return np.stack([(c >> (4 * k)) & 15 for k in range(4)], axis=1)
 
@@ -199,7 +214,7 @@ class SelfPlayEngine:
         eps = (C.c_double * 2)()
         native.check(self.L.nfsp_engine_snapshot(self.h, int(parity), C.byref(p), eps), "snapshot")
         torch.cuda.synchronize(self.dev)
-        w = _wrap_device(p.value, 6 * NP, torch.float32, self.dev, self).cpu().numpy().copy()
+        w = native.wrap_device(p.value, 6 * NP, torch.float32, self.dev, self).cpu().numpy().copy()
         return w, (eps[0], eps[1])
 
     def set_exchange(self, every: int, scale: float, comm=None, fn=None):
@@ -247,7 +262,6 @@ class SelfPlayEngine:
     def policy(self, agent: int, net: int = NET_AR, mode: int = 0):
         """An ``evaluation.Policy`` reading this engine's weights in place: the AR net as its
         softmax / argmax, or the BR net played greedily (the head kind from ``cfg.quirks``)."""
-        from . import evaluation
         if net == NET_AR:
             return evaluation.Policy.ar(self._wptr(agent, NET_AR), mode, owner=self)
         return evaluation.Policy.br(self._wptr(agent, net), bool(self.cfg.quirks & native.EXT_LINEAR_Q), owner=self)
@@ -259,7 +273,7 @@ class SelfPlayEngine:
         against it; ``gap`` = their difference (>= 0).  With ``eta`` the opponent is the per-hand
         mixture eta x greedy BR + (1 - eta) x AR it plays in self-play (``evaluation.mix``):
         kuhn_diag's ``anticip``."""
-        return _br_gaps(self.ctx, [self], ar_mode, eta)[0]
+        return diagnostics.br_gaps(self.ctx, [self], ar_mode, eta)[0]
 
     def best_response_table(self, eta: float | None = None, values: bool = False):
         """The exact best responses behind ``br_gap``'s ``br_exact``, as a strategy
@@ -270,10 +284,7 @@ class SelfPlayEngine:
         (``evaluation.policy_table(ctx, engine.policy(i, NET_BR))``) to see where the learned
         best response deviates; with ``values`` returns ``(beta, q, reach)``, the exact action
         values there."""
-        from . import evaluation as ev
-        tree = ev.GameTree(self.ctx.game)
-        opp = _opponents(self.ctx, self, 0, eta, tree)
-        return ev.best_response(self.ctx, opp[0], opp[1], values, tree)
+        return diagnostics.best_response_table(self, eta, values)
 
     # -- tables that act (DESIGN.md §9) ---------------------------------------------------
     def set_act_table(self, agent: int, role: int, rows):
@@ -297,9 +308,8 @@ class SelfPlayEngine:
                      "nfsp_engine_get_act_table")
         if not p.value:
             return None, m.value
-        from . import evaluation as ev
-        n = ev.GameTree(self.ctx.game).ndec * 9
-        return _wrap_device(p.value, n, torch.float32, self.dev, self).view(-1, 3, 3).clone(), m.value
+        n = evaluation.GameTree.of(self.ctx.game).ndec * 9
+        return native.wrap_device(p.value, n, torch.float32, self.dev, self).view(-1, 3, 3).clone(), m.value
 
     def clear_act_tables(self):
         """Every slot acts with its net again."""
@@ -319,21 +329,7 @@ class SelfPlayEngine:
         (``EXT_SAMPLE_AR``: action 0 with probability y0, 1 with y1, else 2, so a table's rows
         are taken as they stand, clipped to [0, 1]), under 1 its argmax; the BR role is greedy.
         ``ar_mode`` defaults to what the rollout does under ``cfg.quirks``."""
-        from . import evaluation as ev
-        tree = tree or ev.GameTree(self.ctx.game)
-        if ar_mode is None:
-            ar_mode = 0 if self.cfg.quirks & native.EXT_SAMPLE_AR else 1
-        rows, _ = self.act_table(agent, role)
-        if rows is None:
-            return ev.policy_table(self.ctx, self.policy(agent, role, ar_mode), tree).cpu().numpy()
-        y = rows.cpu().numpy().astype(np.float64)
-        if role == NET_AR and ar_mode == 0:
-            c0 = np.clip(y[..., 0], 0.0, 1.0)
-            c1 = np.clip(y[..., 0] + y[..., 1], c0, 1.0)
-            t = np.stack([c0, c1 - c0, 1.0 - c1], axis=-1)
-        else:
-            t = np.eye(3)[np.argmax(y, axis=-1)]            # the first maximum, as the env's argmax
-        return tree.remap(t)
+        return diagnostics.acting_policy(self, agent, role, ar_mode, tree)
 
     def install_oracle_br(self, eta: float | None = None, ar_mode: int | None = None):
         """Oracle-BR self-play (sampled FSP): both agents' BR role acts with the exact best
@@ -343,18 +339,8 @@ class SelfPlayEngine:
         (``evaluation.mix``), the BR part being its installed BR table if it has one, else its
         greedy BR net.  Call it before every step to refresh; ``clear_act_tables`` undoes it.
         The BR chains still train on M_RL.  Returns the installed joint table (float64, device)."""
-        from . import evaluation as ev
-        tree = ev.GameTree(self.ctx.game)
-        opp = []
-        for o in (0, 1):
-            ar = self.acting_policy(o, NET_AR, ar_mode, tree)
-            if eta is None:
-                opp.append(ev.Policy.table(ar))
-            else:
-                br = self.acting_policy(o, NET_BR, None, tree)
-                opp.append(ev.Policy.table(ev.mix(tree, [(eta, br), (1.0 - eta, ar)])))
-        beta = ev.best_response(self.ctx, opp[0], opp[1], False, tree)
-        rows = ev.act_rows(beta)
+        beta = diagnostics.oracle_br(self, eta, ar_mode)
+        rows = evaluation.act_rows(beta)
         for a in (0, 1):
             self._set_act_table(a, NET_BR, rows)
         return beta
@@ -364,13 +350,7 @@ class SelfPlayEngine:
         """``(evaluation.MemoryTable, [info of agent 0, of agent 1])`` of M_SL
         (``native.MEM_SL``) or M_RL (``native.MEM_RL``), both agents in one launch on the packed
         records where they lie (nfsp_engine_memory_table; step boundaries only)."""
-        from . import evaluation as ev
-        tree = ev.GameTree(self.ctx.game)
-        out = torch.empty((tree.ndec, 3, 3, 3), dtype=torch.int64, device=self.dev)
-        info = (native.MemtabInfo * 2)()
-        native.check(self.L.nfsp_engine_memory_table(self.h, int(kind), native.P(out.data_ptr()), info),
-                     "nfsp_engine_memory_table")
-        return ev.MemoryTable(tree, kind, out), [info[0].to_dict(), info[1].to_dict()]
+        return _count_tables(self, self.dev, "nfsp_engine_memory_table", 1, kind, int(kind))[0]
 
     def memory_report(self) -> dict:
         """What the memories hold against what the nets make of them, all exact:
@@ -381,11 +361,9 @@ class SelfPlayEngine:
         ((information set, legal action) pairs without an M_RL record), ``ar_mass_l1`` (the mean
         L1 distance between the AR nets' executed policy and the "mass" table, weighted by the
         records per set) and both calls' infos per agent."""
-        from . import evaluation as ev
-        tree = ev.GameTree(self.ctx.game)
         sl, si = self.memory_table(native.MEM_SL)
         rl, ri = self.memory_table(native.MEM_RL)
-        return ev.memory_reports(self.ctx, [self], [sl], [rl], [(si, ri)], tree)[0]
+        return diagnostics.memory_reports(self.ctx, [self], [sl], [rl], [(si, ri)])[0]
 
     def td_table(self):
         """``(evaluation.MemoryTable of kind native.MEM_TD, [info of agent 0, of agent 1])``: the TD
@@ -393,12 +371,7 @@ class SelfPlayEngine:
         action) over the live M_RL records where they lie, each agent against its own target net
         with ``cfg.gamma`` and ``cfg.quirks`` (nfsp_engine_td_table; step boundaries only).  Under
         ``QUIRK_ALIAS_RL`` a record's key is its hand's LAST s."""
-        from . import evaluation as ev
-        tree = ev.GameTree(self.ctx.game)
-        out = torch.empty((tree.ndec, 3, 3, 3), dtype=torch.int64, device=self.dev)
-        info = (native.MemtabInfo * 2)()
-        native.check(self.L.nfsp_engine_td_table(self.h, native.P(out.data_ptr()), info), "nfsp_engine_td_table")
-        return ev.MemoryTable(tree, native.MEM_TD, out), [info[0].to_dict(), info[1].to_dict()]
+        return _count_tables(self, self.dev, "nfsp_engine_td_table", 1, native.MEM_TD)[0]
 
     def q_report(self, eta: float | None = None) -> list:
         """The BR half of ``memory_report``, per agent i (``evaluation.q_report_from`` has the keys):
@@ -409,9 +382,8 @@ class SelfPlayEngine:
         ``fit_rmse_td`` the net against its data.  Under ``QUIRK_ALIAS_RL`` a record's key is its
         hand's LAST s, and under ``QUIRK_ROW0_TARGET`` the net is fitted to one TD value per 128
         sampled rows: the report states what is stored and what the net holds."""
-        from . import evaluation as ev
         td, info = self.td_table()
-        return ev.q_reports(self.ctx, [self], [td], [info], eta)[0]
+        return diagnostics.q_reports(self.ctx, [self], [td], [info], eta)[0]
 
     # -- checkpoints (checkpoint.py, DESIGN.md §10) ----------------------------------
     def save(self, path):
@@ -456,19 +428,12 @@ class SelfPlayEngine:
             raise
         return eng
 
-    def close(self):
-        if getattr(self, "h", None) and getattr(self, "_owner", None) is None:
+    def _destroy(self):
+        if self._owner is None:                # a replica's handle is its group's
             self.L.nfsp_engine_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class EngineGroup:
+class EngineGroup(native.Handle):
     """R replicas of the engine stepped together (``nfsp_group_*``, include/nfsp.h): each an
     independent main.train over ``n_lanes`` lanes with its own memories and nets (seed + r,
     initial nets from ``init_seed + r`` -- replica r is bit-identical to
@@ -598,10 +563,7 @@ class EngineGroup:
         native.check(self.L.nfsp_group_set_timing(self.h, int(bool(on))), "set_timing")
 
     def timings(self) -> dict:
-        ms = (native.F64 * len(self.KERNELS))()
-        n = (native.I64 * len(self.KERNELS))()
-        native.check(self.L.nfsp_group_get_timings(self.h, ms, n), "get_timings")
-        return {k: (ms[i], n[i]) for i, k in enumerate(self.KERNELS)}
+        return _timings(self, "nfsp_group_get_timings")
 
     def exploitability(self, mode: int = 0, replica: int = 0) -> dict:
         return self.replicas[replica].exploitability(mode)
@@ -615,12 +577,11 @@ class EngineGroup:
 
     def br_gap_all(self, ar_mode: int = 0, eta: float | None = None) -> list:
         """``SelfPlayEngine.br_gap`` of every replica, in one batch call (two pairs per replica)."""
-        return _br_gaps(self.ctx, self.replicas, ar_mode, eta)
+        return diagnostics.br_gaps(self.ctx, self.replicas, ar_mode, eta)
 
     def crossplay(self, mode: int = 0) -> np.ndarray:
         """[R, R]: seat 0's value when replica i's AR net at seat 0 plays replica j's AR net at
         seat 1, all R x R pairs in one batch call (nfsp_evaluate_batch)."""
-        from . import evaluation
         p0 = [e.policy(0, NET_AR, mode) for e in self.replicas]
         p1 = [e.policy(1, NET_AR, mode) for e in self.replicas]
         res = evaluation.evaluate_batch(self.ctx, [(a, b) for a in p0 for b in p1])
@@ -636,47 +597,29 @@ class EngineGroup:
     def memory_tables(self, kind: int) -> list:
         """Every replica's ``SelfPlayEngine.memory_table(kind)`` in one launch
         (nfsp_group_memory_tables): ``[(MemoryTable, [info 0, info 1])]`` by replica."""
-        from . import evaluation as ev
-        tree = ev.GameTree(self.ctx.game)
-        out = torch.empty((self.R, tree.ndec, 3, 3, 3), dtype=torch.int64, device=self.replicas[0].dev)
-        info = (native.MemtabInfo * (2 * self.R))()
-        native.check(self.L.nfsp_group_memory_tables(self.h, int(kind), native.P(out.data_ptr()), info),
-                     "nfsp_group_memory_tables")
-        raw = out.cpu().numpy()
-        return [(ev.MemoryTable(tree, kind, raw[r]), [info[2 * r].to_dict(), info[2 * r + 1].to_dict()])
-                for r in range(self.R)]
+        return _count_tables(self, self.replicas[0].dev, "nfsp_group_memory_tables", self.R, kind, int(kind))
 
     def memory_report_all(self) -> list:
         """``SelfPlayEngine.memory_report`` of every replica: one table launch per memory, and
         one ``evaluate_batch`` per 64 replicas."""
-        from . import evaluation as ev
-        tree = ev.GameTree(self.ctx.game)
         sl, rl = self.memory_tables(native.MEM_SL), self.memory_tables(native.MEM_RL)
         out = []
         for r0 in range(0, self.R, 64):
             rs = range(r0, min(r0 + 64, self.R))
-            out += ev.memory_reports(self.ctx, [self.replicas[r] for r in rs], [sl[r][0] for r in rs],
-                                     [rl[r][0] for r in rs], [(sl[r][1], rl[r][1]) for r in rs], tree)
+            out += diagnostics.memory_reports(self.ctx, [self.replicas[r] for r in rs], [sl[r][0] for r in rs],
+                                              [rl[r][0] for r in rs], [(sl[r][1], rl[r][1]) for r in rs])
         return out
 
     def td_tables(self) -> list:
         """Every replica's ``SelfPlayEngine.td_table()`` in one launch (nfsp_group_td_tables), each
         with its own gamma, quirks and target nets: ``[(MemoryTable, [info 0, info 1])]``."""
-        from . import evaluation as ev
-        tree = ev.GameTree(self.ctx.game)
-        out = torch.empty((self.R, tree.ndec, 3, 3, 3), dtype=torch.int64, device=self.replicas[0].dev)
-        info = (native.MemtabInfo * (2 * self.R))()
-        native.check(self.L.nfsp_group_td_tables(self.h, native.P(out.data_ptr()), info), "nfsp_group_td_tables")
-        raw = out.cpu().numpy()
-        return [(ev.MemoryTable(tree, native.MEM_TD, raw[r]), [info[2 * r].to_dict(), info[2 * r + 1].to_dict()])
-                for r in range(self.R)]
+        return _count_tables(self, self.replicas[0].dev, "nfsp_group_td_tables", self.R, native.MEM_TD)
 
     def q_report_all(self, eta: float | None = None) -> list:
         """``SelfPlayEngine.q_report`` of every replica: one TD launch and one head launch (per 32
         replicas) for all of them."""
-        from . import evaluation as ev
         tds = self.td_tables()
-        return ev.q_reports(self.ctx, self.replicas, [t for t, _ in tds], [i for _, i in tds], eta)
+        return diagnostics.q_reports(self.ctx, self.replicas, [t for t, _ in tds], [i for _, i in tds], eta)
 
     # -- checkpoints (checkpoint.py, DESIGN.md §10) ----------------------------------
     def save(self, path):
@@ -711,105 +654,20 @@ class EngineGroup:
             raise
         return grp
 
-    def close(self):
-        if getattr(self, "h", None):
-            for e in self.replicas:
-                e.h = None
-            self.L.nfsp_group_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def exploitability(ctx, dev_w_ar0: int, dev_w_ar1: int, mode: int = 0) -> dict:
-    """nfsp_exploitability on two packed AR nets given as device pointers."""
-    out = (C.c_double * 4)()
-    native.check(ctx.L.nfsp_exploitability(ctx.h, dev_w_ar0, dev_w_ar1, mode, out), "nfsp_exploitability")
-    return {"br0": out[0], "br1": out[1], "exploitability": out[2], "value0": out[3]}
-
-
-def exploitability_batch(ctx, dev_w_ar0: list, dev_w_ar1: list, mode: int = 0) -> list:
-    """nfsp_exploitability_batch on n pairs of packed AR nets (lists of device pointers)."""
-    n = len(dev_w_ar0)
-    assert len(dev_w_ar1) == n
-    a0 = (C.c_void_p * max(n, 1))(*dev_w_ar0)
-    a1 = (C.c_void_p * max(n, 1))(*dev_w_ar1)
-    out = (C.c_double * (4 * max(n, 1)))()
-    native.check(ctx.L.nfsp_exploitability_batch(ctx.h, a0, a1, n, mode, out), "nfsp_exploitability_batch")
-    return [{"br0": out[4 * k], "br1": out[4 * k + 1], "exploitability": out[4 * k + 2], "value0": out[4 * k + 3]}
-            for k in range(n)]
-
-
-def _opponents(ctx, e, ar_mode, eta, tree) -> list:
-    """[the policy agent 1 - o faces at seat o, o = 0, 1]: engine e's AR policy there, or with
-    ``eta`` the per-hand mixture eta x greedy BR + (1 - eta) x AR it plays in self-play."""
-    from . import evaluation as ev
-    opp = []
-    for o in (0, 1):
-        # a slot that acts with a table (set_act_table) is scored as that table
-        tab = [e.act_table(o, role)[0] is not None for role in (NET_AR, NET_BR)]
-        if eta is None:
-            opp.append(ev.Policy.table(e.acting_policy(o, NET_AR, ar_mode, tree)) if tab[0]
-                       else e.policy(o, NET_AR, ar_mode))
-        else:
-            ar = (e.acting_policy(o, NET_AR, ar_mode, tree) if tab[0]
-                  else ev.policy_table(ctx, e.policy(o, NET_AR, ar_mode), tree).cpu().numpy())
-            br = (e.acting_policy(o, NET_BR, None, tree) if tab[1]
-                  else ev.policy_table(ctx, e.policy(o, NET_BR), tree).cpu().numpy())
-            opp.append(ev.Policy.table(ev.mix(tree, [(eta, br), (1.0 - eta, ar)])))
-    return opp
-
-
-def _br_gaps(ctx, engines, ar_mode, eta) -> list:
-    """br_gap of each engine: per agent {br_exact, br_learned, gap}; one nfsp_evaluate_batch."""
-    from . import evaluation as ev
-    pairs = []
-    keep = []
-    tree = ev.GameTree(ctx.game) if eta is not None else None
-    for e in engines:
-        opp = _opponents(ctx, e, ar_mode, eta, tree)
-        keep.append(opp)
-        pairs += [(e.policy(0, NET_BR), opp[1]), (opp[0], e.policy(1, NET_BR))]
-    res = ev.evaluate_batch(ctx, pairs)
-    out = []
-    for k in range(len(engines)):
-        r0, r1 = res[2 * k], res[2 * k + 1]
-        out.append([{"br_exact": r0["br0"], "br_learned": r0["value0"], "gap": r0["br0"] - r0["value0"]},
-                    {"br_exact": r1["br1"], "br_learned": -r1["value0"], "gap": r1["br1"] + r1["value0"]}])
-    return out
+    def _destroy(self):
+        for e in self.replicas:
+            e.h = None
+        self.L.nfsp_group_destroy(self.h)
 
 
 def _act_rows_dev(e, rows):
     """``rows`` of a set_act_table call as a float32 device tensor of the game's size, or None."""
     if rows is None:
         return None
-    from . import evaluation as ev
     t = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(rows))
     if t.dtype != torch.float32:
         raise TypeError("set_act_table: float32 rows (evaluation.act_rows converts a policy table)")
-    ndec = ev.GameTree(e.ctx.game).ndec
+    ndec = evaluation.GameTree.of(e.ctx.game).ndec
     if t.numel() != ndec * 9:
         raise ValueError(f"set_act_table: expected [{ndec}, 3, 3] rows, got {tuple(t.shape)}")
     return t.to(e.dev).contiguous()
-
-
-def _wrap_device(addr, numel, dtype, device, owner=None) -> torch.Tensor:
-    """Zero-copy torch view of device memory owned by libnfsp.  ``owner`` (the engine) is
-    referenced by the view's array-interface object, which torch keeps alive with the tensor:
-    the engine -- and so the memory -- outlives every view of it."""
-    if numel == 0:
-        return torch.empty(0, dtype=dtype, device=device)
-
-    class _Holder:
-        pass
-    h = _Holder()
-    h.owner = owner
-    esize = torch.empty(0, dtype=dtype).element_size()
-    h.__cuda_array_interface__ = {
-        "shape": (int(numel),), "typestr": torch.empty(0, dtype=dtype).numpy().dtype.str,
-        "data": (int(addr), False), "version": 2, "strides": (esize,)}
-    return torch.as_tensor(h, device=device)

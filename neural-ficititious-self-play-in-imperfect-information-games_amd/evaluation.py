@@ -1,7 +1,7 @@
 """Exact evaluation of any policy, and a tabular equilibrium to measure against.
 
-``engine.exploitability`` scores a pair of AR nets.  This module scores every kind of policy
-the project meets, on the same public tree and with the same f64 walk
+``exploitability`` scores a pair of AR nets.  The rest of this module scores every kind of
+policy the project meets, on the same public tree and with the same f64 walk
 (``nfsp_evaluate_batch``, csrc/evaluate.hip):
 
 * ``Policy.ar(w, mode)``    an average-policy net, as its softmax (mode 0) or argmax (mode 1);
@@ -26,13 +26,15 @@ approximates, with an exact best response and exact averaging.
 
 ``MemoryTable`` is a memory counted per information set on the device (``nfsp_memory_table``,
 csrc/memtab.hip): M_SL as the tabular average strategy the AR net is a fit of, M_RL as what the
-BR net had to learn from; ``memory_reports`` scores the former beside the nets.
+BR net had to learn from; ``diagnostics.memory_reports`` scores the former beside the nets.
 
 ``head_tables`` (``nfsp_head_tables``) reads out the Q values a BR net holds where ``policy_table``
 only has its one-hot argmax, ``td_table`` (``nfsp_td_table``) counts the TD values the net is
 fitted to per (information set, action) over M_RL where it lies, and ``q_report_from`` splits the
 BR net's error against ``best_response``'s exact action values in two: what the data say against
 the truth, and what the net makes of its data.
+
+Nothing here knows an engine: what needs both an engine and this module is ``diagnostics``.
 """
 from __future__ import annotations
 
@@ -54,7 +56,21 @@ class GameTree:
 
     ``nodes`` (NODE_DTYPE), ``obs[ndec, 3]``, ``legal[ndec]`` (whether a raise is executed as a
     raise), ``seat[ndec]`` (who acts), ``pay[nterm, 2, 3, 3]``, ``lev[nlev + 1]``, ``root[2]``
-    (by dealer), ``deal[3, 3]``; ``node_of_row[ndec]`` maps a decision row back to its node."""
+    (by dealer), ``deal[3, 3]``; ``node_of_row[ndec]`` maps a decision row back to its node.
+
+    ``GameTree.of(game)`` is the one shared tree of a game, its arrays read-only."""
+    _shared = {}
+
+    @classmethod
+    def of(cls, game: int = native.GAME_LEDUC) -> "GameTree":
+        game = int(game)
+        if game not in cls._shared:
+            tree = cls(game)
+            for a in vars(tree).values():
+                if isinstance(a, np.ndarray):
+                    a.flags.writeable = False
+            cls._shared[game] = tree
+        return cls._shared[game]
 
     def __init__(self, game: int = native.GAME_LEDUC):
         L = native.load()
@@ -193,14 +209,14 @@ class Policy:
         import torch
         if mode not in (0, 1):
             raise ValueError("mode must be 0 (softmax) or 1 (argmax)")
-        t, p = cls._dev(weights, torch.float32, 30 * 64 + 64 + 64 * 3 + 3)
+        t, p = cls._dev(weights, torch.float32, native.NP)
         return cls(native.POL_AR_ARGMAX if mode else native.POL_AR_SOFTMAX, t, p, owner)
 
     @classmethod
     def br(cls, weights, linear: bool = False, owner=None) -> "Policy":
         """A BR net played greedily; ``linear`` for the Q head of ``EXT_LINEAR_Q``."""
         import torch
-        t, p = cls._dev(weights, torch.float32, 30 * 64 + 64 + 64 * 3 + 3)
+        t, p = cls._dev(weights, torch.float32, native.NP)
         return cls(native.POL_BR_GREEDY_LINEAR if linear else native.POL_BR_GREEDY, t, p, owner)
 
     @classmethod
@@ -212,6 +228,25 @@ class Policy:
 
     def spec(self) -> native.PolicySpec:
         return native.PolicySpec(self.kind, 0, native.P(self.ptr))
+
+
+def exploitability(ctx, dev_w_ar0: int, dev_w_ar1: int, mode: int = 0) -> dict:
+    """nfsp_exploitability on two packed AR nets given as device pointers."""
+    out = (C.c_double * 4)()
+    native.check(ctx.L.nfsp_exploitability(ctx.h, dev_w_ar0, dev_w_ar1, mode, out), "nfsp_exploitability")
+    return {"br0": out[0], "br1": out[1], "exploitability": out[2], "value0": out[3]}
+
+
+def exploitability_batch(ctx, dev_w_ar0: list, dev_w_ar1: list, mode: int = 0) -> list:
+    """nfsp_exploitability_batch on n pairs of packed AR nets (lists of device pointers)."""
+    n = len(dev_w_ar0)
+    assert len(dev_w_ar1) == n
+    a0 = (C.c_void_p * max(n, 1))(*dev_w_ar0)
+    a1 = (C.c_void_p * max(n, 1))(*dev_w_ar1)
+    out = (C.c_double * (4 * max(n, 1)))()
+    native.check(ctx.L.nfsp_exploitability_batch(ctx.h, a0, a1, n, mode, out), "nfsp_exploitability_batch")
+    return [{"br0": out[4 * k], "br1": out[4 * k + 1], "exploitability": out[4 * k + 2], "value0": out[4 * k + 3]}
+            for k in range(n)]
 
 
 def _result(out, k):
@@ -238,7 +273,7 @@ def policy_table(ctx, policy: Policy, tree: GameTree | None = None):
     """``nfsp_policy_table``: the policy as executed at every row, a float64 device tensor
     ``[ndec, 3, 3]`` (``Policy.table`` of it scores bit-identically to ``policy``)."""
     import torch
-    tree = tree or GameTree(ctx.game)
+    tree = tree or GameTree.of(ctx.game)
     out = torch.empty((tree.ndec, 3, 3), dtype=torch.float64, device="cuda")
     spec = policy.spec()
     native.check(ctx.L.nfsp_policy_table(ctx.h, C.byref(spec), native.P(out.data_ptr())), "nfsp_policy_table")
@@ -257,7 +292,7 @@ def best_response(ctx, seat0: Policy, seat1: Policy, values: bool = False, tree:
     information set, so ``q / reach`` is the exact expected chips per action given that it is
     reached -- what a BR net's Q head is to learn there."""
     import torch
-    tree = tree or GameTree(ctx.game)
+    tree = tree or GameTree.of(ctx.game)
     beta = torch.empty((tree.ndec, 3, 3), dtype=torch.float64, device="cuda")
     q = torch.empty((tree.ndec, 3, 3), dtype=torch.float64, device="cuda") if values else None
     reach = torch.empty((tree.ndec, 3), dtype=torch.float64, device="cuda") if values else None
@@ -368,7 +403,7 @@ def memory_table(ctx, kind: int, seat: int, records, out=None, tree: GameTree | 
     list of them, each a contiguous device tensor of whole records or ``(device address, n)``.
     Returns ``(out, info)``; ``MemoryTable(tree, kind, out)`` reads it."""
     import torch
-    tree = tree or GameTree(ctx.game)
+    tree = tree or GameTree.of(ctx.game)
     arr, nsegs = _segments(records, 16 if kind == native.MEM_SL else 32)
     if out is None:
         out = torch.zeros((tree.ndec, 3, 3, 3), dtype=torch.int64, device="cuda")
@@ -387,9 +422,9 @@ def td_table(ctx, seat: int, records, target_w, gamma: float, quirks: int, out=N
     ``quirks``.  The key is the stored s and the stored argmax: under ``QUIRK_ALIAS_RL`` the hand's
     LAST s.  Returns ``(out, info)``; ``MemoryTable(tree, native.MEM_TD, out)`` reads it."""
     import torch
-    tree = tree or GameTree(ctx.game)
+    tree = tree or GameTree.of(ctx.game)
     arr, nsegs = _segments(records, 32)
-    w, addr = Policy._dev(target_w, torch.float32, 30 * 64 + 64 + 64 * 3 + 3)
+    w, addr = Policy._dev(target_w, torch.float32, native.NP)
     if out is None:
         out = torch.zeros((tree.ndec, 3, 3, 3), dtype=torch.int64, device="cuda")
     td = native.TdArgs(native.P(w.data_ptr() if addr is None else addr), float(gamma), int(quirks), 0)
@@ -405,11 +440,11 @@ def head_tables(ctx, nets, acts, tree: GameTree | None = None):
     the Q values it holds, with the bits the rollout acts on.  ``acts[k]``: ``native.ACT_RELU``,
     ``ACT_LINEAR`` or ``ACT_SOFTMAX``.  All three outputs are there, an illegal raise's too."""
     import torch
-    tree = tree or GameTree(ctx.game)
+    tree = tree or GameTree.of(ctx.game)
     n = len(nets)
     if len(acts) != n:
         raise ValueError("one act per net")
-    keep = [Policy._dev(w, torch.float32, 30 * 64 + 64 + 64 * 3 + 3) for w in nets]
+    keep = [Policy._dev(w, torch.float32, native.NP) for w in nets]
     ptrs = (native.P * max(n, 1))(*[t.data_ptr() if p is None else p for t, p in keep])
     act = (native.I32 * max(n, 1))(*[int(a) for a in acts])
     out = torch.empty((n, tree.ndec, 3, 3), dtype=torch.float32, device="cuda")
@@ -517,60 +552,25 @@ def q_report_from(tree: GameTree, seat: int, beta, q, reach, head, td, linear: b
     return out
 
 
-def q_reports(ctx, engines, td_tables, infos, eta=None, tree: GameTree | None = None) -> list:
-    """``SelfPlayEngine.q_report`` of every engine from its TD table: one ``head_tables`` launch for
-    all of their BR nets (per 64), one ``best_response`` per engine."""
-    from .engine import NET_BR, _opponents
-    tree = tree or GameTree(ctx.game)
-    lin = [bool(e.cfg.quirks & native.EXT_LINEAR_Q) for e in engines]
-    head = head_tables(ctx, [e._wptr(a, NET_BR) for e in engines for a in (0, 1)],
-                       [native.ACT_LINEAR if l else native.ACT_RELU for l in lin for _ in (0, 1)], tree).cpu().numpy()
-    out = []
-    for k, e in enumerate(engines):
-        opp = _opponents(ctx, e, 0, eta, tree)
-        beta, q, reach = (t.cpu().numpy() for t in best_response(ctx, opp[0], opp[1], True, tree))
-        out.append([q_report_from(tree, a, beta, q, reach, head[2 * k + a], td_tables[k], lin[k],
-                                  float(e.cfg.gamma), infos[k][a]) for a in (0, 1)])
-    return out
+class _Solver(native.Handle):
+    """What the two solvers share: the tree, a device table read to the host, the handle's release."""
+    DESTROY = None
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.tree = GameTree.of(ctx.game)
+
+    def _host_table(self, policy: Policy) -> np.ndarray:
+        import torch
+        t = native.wrap_device(policy.ptr, self.tree.ndec * 9, torch.float64,
+                               torch.device("cuda", torch.cuda.current_device()), self)
+        return t.cpu().numpy().reshape(self.tree.ndec, 3, 3).copy()
+
+    def _destroy(self):
+        getattr(self.ctx.L, self.DESTROY)(self.h)
 
 
-def memory_reports(ctx, engines, sl_tables, rl_tables, infos, tree: GameTree | None = None) -> list:
-    """``SelfPlayEngine.memory_report`` of every engine from its tables: the AR pair and the two
-    M_SL tables of all of them scored in one ``evaluate_batch`` call."""
-    tree = tree or GameTree(ctx.game)
-    from .engine import NET_AR
-    tabs = [(sl.policy("argmax"), sl.policy("mass")) for sl in sl_tables]
-    pairs = []
-    for e, (am, ms) in zip(engines, tabs):
-        pa, pm = Policy.table(am), Policy.table(ms)
-        pairs += [(e.policy(0, NET_AR), e.policy(1, NET_AR)), (pa, pa), (pm, pm)]
-    res = evaluate_batch(ctx, pairs)
-    legal = np.ones((tree.ndec, 3, 3), bool)
-    legal[~tree.legal, :, 2] = False
-    out = []
-    for k, e in enumerate(engines):
-        sl, rl = sl_tables[k], rl_tables[k]
-        ar, am, ms = (res[3 * k + j]["exploitability"] for j in range(3))
-        mass = tree.remap(tabs[k][1])
-        num = den = 0.0
-        for seat in (0, 1):
-            net = policy_table(ctx, e.policy(seat, NET_AR), tree).cpu().numpy()
-            rows = tree.seat == seat
-            w = sl.n[rows].astype(np.float64)
-            num += float((w * np.abs(net[rows] - mass[rows]).sum(axis=2)).sum())
-            den += float(w.sum())
-        out.append({
-            "exploitability_ar": ar, "exploitability_sl_argmax": am, "exploitability_sl_mass": ms,
-            # what the net adds to the strategy it is a fit of (> 0: the net is more exploitable)
-            "fit_gap_argmax": ar - am, "fit_gap_mass": ar - ms,
-            "sl_empty_sets": int((sl.n == 0).sum()),
-            "rl_empty_actions": int(((rl.counts == 0) & legal).sum()),
-            "ar_mass_l1": num / den if den > 0 else float("nan"),
-            "sl_info": infos[k][0], "rl_info": infos[k][1]})
-    return out
-
-
-class XfpSolver:
+class XfpSolver(_Solver):
     """Full-width extensive-form fictitious play on the evaluator's tree (``nfsp_xfp_*``): the
     ideal curve of the algorithm NFSP approximates.  ``cfgs`` is one ``(eta, weight)`` per
     independent run (weight: ``native.XFP_WEIGHT_UNIFORM`` / ``_LINEAR`` or "uniform" /
@@ -580,10 +580,10 @@ class XfpSolver:
     ``average(k)`` is run k's average strategy as a ``Policy``."""
 
     WEIGHTS = {"uniform": native.XFP_WEIGHT_UNIFORM, "linear": native.XFP_WEIGHT_LINEAR}
+    DESTROY = "nfsp_xfp_destroy"
 
     def __init__(self, ctx, cfgs=((0.0, native.XFP_WEIGHT_UNIFORM),)):
-        self.ctx = ctx
-        self.tree = GameTree(ctx.game)
+        super().__init__(ctx)
         self.cfgs = [(float(eta), int(self.WEIGHTS.get(w, w))) for eta, w in cfgs]
         self.n = len(self.cfgs)
         arr = (native.XfpCfg * max(self.n, 1))(*[native.XfpCfg(eta, w, 0) for eta, w in self.cfgs])
@@ -609,11 +609,7 @@ class XfpSolver:
         return Policy(native.POL_TABLE, None, p.value, self)
 
     def average_table(self, run: int = 0) -> np.ndarray:
-        import torch
-        from .engine import _wrap_device
-        t = _wrap_device(self.average(run).ptr, self.tree.ndec * 9, torch.float64,
-                         torch.device("cuda", torch.cuda.current_device()), self)
-        return t.cpu().numpy().reshape(self.tree.ndec, 3, 3).copy()
+        return self._host_table(self.average(run))
 
     def state(self, run: int = 0) -> tuple:
         """(S, B, W) of a run: the weighted sum of the best responses' realisation plans and
@@ -625,25 +621,15 @@ class XfpSolver:
                                                B.ctypes.data_as(native.P), C.byref(W)), "nfsp_xfp_state")
         return S, B, W.value
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.L.nfsp_xfp_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class CfrSolver:
+class CfrSolver(_Solver):
     """CFR+ on the evaluator's tree (``nfsp_cfr_*``): ``run(n)`` continues the run by n
     iterations, ``average()`` is the linearly weighted average strategy as a ``Policy``."""
 
+    DESTROY = "nfsp_cfr_destroy"
+
     def __init__(self, ctx):
-        self.ctx = ctx
-        self.tree = GameTree(ctx.game)
+        super().__init__(ctx)
         h = native.P()
         native.check(ctx.L.nfsp_cfr_create(ctx.h, C.byref(h)), "nfsp_cfr_create")
         self.h = h
@@ -664,11 +650,7 @@ class CfrSolver:
         return Policy(native.POL_TABLE, None, p.value, self)
 
     def average_table(self) -> np.ndarray:
-        import torch
-        from .engine import _wrap_device
-        t = _wrap_device(self.average().ptr, self.tree.ndec * 9, torch.float64,
-                         torch.device("cuda", torch.cuda.current_device()), self)
-        return t.cpu().numpy().reshape(self.tree.ndec, 3, 3).copy()
+        return self._host_table(self.average())
 
     def state(self) -> tuple:
         """(R, S): the regrets and the strategy sums, ``[ndec, 3, 3]`` each."""
@@ -677,14 +659,3 @@ class CfrSolver:
         native.check(self.ctx.L.nfsp_cfr_state(self.h, R.ctypes.data_as(native.P), S.ctypes.data_as(native.P)),
                      "nfsp_cfr_state")
         return R, S
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.L.nfsp_cfr_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -25,6 +25,9 @@ EXT_MSE_Q = 256
 TEXTBOOK_MSE = TEXTBOOK | EXT_MSE_Q
 TEXTBOOK_MSE_DECAY = TEXTBOOK_MSE & ~EXT_EPS_CONST      # epsilon / iteration, as the reference
 
+NP = 30 * 64 + 64 + 64 * 3 + 3      # floats of a packed net: W1 | b1 | W2 | b2 (include/nfsp.h)
+NET_AR, NET_BR, NET_TARGET = 0, 1, 2
+
 P = C.c_void_p
 I32, I64, U32, U64, F32, F64 = C.c_int, C.c_int64, C.c_uint, C.c_uint64, C.c_float, C.c_double
 
@@ -295,7 +298,41 @@ def stream_handle():
     return P(torch.cuda.current_stream().cuda_stream)
 
 
-class Context:
+def wrap_device(addr, numel, dtype, device, owner=None):
+    """Zero-copy torch view of device memory owned by libnfsp.  ``owner`` (the engine) is
+    referenced by the view's array-interface object, which torch keeps alive with the tensor:
+    the engine -- and so the memory -- outlives every view of it."""
+    import torch
+    if numel == 0:
+        return torch.empty(0, dtype=dtype, device=device)
+
+    class _Holder:
+        pass
+    h = _Holder()
+    h.owner = owner
+    esize = torch.empty(0, dtype=dtype).element_size()
+    h.__cuda_array_interface__ = {
+        "shape": (int(numel),), "typestr": torch.empty(0, dtype=dtype).numpy().dtype.str,
+        "data": (int(addr), False), "version": 2, "strides": (esize,)}
+    return torch.as_tensor(h, device=device)
+
+
+class Handle:
+    """Owner of a library handle ``h``: ``close()``, and the collector, give it to ``_destroy``."""
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._destroy()
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Context(Handle):
     """Owns one ``nfsp_ctx`` (n envs on the current device), bound to torch's stream."""
 
     def __init__(self, n_envs: int, seed: int = 1234, device: int | None = None, game: int = GAME_LEDUC):
@@ -314,13 +351,5 @@ class Context:
     def call(self, name, *args):
         check(getattr(self.L, name)(self.h, *args), name)
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.nfsp_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _destroy(self):
+        self.L.nfsp_destroy(self.h)

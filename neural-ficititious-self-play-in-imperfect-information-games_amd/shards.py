@@ -42,16 +42,17 @@ from typing import Callable, Sequence
 
 import torch
 
+from . import native
+
 
 def ar_nets_digest(engine) -> str:
     """sha256 of both agents' AR nets as they are now (synchronises the device): equal on
     every rank after an exchange that worked (bench.py checks it over the ranks)."""
     import hashlib
-    from .engine import NET_AR
     torch.cuda.synchronize()
     h = hashlib.sha256()
     for a in (0, 1):
-        h.update(engine.get_weights(a, NET_AR).tobytes())
+        h.update(engine.get_weights(a, native.NET_AR).tobytes())
     return h.hexdigest()
 
 
@@ -117,16 +118,14 @@ class AvgPolicyExchange:
 
     def __init__(self, engine, dist, every: int = 1, transport: str = "auto", gain: float = 1.0,
                  src: int = 0):
-        from . import native
-        from .engine import NET_AR, _wrap_device
         self.engine, self.dist, self.every, self.gain = engine, dist, int(every), float(gain)
         self.world, self.rank = dist.get_world_size(), dist.get_rank()
         backend = dist.get_backend()
         self.transport = ("rccl" if backend == "nccl" else "host") if transport == "auto" else transport
-        self._wrap, self._dev = _wrap_device, engine.dev
+        self._dev = engine.dev
         # the common start: rank 0's AR nets everywhere (one broadcast)
         torch.cuda.synchronize()
-        views = [engine.weights_tensor(a, NET_AR) for a in (0, 1)]
+        views = [engine.weights_tensor(a, native.NET_AR) for a in (0, 1)]
         flat = torch.cat([v.reshape(-1) for v in views])
         if backend == "gloo":
             x = flat.cpu()
@@ -194,7 +193,7 @@ class AvgPolicyExchange:
         """nfsp_exchange_fn: the engine synchronised its AR stream; leave the sum over ranks
         of the [2][NP] deltas at ptr (device), complete on return."""
         try:
-            t = self._wrap(ptr, n, torch.float32, self._dev)
+            t = native.wrap_device(ptr, n, torch.float32, self._dev)
             if self.dist.get_backend() == "gloo":
                 x = t.cpu()
                 self.dist.all_reduce(x)

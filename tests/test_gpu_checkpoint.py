@@ -213,7 +213,7 @@ def test_group_resume_restores_the_exchange_base(pkg, tmp_path):
 def test_exchange_continues_after_a_load(pkg, tmp_path):
     """A host-callback exchange that is not the identity (S = 2 D, scale 0.75, every slice):
     re-issued after the load, the continuation is the uninterrupted run's."""
-    wrap = pkg.engine._wrap_device
+    wrap = pkg.native.wrap_device
 
     def doubling(_user, ptr, n):
         try:
