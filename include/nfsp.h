@@ -845,6 +845,76 @@ int nfsp_engine_set_act_table(nfsp_engine* e, int agent, int role,
 int nfsp_engine_get_act_table(nfsp_engine* e, int agent, int role, const float** dev_rows, int64_t* misses);
 int nfsp_group_set_act_table(nfsp_group* g, int replica, int agent, int role, const float* dev_rows);
 
+/* ---- tabular NFSP: Q tables from M_RL, M_SL tables as rows (csrc/memtab.hip k_memtab's fourth
+ *      kind; csrc/tabq.hip k_table_rows) ----
+ * Learners without function approximation that see exactly the nets' data, for the tables that act
+ * above: the BR role's net replaced by a Q table fitted to the live M_RL records, the AR role's by
+ * M_SL's own table.  Neither is the reference's algorithm; both are diagnostics.
+ *
+ * Tabular Q by fitted-Q sweeps over one seat's M_RL records.  Q is f32 [ndec][3][3] over
+ * nfsp_tree_export's rows, the act-table layout.  One sweep is Q_{j+1} = rows(TDQ(M_RL; Q_j), fill).
+ * TDQ is NFSP_MEM_TD with the target net replaced by the table.  For a matched record (its stored s
+ * an information set of the seat, its stored argmax k <= 2): sid2 = the lookup of (seat, s2), the
+ * same staged hash; qmax = sid2 < 0 ? 0.0f : fmaxf(fmaxf(Q[sid2][0], Q[sid2][1]), Q[sid2][2]) --
+ * all three entries count, an illegal raise's too, exactly as the net's three outputs do;
+ * terminal = t && !(quirks & NFSP_QUIRK_TERMINAL_BOOTSTRAP); v = r for a terminal record, else
+ * r + gamma * qmax with NFSP_MEM_TD's arithmetic (r as float, the product and the sum in double,
+ * each rounded, one rounding to float).  Fields as NFSP_MEM_TD: [k][0] the count, [k][1] the sum of
+ * fix(v), [k][2] the sum of fix(qmax) over the records that bootstrap; info and `clamped` as there.
+ * No quirk bit but TERMINAL_BOOTSTRAP is read.  A terminal s2 is no information set and bootstraps
+ * 0 (it counts in field 0 and adds 0 to field 2): the table is immune to the terminal-bootstrap
+ * quirk's value where the net is not.
+ * rows, stat NFSP_ROWS_TD_MEAN, per entry with count c and sum S = field 1:
+ * (float)(((double)S / (double)c) * 2^-24) if c > 0, else fill[entry]; fill == NULL means 0.  An
+ * unseen (set, action) therefore stays at fill through every sweep, and Q_0 = fill.
+ * Sweeps are Jacobi: sweep j reads buffer j & 1 and writes the other, never in place.  The sums are
+ * integers, so the bits depend neither on the order of accumulation nor on the grid.
+ * Convergence: without NFSP_QUIRK_ALIAS_RL a record's s2 is a strictly later decision of the same
+ * hand, so the successor relation on a seat's information sets is acyclic and no deeper than the
+ * tree's nlev (nfsp_tree_size): sweeps = nlev reaches the fixed point of the sample-mean Bellman
+ * operator exactly, and a further sweep changes no bit.  Under ALIAS_RL the key is the hand's LAST
+ * s and nothing is promised beyond "K sweeps of the stated operator".
+ *
+ * M_SL rows, per (row, rank) from an NFSP_MEM_SL table, with m_a = field 1 of action a,
+ * M = (m0 + m1) + m2 in int64, c_a = field 0 and n = c0 + c1 + c2:
+ *   NFSP_ROWS_SL_MASS    out[a] = (float)((double)m_a / (double)M)
+ *   NFSP_ROWS_SL_ARGMAX  out[a] = (float)((double)c_a / (double)n)
+ * For both the whole row is fill's row (0 with fill == NULL) where n == 0, where M <= 0 or where any
+ * m_a < 0: the memory tables' two strategies before the raise-to-call remap, with a declared value
+ * where M_SL is empty or holds no mass. */
+#define NFSP_MEM_TDQ 3
+#define NFSP_ROWS_SL_MASS 0
+#define NFSP_ROWS_SL_ARGMAX 1
+#define NFSP_ROWS_TD_MEAN 2
+#define NFSP_TABQ_MAX_SWEEPS 64
+#define NFSP_TABLE_ROWS_MAX 65535
+/* Raw form, one sweep's sums: RlRec segments of `seat` against the joint Q table dev_q (only the
+ * seat's rows are read), as nfsp_td_table otherwise.  Synchronises the ctx stream. */
+int nfsp_tdq_table(nfsp_ctx* ctx, int game, int seat, const nfsp_mem_segment* segs, int nsegs,
+                   const float* dev_q /*[ndec][3][3]*/, double gamma, uint32_t quirks, int64_t* dev_out,
+                   nfsp_memtab_info* info);
+/* n joint int64 tables -> n f32 row tables, one workgroup each, on the ctx stream; synchronises.
+ * dev_changed[t] (if given): the entries of table t whose f32 bits differ from dev_prev's (0
+ * without dev_prev).  dev_prev may be dev_rows itself: an entry is compared before it is stored.
+ * At most NFSP_TABLE_ROWS_MAX tables. */
+int nfsp_table_rows(nfsp_ctx* ctx, int game, int stat, const int64_t* dev_tab /*[n][ndec][3][3][3]*/,
+                    const float* dev_fill /*[n][ndec][3][3] or NULL*/, const float* dev_prev /*or NULL*/, int n,
+                    float* dev_rows /*[n][ndec][3][3]*/, int32_t* dev_changed /*[n] or NULL*/);
+/* `sweeps` (1..NFSP_TABQ_MAX_SWEEPS) fitted-Q sweeps over an engine's live M_RL records, each
+ * agent against its own rows of the joint table with its cfg.gamma and cfg.quirks: 3 launches per
+ * sweep on the ctx stream, the two Q buffers in the library's workspace, ONE synchronisation and
+ * one info copy at the end.  dev_q: the final table; dev_tab (or NULL): the last sweep's sums;
+ * info: the last sweep's (only `clamped` depends on the sweep); *changed: the entries the last sweep
+ * changed.  Requires what nfsp_engine_memory_table requires (a step boundary); a group replica's
+ * handle is accepted.  Neither the engine's state nor its digest changes. */
+int nfsp_engine_tabular_q(nfsp_engine* e, int sweeps, const float* dev_fill /*[ndec][3][3] or NULL*/,
+                          float* dev_q /*[ndec][3][3]*/, int64_t* dev_tab /*[ndec][3][3][3] or NULL*/,
+                          nfsp_memtab_info info[2], int32_t* changed);
+/* Every replica's in the same launches (2R jobs per sweep), each replica with its own gamma and
+ * quirks: arrays as above with a leading [R]. */
+int nfsp_group_tabular_q(nfsp_group* g, int sweeps, const float* dev_fill, float* dev_q, int64_t* dev_tab,
+                         nfsp_memtab_info* info /*[R][2]*/, int32_t* changed /*[R]*/);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,14 @@
 // record's s2 -- lanes without a record or an information set forward x = 0, fwd_lds ballots --
 // and adds fix(v) and fix(max Q).  gamma, quirks and the net ride in the table's job, so the
 // replicas of a heterogeneous group go through one launch.
+//
+// The fourth kind, NFSP_MEM_TDQ (nfsp_tdq_table), is the third with a table in the target net's
+// place: the seat's Q rows lie in LDS in front of the bins, compact by sid as the bins are, and a
+// record's bootstrap is the largest of the three entries at lookup(seat, s2), 0 where s2 is no
+// information set.  There is no forward, so it keeps MT_U records per lane in flight as the
+// counting kinds do.  nfsp_engine_tabular_q / nfsp_group_tabular_q run K fitted-Q sweeps with it:
+// per sweep k_memtab<TDQ>, k_memtab_sum and k_table_rows (tabq.hip) on the stream, the Q tables
+// alternating between two buffers of the workspace, and one synchronisation at the end.
 #include <math.h>
 
 #include <map>
@@ -115,7 +123,8 @@ struct MtTab {                            // one table: a seat's records in up t
   int64_t n[MT_MAX_SEG];                  // records
   int64_t* out;                           // the joint table [ndec][3][3][3] the seat's rows go to
   int32_t nseg, seat;
-  const float* tw;                        // NFSP_MEM_TD: the target net (packed), gamma and the quirks
+  const float* tw;                        // NFSP_MEM_TD: the target net (packed), gamma and the quirks;
+                                          //   NFSP_MEM_TDQ: the joint Q table [ndec][3][3] in its place
   double gamma;
   uint32_t quirks, pad;
 };
@@ -141,7 +150,7 @@ __device__ inline void lds_add(int64_t* p, int64_t v) {
 
 // One record (sid >= 0) into the bins.  SL: val = fix(a), the count goes to action k.  RL:
 // val[0] = r in half units, val[1] = t, both to k.  TD: val[0] = fix(v), val[1] = fix(max Q) of a
-// record that bootstraps, both to k.
+// record that bootstraps, both to k; TDQ as TD.
 template <int KIND>
 __device__ inline void mt_accum(int64_t* bins, int sid, int k, const int64_t val[3]) {
   constexpr int NF = KIND == NFSP_MEM_SL ? 2 : 3;
@@ -168,11 +177,12 @@ __global__ void __launch_bounds__(MT_WG) k_memtab(MtArgs A) {
   extern __shared__ __attribute__((aligned(16))) int64_t mt_lds[];
   constexpr int NF = KIND == NFSP_MEM_SL ? 2 : 3;
   constexpr int RQ = KIND == NFSP_MEM_SL ? 1 : 2;      // 16-byte words per record
-  constexpr int NETQ = KIND == NFSP_MEM_TD ? NET_LDS / 2 : 0;   // TD: the target net comes first
   const MtTab& T = A.tabs[blockIdx.y];
   const int seat = T.seat;
   const int nv = A.nrows[seat] * 9 * NF;
-  float* sw = reinterpret_cast<float*>(mt_lds);        // [NET_LDS], fwd_lds' layout and bank map
+  // TD: the target net comes first; TDQ: the seat's Q rows [sid][3], an even number of floats
+  const int NETQ = KIND == NFSP_MEM_TD ? NET_LDS / 2 : KIND == NFSP_MEM_TDQ ? (A.nrows[seat] * 9 + 1) / 2 : 0;
+  float* sw = reinterpret_cast<float*>(mt_lds);        // TD: [NET_LDS], fwd_lds' layout and bank map
   int64_t* bins = mt_lds + NETQ;                       // [nv]
   int64_t* ctr = bins + nv;                            // matched, unmatched, clamped
   uint32_t* hk = reinterpret_cast<uint32_t*>(ctr + 4);
@@ -183,6 +193,8 @@ __global__ void __launch_bounds__(MT_WG) k_memtab(MtArgs A) {
     hv[h] = A.vals[seat * MT_H + h];
   }
   if (KIND == NFSP_MEM_TD) stage_net_lds(sw, T.tw, threadIdx.x, MT_WG);
+  if (KIND == NFSP_MEM_TDQ)                            // compact row c of the seat is row A.rows[c] of the joint table
+    for (int v = threadIdx.x; v < A.nrows[seat] * 9; v += MT_WG) sw[v] = T.tw[A.rows[seat * MT_MAX_ROWS + v / 9] * 9 + v % 9];
   const double gamma = T.gamma;                        // TD; uniform over the workgroup, as act
   const unsigned quirks = T.quirks;
   const int act = br_act(quirks);
@@ -222,6 +234,15 @@ __global__ void __launch_bounds__(MT_WG) k_memtab(MtArgs A) {
           if (KIND == NFSP_MEM_RL) {
             val[0] = (int8_t)(rec[u].z >> 16);
             val[1] = (rec[u].z >> 8) & 1u;
+          } else if (KIND == NFSP_MEM_TDQ) {
+            if (sid >= 0) {
+              const int sid2 = mt_find(hk, hv, rec[u].y);          // s2 is any word: a terminal one is no set
+              const float qmax = sid2 < 0 ? 0.f : fmaxf(fmaxf(sw[sid2 * 3], sw[sid2 * 3 + 1]), sw[sid2 * 3 + 2]);
+              const float r = (float)(int8_t)((rec[u].z >> 16) & 0xFFu) * 0.5f;
+              const bool terminal = !(quirks & NFSP_QUIRK_TERMINAL_BOOTSTRAP) && ((rec[u].z >> 8) & 1u);
+              val[0] = mt_fix(td_value(r, qmax, gamma, terminal), clamped);
+              val[1] = terminal ? 0 : mt_fix(qmax, clamped);
+            }
           } else {
             // every lane of the wave forwards (fwd_lds ballots): one without a record or a bin
             // forwards x = 0 and drops the result.  s2 is any 30-bit word, fwd_lds exact for it
@@ -334,27 +355,39 @@ int mt_lookup(int game, const MtHost** host, MtDev* dev) {
 
 namespace {
 
-// The tables of `tabs` (their `out` set) on `st`; info[t] filled; synchronises st.
-int mt_run(hipStream_t st, int game, int kind, std::vector<MtTab>& tabs, nfsp_memtab_info* info) {
+// A call in three parts, all under g_mu: mt_plan sizes the launch for `nt` tables and lays the
+// workspace out -- `sets` job tables (a sweep alternates between two), the info, the partials
+// and `extra` bytes of the caller's behind them; mt_enqueue uploads nothing and synchronises
+// nothing, it launches k_memtab and k_memtab_sum for one job table; mt_finish copies the last
+// launch's info and synchronises.  K sweeps are K enqueues between one plan and one finish.
+struct MtPlan {
+  MtArgs A{};                             // A.tabs: job table 0
+  int nt = 0, kind = 0, sets = 1;
+  size_t lds = 0, b_set = 0;
+  std::vector<int64_t> total;             // records per table
+  char* extra = nullptr;                  // 16-byte aligned
+  MtWork* W = nullptr;
+};
+
+int mt_plan(int game, int kind, const std::vector<MtTab>& tabs, int sets, size_t extra, MtPlan* P) {
   const int nt = (int)tabs.size();
-  if (nt == 0) return NFSP_OK;
   const MtHost* M = nullptr;
   int rc = mt_host(game, &M);
   if (rc != NFSP_OK) return rc;
   int64_t maxn = 0;
-  std::vector<int64_t> total(nt, 0);
+  P->total.assign(nt, 0);
   for (int t = 0; t < nt; ++t) {
-    for (int s = 0; s < tabs[t].nseg; ++s) total[t] += tabs[t].n[s];
-    NFSP_REQUIRE(total[t] < (1ll << 31), "memory table: 2^31 records or more in one table");
-    maxn = total[t] > maxn ? total[t] : maxn;
+    for (int s = 0; s < tabs[t].nseg; ++s) P->total[t] += tabs[t].n[s];
+    NFSP_REQUIRE(P->total[t] < (1ll << 31), "memory table: 2^31 records or more in one table");
+    maxn = P->total[t] > maxn ? P->total[t] : maxn;
   }
   const int NF = kind == NFSP_MEM_SL ? 2 : 3;
   const int nrmax = M->nrows[0] > M->nrows[1] ? M->nrows[0] : M->nrows[1];
   const int nvp = nrmax * 9 * NF + 3;
   const bool td = kind == NFSP_MEM_TD;
-  const size_t lds = sizeof(int64_t) * ((size_t)(nvp - 3) + 4) + MT_H * (sizeof(uint32_t) + sizeof(uint16_t)) +
-                     (td ? sizeof(float) * NET_LDS : 0);
-  NFSP_REQUIRE(lds <= (size_t)MT_LDS_MAX, "memory table: the bins do not fit the workgroup's LDS");
+  const size_t front = td ? sizeof(float) * NET_LDS : kind == NFSP_MEM_TDQ ? sizeof(int64_t) * (size_t)((nrmax * 9 + 1) / 2) : 0;
+  P->lds = sizeof(int64_t) * ((size_t)(nvp - 3) + 4) + MT_H * (sizeof(uint32_t) + sizeof(uint16_t)) + front;
+  NFSP_REQUIRE(P->lds <= (size_t)MT_LDS_MAX, "memory table: the bins do not fit the workgroup's LDS");
   const int64_t turn = (int64_t)MT_WG * (td ? TD_U : MT_U);      // two turns of a workgroup per block
   int64_t nb = (maxn + turn * 2 - 1) / (turn * 2);
   const int64_t cap = MT_BLOCKS / nt > 1 ? MT_BLOCKS / nt : 1;
@@ -362,12 +395,13 @@ int mt_run(hipStream_t st, int game, int kind, std::vector<MtTab>& tabs, nfsp_me
 
   int dev = 0;
   NFSP_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_mu);
   MtDev D;
   if ((rc = mt_device(dev, game, *M, &D)) != NFSP_OK) return rc;
   MtWork& W = g_work[dev];
-  const size_t b_tabs = (sizeof(MtTab) * nt + 15) & ~(size_t)15, b_info = sizeof(int64_t) * 4 * nt;
-  const size_t need = b_tabs + b_info + sizeof(int64_t) * (size_t)nt * nb * nvp;
+  P->b_set = (sizeof(MtTab) * nt + 15) & ~(size_t)15;
+  const size_t b_info = sizeof(int64_t) * 4 * nt;
+  const size_t b_part = (sizeof(int64_t) * (size_t)nt * nb * nvp + 15) & ~(size_t)15;
+  const size_t need = P->b_set * sets + b_info + b_part + extra;
   if (W.cap < need) {
     if (W.buf) NFSP_HIP(hipFree(W.buf));
     W.buf = nullptr;
@@ -377,35 +411,112 @@ int mt_run(hipStream_t st, int game, int kind, std::vector<MtTab>& tabs, nfsp_me
   }
   for (hipEvent_t& ev : W.ev)
     if (!ev) NFSP_HIP(hipEventCreate(&ev));
-  MtArgs A{};
+  MtArgs& A = P->A;
   A.keys = D.keys;
   A.vals = D.vals;
   A.rows = D.rows;
   A.tabs = reinterpret_cast<const MtTab*>(W.buf);
-  A.info = reinterpret_cast<int64_t*>(W.buf + b_tabs);
-  A.partial = reinterpret_cast<int64_t*>(W.buf + b_tabs + b_info);
+  A.info = reinterpret_cast<int64_t*>(W.buf + P->b_set * sets);
+  A.partial = reinterpret_cast<int64_t*>(W.buf + P->b_set * sets + b_info);
   A.nb = (int32_t)nb;
   A.nvp = nvp;
   A.nrows[0] = M->nrows[0];
   A.nrows[1] = M->nrows[1];
-  NFSP_HIP(hipMemcpyAsync(W.buf, tabs.data(), sizeof(MtTab) * nt, hipMemcpyHostToDevice, st));
-  NFSP_HIP(hipEventRecord(W.ev[0], st));
-  const dim3 grid((unsigned)nb, (unsigned)nt);
-  if (kind == NFSP_MEM_SL) k_memtab<NFSP_MEM_SL, MT_U><<<grid, MT_WG, lds, st>>>(A);
-  else if (kind == NFSP_MEM_RL) k_memtab<NFSP_MEM_RL, MT_U><<<grid, MT_WG, lds, st>>>(A);
-  else k_memtab<NFSP_MEM_TD, TD_U><<<grid, MT_WG, lds, st>>>(A);
+  P->nt = nt;
+  P->kind = kind;
+  P->sets = sets;
+  P->extra = W.buf + P->b_set * sets + b_info + b_part;
+  P->W = &W;
+  return NFSP_OK;
+}
+
+// job table `set` <- tabs (pageable host memory: the copy has left it when the call returns)
+int mt_upload(hipStream_t st, const MtPlan& P, int set, const std::vector<MtTab>& tabs) {
+  NFSP_HIP(hipMemcpyAsync(P.W->buf + P.b_set * set, tabs.data(), sizeof(MtTab) * P.nt, hipMemcpyHostToDevice, st));
+  return NFSP_OK;
+}
+
+int mt_enqueue(hipStream_t st, const MtPlan& P, int set) {
+  MtArgs A = P.A;
+  A.tabs = reinterpret_cast<const MtTab*>(P.W->buf + P.b_set * set);
+  const dim3 grid((unsigned)A.nb, (unsigned)P.nt);
+  if (P.kind == NFSP_MEM_SL) k_memtab<NFSP_MEM_SL, MT_U><<<grid, MT_WG, P.lds, st>>>(A);
+  else if (P.kind == NFSP_MEM_RL) k_memtab<NFSP_MEM_RL, MT_U><<<grid, MT_WG, P.lds, st>>>(A);
+  else if (P.kind == NFSP_MEM_TD) k_memtab<NFSP_MEM_TD, TD_U><<<grid, MT_WG, P.lds, st>>>(A);
+  else k_memtab<NFSP_MEM_TDQ, MT_U><<<grid, MT_WG, P.lds, st>>>(A);
   NFSP_LAUNCHED("k_memtab");
-  k_memtab_sum<<<dim3((unsigned)((nvp + 63) / 64), (unsigned)nt), MT_WG, 0, st>>>(A, kind);
+  k_memtab_sum<<<dim3((unsigned)((A.nvp + 63) / 64), (unsigned)P.nt), MT_WG, 0, st>>>(A, P.kind);
   NFSP_LAUNCHED("k_memtab_sum");
-  NFSP_HIP(hipEventRecord(W.ev[1], st));
-  std::vector<int64_t> h((size_t)4 * nt);
-  NFSP_HIP(hipMemcpyAsync(h.data(), A.info, b_info, hipMemcpyDeviceToHost, st));
+  return NFSP_OK;
+}
+
+// after the last enqueue (W.ev[0] recorded before the first): the one info copy, the one wait
+int mt_finish(hipStream_t st, const MtPlan& P, nfsp_memtab_info* info) {
+  NFSP_HIP(hipEventRecord(P.W->ev[1], st));
+  std::vector<int64_t> h((size_t)4 * P.nt);
+  NFSP_HIP(hipMemcpyAsync(h.data(), P.A.info, sizeof(int64_t) * 4 * P.nt, hipMemcpyDeviceToHost, st));
   NFSP_HIP(hipStreamSynchronize(st));
   float ms = 0.f;
-  NFSP_HIP(hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
+  NFSP_HIP(hipEventElapsedTime(&ms, P.W->ev[0], P.W->ev[1]));
   g_last_ms = ms;
-  for (int t = 0; t < nt; ++t)
-    if (info) info[t] = nfsp_memtab_info{total[t], h[4 * t + 1], h[4 * t + 2], h[4 * t + 3]};
+  for (int t = 0; t < P.nt; ++t)
+    if (info) info[t] = nfsp_memtab_info{P.total[t], h[4 * t + 1], h[4 * t + 2], h[4 * t + 3]};
+  return NFSP_OK;
+}
+
+// The tables of `tabs` (their `out` set) on `st`; info[t] filled; synchronises st.
+int mt_run(hipStream_t st, int game, int kind, std::vector<MtTab>& tabs, nfsp_memtab_info* info) {
+  if (tabs.empty()) return NFSP_OK;
+  std::lock_guard<std::mutex> lk(g_mu);
+  MtPlan P;
+  int rc = mt_plan(game, kind, tabs, 1, 0, &P);
+  if (rc != NFSP_OK || (rc = mt_upload(st, P, 0, tabs)) != NFSP_OK) return rc;
+  NFSP_HIP(hipEventRecord(P.W->ev[0], st));
+  if ((rc = mt_enqueue(st, P, 0)) != NFSP_OK) return rc;
+  return mt_finish(st, P, info);
+}
+
+// K fitted-Q sweeps (include/nfsp.h nfsp_engine_tabular_q) over R joint tables: tabs[2r + a] is
+// agent a of engine r with its segments, gamma and quirks set; its Q pointer and `out` are set
+// here.  Q_0 = fill (0 where NULL); sweep j reads Q buffer j & 1 and writes the other, through the
+// int64 table (dev_tab, or a scratch one of the workspace).  3K launches, one synchronisation.
+int mt_sweeps(hipStream_t st, int game, std::vector<MtTab>& tabs, int sweeps, const float* dev_fill, float* dev_q,
+              int64_t* dev_tab, nfsp_memtab_info* info, int32_t* changed) {
+  const int nt = (int)tabs.size(), R = nt / 2;
+  if (R == 0) return NFSP_OK;
+  const MtHost* M = nullptr;
+  int rc = mt_host(game, &M);
+  if (rc != NFSP_OK) return rc;
+  const size_t nq = (size_t)R * M->ndec * 9;
+  const size_t b_q = (sizeof(float) * nq + 15) & ~(size_t)15, b_tab = dev_tab ? 0 : sizeof(int64_t) * nq * 3;
+  const size_t b_chg = (sizeof(int32_t) * R + 15) & ~(size_t)15;
+  std::lock_guard<std::mutex> lk(g_mu);
+  MtPlan P;
+  if ((rc = mt_plan(game, NFSP_MEM_TDQ, tabs, 2, 2 * b_q + b_chg + b_tab, &P)) != NFSP_OK) return rc;
+  float* q[2] = {reinterpret_cast<float*>(P.extra), reinterpret_cast<float*>(P.extra + b_q)};
+  int32_t* chg = reinterpret_cast<int32_t*>(P.extra + 2 * b_q);
+  int64_t* tab = dev_tab ? dev_tab : reinterpret_cast<int64_t*>(P.extra + 2 * b_q + b_chg);
+  for (int set = 0; set < 2; ++set) {
+    for (int t = 0; t < nt; ++t) {
+      tabs[t].tw = q[set] + (size_t)(t / 2) * M->ndec * 9;
+      tabs[t].out = tab + (size_t)(t / 2) * M->ndec * 27;
+    }
+    if ((rc = mt_upload(st, P, set, tabs)) != NFSP_OK) return rc;
+  }
+  if (dev_fill) NFSP_HIP(hipMemcpyAsync(q[0], dev_fill, sizeof(float) * nq, hipMemcpyDeviceToDevice, st));
+  else NFSP_HIP(hipMemsetAsync(q[0], 0, sizeof(float) * nq, st));
+  NFSP_HIP(hipEventRecord(P.W->ev[0], st));
+  for (int j = 0; j < sweeps; ++j) {
+    if ((rc = mt_enqueue(st, P, j & 1)) != NFSP_OK) return rc;
+    if ((rc = table_rows_enqueue(st, M->ndec, NFSP_ROWS_TD_MEAN, tab, dev_fill, q[j & 1], R, q[(j + 1) & 1], chg)) != NFSP_OK)
+      return rc;
+  }
+  NFSP_HIP(hipMemcpyAsync(dev_q, q[sweeps & 1], sizeof(float) * nq, hipMemcpyDeviceToDevice, st));
+  std::vector<int32_t> hc(R);
+  NFSP_HIP(hipMemcpyAsync(hc.data(), chg, sizeof(int32_t) * R, hipMemcpyDeviceToHost, st));
+  if ((rc = mt_finish(st, P, info)) != NFSP_OK) return rc;
+  for (int r = 0; r < R; ++r)
+    if (changed) changed[r] = hc[r];
   return NFSP_OK;
 }
 
@@ -418,13 +529,15 @@ int mt_seg(MtTab& T, const void* p, int64_t n) {
 }
 
 // agent a's table of an engine at a step boundary (A: the agent's view, mem_view.h); TD: with the
-// agent's own target net, gamma and quirks
+// agent's own target net, gamma and quirks; TDQ: with these two, the Q rows being mt_sweeps'
 int mt_engine_tab(nfsp_engine* e, const AgentView& A, int kind, int a, int64_t* out, MtTab* T) {
   *T = MtTab{};
   T->seat = a;
   T->out = out;
   if (kind == NFSP_MEM_TD) {
     T->tw = e->w + (a * 3 + 2) * nfsp::nn::NP;       // NET_TARGET
+  }
+  if (kind == NFSP_MEM_TD || kind == NFSP_MEM_TDQ) {
     T->gamma = e->cfg.gamma;
     T->quirks = e->cfg.quirks;
   }
@@ -463,7 +576,8 @@ extern "C" int nfsp_memtab_last_ms(double* ms) {
 
 namespace {
 
-// the raw forms: one seat's table of the caller's segments (td: NFSP_MEM_TD's arguments)
+// the raw forms: one seat's table of the caller's segments (td: NFSP_MEM_TD's arguments, or
+// NFSP_MEM_TDQ's with the Q table as dev_target_w)
 int mt_raw(nfsp_ctx* ctx, int game, int kind, int seat, const nfsp_mem_segment* segs, int nsegs, const nfsp_td_args* td,
            int64_t* dev_out, nfsp_memtab_info* info) {
   NFSP_REQUIRE(ctx && dev_out && (segs || nsegs == 0), "null argument");
@@ -550,4 +664,50 @@ extern "C" int nfsp_engine_td_table(nfsp_engine* e, int64_t* dev_out, nfsp_memta
 extern "C" int nfsp_group_td_tables(nfsp_group* g, int64_t* dev_out, nfsp_memtab_info* info) {
   NFSP_REQUIRE(g && dev_out, "null argument");
   return mt_group(g, "nfsp_group_td_tables", NFSP_MEM_TD, dev_out, info);
+}
+
+extern "C" int nfsp_tdq_table(nfsp_ctx* ctx, int game, int seat, const nfsp_mem_segment* segs, int nsegs, const float* dev_q,
+                              double gamma, uint32_t quirks, int64_t* dev_out, nfsp_memtab_info* info) {
+  NFSP_REQUIRE(dev_q, "null argument");
+  NFSP_REQUIRE(((uintptr_t)dev_q & 3u) == 0, "TDQ table: the Q table must be 4-byte aligned");
+  const nfsp_td_args td{dev_q, gamma, quirks, 0};
+  return mt_raw(ctx, game, NFSP_MEM_TDQ, seat, segs, nsegs, &td, dev_out, info);
+}
+
+namespace {
+int tq_args(int sweeps, const float* dev_fill, float* dev_q, int64_t* dev_tab) {
+  NFSP_REQUIRE(dev_q, "null argument");
+  NFSP_REQUIRE(sweeps >= 1 && sweeps <= NFSP_TABQ_MAX_SWEEPS, "tabular Q: sweeps must be in [1, 64]");
+  NFSP_REQUIRE((((uintptr_t)dev_fill | (uintptr_t)dev_q) & 3u) == 0 && ((uintptr_t)dev_tab & 7u) == 0,
+               "tabular Q: misaligned table");
+  return NFSP_OK;
+}
+}  // namespace
+
+extern "C" int nfsp_engine_tabular_q(nfsp_engine* e, int sweeps, const float* dev_fill, float* dev_q, int64_t* dev_tab,
+                                     nfsp_memtab_info info[2], int32_t* changed) {
+  NFSP_REQUIRE(e, "null argument");
+  int rc = tq_args(sweeps, dev_fill, dev_q, dev_tab);
+  if (rc != NFSP_OK) return rc;
+  MemView v;
+  if ((rc = engine_view(e, "nfsp_engine_tabular_q", &v)) != NFSP_OK) return rc;
+  std::vector<MtTab> tabs(2);
+  for (int a = 0; a < 2; ++a)
+    if ((rc = mt_engine_tab(e, v.agent[a], NFSP_MEM_TDQ, a, nullptr, &tabs[a])) != NFSP_OK) return rc;
+  return mt_sweeps(e->ctx->stream, e->ctx->game, tabs, sweeps, dev_fill, dev_q, dev_tab, info, changed);
+}
+
+extern "C" int nfsp_group_tabular_q(nfsp_group* g, int sweeps, const float* dev_fill, float* dev_q, int64_t* dev_tab,
+                                    nfsp_memtab_info* info, int32_t* changed) {
+  NFSP_REQUIRE(g, "null argument");
+  int rc = tq_args(sweeps, dev_fill, dev_q, dev_tab);
+  if (rc != NFSP_OK) return rc;
+  GroupState G;
+  std::vector<MemView> v;
+  if ((rc = group_view(g, "nfsp_group_tabular_q", &G, &v)) != NFSP_OK) return rc;
+  std::vector<MtTab> tabs((size_t)2 * G.R);
+  for (int r = 0; r < G.R; ++r)
+    for (int a = 0; a < 2; ++a)
+      if ((rc = mt_engine_tab(G.eng[r], v[r].agent[a], NFSP_MEM_TDQ, a, nullptr, &tabs[2 * r + a])) != NFSP_OK) return rc;
+  return mt_sweeps(G.ctx->stream, G.ctx->game, tabs, sweeps, dev_fill, dev_q, dev_tab, info, changed);
 }

@@ -51,5 +51,9 @@ struct MtDev {
 int mt_host(int game, const MtHost** out);
 int mt_lookup(int game, const MtHost** host, MtDev* dev);
 
+// tabq.hip: k_table_rows for n tables on `st` (include/nfsp.h nfsp_table_rows; no synchronisation)
+int table_rows_enqueue(hipStream_t st, int ndec, int stat, const int64_t* dev_tab, const float* dev_fill,
+                       const float* dev_prev, int n, float* dev_rows, int32_t* dev_changed);
+
 }  // namespace eng
 }  // namespace nfsp

@@ -130,3 +130,87 @@ def memory_reports(ctx, engines, sl_tables, rl_tables, infos, tree=None) -> list
             "ar_mass_l1": num / den if den > 0 else float("nan"),
             "sl_info": infos[k][0], "rl_info": infos[k][1]})
     return out
+
+
+# -- tabular NFSP: the nets' roles played by tables of exactly the nets' data ----------
+def _group_of(engines):
+    """The ``EngineGroup`` whose replicas ``engines`` are, in order; None for anything else."""
+    g = getattr(engines[0], "_owner", None)
+    return g if g is not None and len(engines) == len(g.replicas) and all(a is b for a, b in zip(engines, g.replicas)) else None
+
+
+def _fill_dev(fill, R, tree, dev):
+    """``fill`` of a tabular call as a float32 device tensor ``[R, ndec, 3, 3]`` (one table serves
+    every engine), or None."""
+    import torch
+    if fill is None:
+        return None
+    t = fill if isinstance(fill, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(fill))
+    if t.dtype != torch.float32 or t.numel() not in (tree.ndec * 9, R * tree.ndec * 9):
+        raise ValueError(f"fill: float32 [{tree.ndec}, 3, 3], or one such table per engine")
+    t = t.to(dev).reshape(-1, tree.ndec, 3, 3)
+    return (t.expand(R, -1, -1, -1) if t.shape[0] != R else t).contiguous()
+
+
+def tabular_q(engines, sweeps=None, fill=None) -> list:
+    """``SelfPlayEngine.tabular_q`` of every engine: ``[(q, MemoryTable, info, changed)]``.  The
+    replicas of an ``EngineGroup``, all and in order, go through nfsp_group_tabular_q (three
+    launches per sweep for all of them); other engines through one nfsp_engine_tabular_q each."""
+    import ctypes as C
+    import torch
+    e0 = engines[0]
+    tree = ev.GameTree.of(e0.ctx.game)
+    sweeps = tree.nlev if sweeps is None else int(sweeps)
+    grp = _group_of(engines)
+    calls = [(grp, "nfsp_group_tabular_q", len(engines))] if grp is not None else [(e, "nfsp_engine_tabular_q", 1) for e in engines]
+    fill = _fill_dev(fill, len(engines), tree, e0.dev)
+    out, r0 = [], 0
+    for obj, fn, R in calls:
+        q = torch.empty((R, tree.ndec, 3, 3), dtype=torch.float32, device=e0.dev)
+        tab = torch.empty((R, tree.ndec, 3, 3, 3), dtype=torch.int64, device=e0.dev)
+        info = (native.MemtabInfo * (2 * R))()
+        changed = (C.c_int32 * R)()
+        native.check(getattr(obj.L, fn)(obj.h, sweeps, native.ptr(None if fill is None else fill[r0:r0 + R]), native.ptr(q),
+                                        native.ptr(tab), info, changed), fn)
+        raw = tab.cpu().numpy()
+        out += [(q[r], ev.MemoryTable(tree, native.MEM_TDQ, raw[r]), [info[2 * r].to_dict(), info[2 * r + 1].to_dict()],
+                 int(changed[r])) for r in range(R)]
+        r0 += R
+    return out
+
+
+def tabular_ar_rows(engines, stat="mass", fill=None, sl_tables=None):
+    """The rows ``SelfPlayEngine.install_tabular_ar`` installs, float32 device ``[R, ndec, 3, 3]``:
+    every engine's M_SL table (``sl_tables``: their ``MemoryTable``s when already counted) through
+    one ``table_rows`` launch.  ``fill`` None: each agent's AR net's own softmax head row
+    (one ``head_tables`` launch for all of them)."""
+    import torch
+    e0 = engines[0]
+    tree = ev.GameTree.of(e0.ctx.game)
+    if stat not in ("mass", "argmax"):
+        raise ValueError('stat must be "mass" or "argmax"')
+    R = len(engines)
+    if fill is None:
+        heads = ev.head_tables(e0.ctx, [e._wptr(a, NET_AR) for e in engines for a in (0, 1)], [native.ACT_SOFTMAX] * (2 * R), tree)
+        mine = torch.as_tensor(tree.seat.astype(np.int64), device=heads.device)          # row -> the agent that acts there
+        heads = heads.view(R, 2, tree.ndec, 3, 3)
+        fill = torch.where((mine == 0)[None, :, None, None], heads[:, 0], heads[:, 1]).contiguous()
+    else:
+        fill = _fill_dev(fill, R, tree, e0.dev)
+    if sl_tables is None:
+        grp = _group_of(engines)
+        sl_tables = [t for t, _ in grp.memory_tables(native.MEM_SL)] if grp is not None else \
+            [e.memory_table(native.MEM_SL)[0] for e in engines]
+    raw = np.stack([t.raw for t in sl_tables])
+    rows, _ = ev.table_rows(e0.ctx, native.ROWS_SL_MASS if stat == "mass" else native.ROWS_SL_ARGMAX, raw, fill, tree=tree)
+    return rows
+
+
+def tabular_q_report(e, q, td, info, eta=None, tree=None) -> list:
+    """``SelfPlayEngine.q_report`` with the Q table ``q`` of ``tabular_q`` in the BR heads' place and
+    its last sweep's table ``td`` as the data, per agent (``evaluation.q_report_from`` has the keys,
+    ``linear`` True: a table has no ReLU).  ``q_rmse_exact`` and ``greedy_mismatch_share`` are the
+    tabular learner's; at the sweeps' fixed point ``fit_rmse_td`` is 0 by construction."""
+    tree = tree or ev.GameTree.of(e.ctx.game)
+    beta, qx, reach = (t.cpu().numpy() for t in best_response_table(e, eta, True))
+    return [ev.q_report_from(tree, a, beta, qx, reach, q, td, True, float(e.cfg.gamma), info[a]) for a in (0, 1)]

@@ -385,6 +385,49 @@ class SelfPlayEngine(native.Handle):
         td, info = self.td_table()
         return diagnostics.q_reports(self.ctx, [self], [td], [info], eta)[0]
 
+    # -- tabular NFSP ----------------------------------------------------
+    def tabular_q(self, sweeps: int | None = None, fill=None):
+        """``(q, MemoryTable, [info of agent 0, of agent 1], changed)``: a Q table fitted to the live
+        M_RL records by ``sweeps`` Jacobi sweeps Q <- mean over the records of (set, action) of
+        r + gamma max_a Q(s2, a), each agent on its own rows with ``cfg.gamma`` and ``cfg.quirks``
+        (nfsp_engine_tabular_q; step boundaries only; include/nfsp.h has the arithmetic).  ``q`` is
+        a float32 device tensor ``[ndec, 3, 3]``, the table the last sweep's sums, ``changed`` the
+        entries the last sweep changed.  A (set, action) without a record is ``fill``'s value
+        (float32 ``[ndec, 3, 3]``, None: 0) through every sweep.  ``sweeps`` None: the tree's
+        ``nlev``, which without ``QUIRK_ALIAS_RL`` is the fixed point; under it a record's key is
+        its hand's LAST s and the result is just that many sweeps."""
+        return diagnostics.tabular_q([self], sweeps, fill)[0]
+
+    def tabular_q_report(self, sweeps: int | None = None, fill=None, eta: float | None = None) -> list:
+        """``q_report`` of the tabular Q (``diagnostics.tabular_q_report``): per agent what a learner
+        without function approximation makes of M_RL, against the exact action values."""
+        q, td, info, _ = self.tabular_q(sweeps, fill)
+        return diagnostics.tabular_q_report(self, q, td, info, eta)
+
+    def install_tabular_br(self, sweeps: int | None = None, fill=None):
+        """Tabular-BR self-play: both agents' BR role acts with ``tabular_q(sweeps, fill)``'s rows,
+        greedily and with the epsilon draw as the net would.  Installed at a step boundary, the
+        table acts in every slice of the step; call it before every step to refresh;
+        ``clear_act_tables`` undoes it.  The BR chains still train on M_RL.  Tables are session
+        settings, in neither the checkpoint nor the digest.  Returns what ``tabular_q`` returns."""
+        res = self.tabular_q(sweeps, fill)
+        for a in (0, 1):
+            self._set_act_table(a, NET_BR, res[0])
+        return res
+
+    def install_tabular_ar(self, stat: str = "mass", fill=None):
+        """Tabular-AR self-play: both agents' AR role acts with M_SL's own table, "mass" (the summed
+        action vectors, the exact minimiser of the AR net's cross-entropy) or "argmax" (the counts),
+        normalised per information set on the device (``evaluation.table_rows``).  A set M_SL never
+        saw, or without positive mass, takes ``fill``'s row (float32 ``[ndec, 3, 3]``); ``fill``
+        None: the AR net's own softmax row there.  Under the reference quirks the slot executes the
+        row's first maximum, under ``EXT_SAMPLE_AR`` it samples it.  Declared as
+        ``install_tabular_br``; the AR chains still train on M_SL.  Returns the installed rows."""
+        rows = diagnostics.tabular_ar_rows([self], stat, fill)[0]
+        for a in (0, 1):
+            self._set_act_table(a, NET_AR, rows)
+        return rows
+
     # -- checkpoints (checkpoint.py, DESIGN.md §10) ----------------------------------
     def save(self, path):
         """Save the engine at a step boundary (nfsp_engine_save_state); returns the bytes written."""
@@ -620,6 +663,30 @@ class EngineGroup(native.Handle):
         replicas) for all of them."""
         tds = self.td_tables()
         return diagnostics.q_reports(self.ctx, self.replicas, [t for t, _ in tds], [i for _, i in tds], eta)
+
+    def tabular_q_all(self, sweeps: int | None = None, fill=None) -> list:
+        """Every replica's ``SelfPlayEngine.tabular_q`` (nfsp_group_tabular_q): three launches per
+        sweep for all of them, each replica with its own gamma and quirks.  ``fill``: one table for
+        all, or ``[R, ndec, 3, 3]``."""
+        return diagnostics.tabular_q(self.replicas, sweeps, fill)
+
+    def install_tabular_br_all(self, sweeps: int | None = None, fill=None) -> list:
+        """``SelfPlayEngine.install_tabular_br`` for every replica, from one ``tabular_q_all``."""
+        res = self.tabular_q_all(sweeps, fill)
+        for r in range(self.R):
+            for a in (0, 1):
+                self.set_act_table(r, a, NET_BR, res[r][0])
+        return res
+
+    def install_tabular_ar_all(self, stat: str = "mass", fill=None):
+        """``SelfPlayEngine.install_tabular_ar`` for every replica: one M_SL table launch, one head
+        launch (without ``fill``) and one rows launch for all of them.  Returns the rows
+        ``[R, ndec, 3, 3]``."""
+        rows = diagnostics.tabular_ar_rows(self.replicas, stat, fill)
+        for r in range(self.R):
+            for a in (0, 1):
+                self.set_act_table(r, a, NET_AR, rows[r])
+        return rows
 
     # -- checkpoints (checkpoint.py, DESIGN.md §10) ----------------------------------
     def save(self, path):

@@ -315,7 +315,8 @@ class MemoryTable:
 
     ``native.MEM_TD`` (``td_table``): field 0 as ``MEM_RL``, field 1 the sum of the records' TD
     values v = r + gamma max Q_target(s2) and field 2 the sum of max Q_target(s2) over the records
-    that bootstrap, both in 2^-24 units.
+    that bootstrap, both in 2^-24 units.  ``native.MEM_TDQ`` (``tdq_table``): the same with a Q
+    table's row at s2 in Q_target's place.
 
     ``counts[ndec, 3, 3]`` is field 0 and ``n[ndec, 3]`` the records per information set."""
 
@@ -362,10 +363,12 @@ class MemoryTable:
         return self.raw[..., 2]
 
     def _td_mean(self, field):
-        if self.kind != native.MEM_TD:
+        if self.kind not in (native.MEM_TD, native.MEM_TDQ):
             raise AttributeError("mean_v / mean_bootstrap belong to TD tables")
         with np.errstate(invalid="ignore", divide="ignore"):
-            return np.where(self.counts > 0, self.raw[..., field] / (2.0**native.MEMTAB_FIX_SHIFT * self.counts), np.nan)
+            m = np.where(self.counts > 0, self.raw[..., field] / (2.0**native.MEMTAB_FIX_SHIFT * self.counts), np.nan)
+        # a TDQ table's means are the float32 values its rows hold (``table_rows``, ROWS_TD_MEAN)
+        return m.astype(np.float32).astype(np.float64) if self.kind == native.MEM_TDQ else m
 
     @property
     def mean_v(self) -> np.ndarray:
@@ -432,6 +435,63 @@ def td_table(ctx, seat: int, records, target_w, gamma: float, quirks: int, out=N
     native.check(ctx.L.nfsp_td_table(ctx.h, tree.game, int(seat), arr, nsegs, C.byref(td), native.P(out.data_ptr()),
                                      C.byref(info)), "nfsp_td_table")
     return out, info.to_dict()
+
+
+def tdq_table(ctx, seat: int, records, q, gamma: float, quirks: int, out=None, tree: GameTree | None = None):
+    """``nfsp_tdq_table``: ``td_table`` with a Q table in the target net's place -- one fitted-Q
+    sweep's sums.  ``q``: float32 ``[ndec, 3, 3]`` over ``tree``'s rows (array or device tensor); a
+    record bootstraps from the largest of the three entries at the information set of its s2, and
+    from 0 where s2 is none (a terminal observation).  Only ``QUIRK_TERMINAL_BOOTSTRAP`` of
+    ``quirks`` is read.  Returns ``(out, info)``; ``MemoryTable(tree, native.MEM_TDQ, out)`` reads
+    it, and ``table_rows(ctx, native.ROWS_TD_MEAN, out, fill)`` is the sweep's Q table."""
+    import torch
+    tree = tree or GameTree.of(ctx.game)
+    arr, nsegs = _segments(records, 32)
+    qd, _ = Policy._dev(q, torch.float32, tree.ndec * 9)
+    if out is None:
+        out = torch.zeros((tree.ndec, 3, 3, 3), dtype=torch.int64, device="cuda")
+    info = native.MemtabInfo()
+    native.check(ctx.L.nfsp_tdq_table(ctx.h, tree.game, int(seat), arr, nsegs, native.P(qd.data_ptr()), float(gamma),
+                                      int(quirks), native.P(out.data_ptr()), C.byref(info)), "nfsp_tdq_table")
+    return out, info.to_dict()
+
+
+def table_rows(ctx, stat: int, tabs, fill=None, prev=None, tree: GameTree | None = None):
+    """``nfsp_table_rows``: int64 tables ``[n, ndec, 3, 3, 3]`` (or one, ``[ndec, 3, 3, 3]``; array,
+    tensor or ``MemoryTable``) as the float32 rows a slot acts on, on the device.  ``stat``
+    ``native.ROWS_TD_MEAN``: field 1 / field 0 in chips per (set, action), of a TD or TDQ table;
+    ``ROWS_SL_MASS`` / ``ROWS_SL_ARGMAX``: an M_SL table's summed action vectors / argmax counts
+    normalised per set, before the raise-to-call remap.  Where the table has no data -- an entry
+    without records, an M_SL set without records or without positive mass -- the value is ``fill``'s
+    (float32, the tables' shape with 3 in place of the fields), 0 without ``fill``.  Returns
+    ``(rows, changed)``: a float32 device tensor of ``fill``'s shape and per table the entries whose
+    bits differ from ``prev``'s (``None`` without ``prev``)."""
+    import torch
+    tree = tree or GameTree.of(ctx.game)
+    raw = tabs.raw if isinstance(tabs, MemoryTable) else tabs
+    t = raw if isinstance(raw, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(raw))
+    if t.dtype != torch.int64 or t.numel() % (tree.ndec * 27):
+        raise ValueError(f"table_rows: int64 tables [n, {tree.ndec}, 3, 3, 3]")
+    one = t.dim() == 4
+    t = t.cuda().contiguous()
+    n = t.numel() // (tree.ndec * 27)
+
+    def rows_like(x, what):
+        if x is None:
+            return None
+        x = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(x))
+        if x.dtype != torch.float32 or x.numel() != n * tree.ndec * 9:
+            raise ValueError(f"table_rows: {what} must be float32 [{n}, {tree.ndec}, 3, 3]")
+        return x.cuda().contiguous()
+    fill, prev = rows_like(fill, "fill"), rows_like(prev, "prev")
+    out = torch.empty((tree.ndec, 3, 3) if one else (n, tree.ndec, 3, 3), dtype=torch.float32, device="cuda")
+    changed = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
+    native.check(ctx.L.nfsp_table_rows(ctx.h, tree.game, int(stat), native.ptr(t), native.ptr(fill), native.ptr(prev), n,
+                                       native.ptr(out), native.ptr(changed)), "nfsp_table_rows")
+    if prev is None:
+        return out, None
+    c = changed[:n].cpu().tolist()
+    return out, c[0] if one else c
 
 
 def head_tables(ctx, nets, acts, tree: GameTree | None = None):

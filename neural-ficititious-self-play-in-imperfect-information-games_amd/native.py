@@ -230,6 +230,11 @@ SIGNATURES = {
     "nfsp_engine_set_act_table": (I32, [P, I32, I32, P]),
     "nfsp_engine_get_act_table": (I32, [P, I32, I32, PP, C.POINTER(I64)]),
     "nfsp_group_set_act_table": (I32, [P, I32, I32, I32, P]),
+    # tabular NFSP: fitted-Q sweeps over M_RL, and the memory tables as the rows a slot acts on
+    "nfsp_tdq_table": (I32, [P, I32, I32, C.POINTER(MemSegment), I32, P, F64, U32, P, C.POINTER(MemtabInfo)]),
+    "nfsp_table_rows": (I32, [P, I32, I32, P, P, P, I32, P, P]),
+    "nfsp_engine_tabular_q": (I32, [P, I32, P, P, P, C.POINTER(MemtabInfo), C.POINTER(C.c_int32)]),
+    "nfsp_group_tabular_q": (I32, [P, I32, P, P, P, C.POINTER(MemtabInfo), C.POINTER(C.c_int32)]),
 }
 # int (*nfsp_exchange_fn)(void* user, float* dev_sum, int64_t n)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, P, P, I64)
@@ -245,7 +250,11 @@ XFP_WEIGHT_UNIFORM, XFP_WEIGHT_LINEAR = 0, 1
 XFP_LAUNCH_ITERS = 1024
 XFP_MAX_RUNS = 1024
 # the memories as tables (NFSP_MEM_*, NFSP_MEMTAB_*)
-MEM_SL, MEM_RL, MEM_TD = 0, 1, 2
+MEM_SL, MEM_RL, MEM_TD, MEM_TDQ = 0, 1, 2, 3
+# what nfsp_table_rows makes of a table (NFSP_ROWS_*), and the most sweeps and tables of a call
+ROWS_SL_MASS, ROWS_SL_ARGMAX, ROWS_TD_MEAN = 0, 1, 2
+TABQ_MAX_SWEEPS = 64
+TABLE_ROWS_MAX = 65535
 MEMTAB_FIX_SHIFT = 24
 MEMTAB_MAX_SEGMENTS = 8
 

@@ -18,6 +18,10 @@ not from HBM -- as the state digest's beside them (nfsp_engine_state_digest_time
      With --td (profiles/qreport/): also the TD table (nfsp_engine_td_table: a forward of the target
      net per record inside k_memtab) beside the M_RL table on the same state, and one q_report();
      part b is skipped.  --quirks picks the reference's quirks or NFSP_TEXTBOOK_MSE_DECAY.
+     With --tdq (profiles/tabular/): as --td, and beside both the TD pass whose bootstrap reads a
+     table (nfsp_engine_tabular_q): one sweep -- k_memtab<TDQ>, k_memtab_sum and k_table_rows under
+     the same events -- and the tree's nlev sweeps; then one install_tabular_br() and one
+     install_tabular_ar() by the wall clock, against one step.
   c  the c3_r16 group (16 replicas x 65,536 lanes, each M_RL 200k + M_SL 2M): the group form
      against 16 engine-form calls."""
 import argparse
@@ -73,7 +77,7 @@ def part_a(pkg, args, torch):
     for kind, name, rec, n in ((nat.MEM_SL, "sl", 16, sum(st["sl_size"])), (nat.MEM_RL, "rl", 32, sum(st["rl_size"]))):
         out[name] = rate(timed(pkg, lambda: eng.memory_table(kind), args.repeats), rec * n)
         # M_RL: the kernel reads the first 16 bytes of each 32-byte record; the bytes are the records'
-    if args.td:
+    if args.td or args.tdq:
         out["td"] = rate(timed(pkg, lambda: eng.td_table(), args.repeats), 32 * sum(st["rl_size"]))
         out["td_over_rl"] = out["td"]["ms_best"] / out["rl"]["ms_best"]
         torch.cuda.synchronize()
@@ -82,6 +86,26 @@ def part_a(pkg, args, torch):
         out["q_report_ms"] = (time.perf_counter() - t) * 1e3
         out["q_report_over_step"] = out["q_report_ms"] / step_ms
         out["q_report"] = [{k: v for k, v in r.items() if k != "info"} for r in rep]
+        if args.tdq:
+            nlev = ev.GameTree.of(eng.ctx.game).nlev
+            out["tdq_sweep"] = rate(timed(pkg, lambda: eng.tabular_q(sweeps=1), args.repeats), 32 * sum(st["rl_size"]))
+            out["tdq_over_td"] = out["tdq_sweep"]["ms_best"] / out["td"]["ms_best"]
+            out["tdq_over_rl"] = out["tdq_sweep"]["ms_best"] / out["rl"]["ms_best"]
+            out["tdq_nlev"] = dict(sweeps=nlev, **timed(pkg, lambda: eng.tabular_q(), args.repeats))
+            for name, call in (("install_tabular_br", eng.install_tabular_br), ("install_tabular_ar", eng.install_tabular_ar)):
+                call()
+                wall = []
+                for _ in range(args.repeats):
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    call()
+                    torch.cuda.synchronize()
+                    wall.append((time.perf_counter() - t) * 1e3)
+                out[name + "_ms"] = min(wall)
+                out[name + "_over_step"] = min(wall) / step_ms
+            rep = eng.tabular_q_report()
+            out["tabular_q_report"] = [{k: v for k, v in r.items() if k != "info"} for r in rep]
+            eng.clear_act_tables()
         out["exploitability"] = eng.exploitability()["exploitability"]
         out["br_gap"] = [g["gap"] for g in eng.br_gap()]
         eng.close()
@@ -177,6 +201,8 @@ def main():
     ap.add_argument("--replicas", type=int, default=16)
     ap.add_argument("--group-steps", type=int, default=3)
     ap.add_argument("--td", action="store_true", help="part a: the TD table beside the M_RL table, and one q_report()")
+    ap.add_argument("--tdq", action="store_true",
+                    help="part a: --td, and the table-bootstrapped TD pass, its sweeps and the two installs beside it")
     ap.add_argument("--quirks", default="reference", choices=["reference", "textbook"],
                     help="part a: NFSP_QUIRKS_REFERENCE or NFSP_TEXTBOOK_MSE_DECAY")
     args = ap.parse_args()
