@@ -915,6 +915,70 @@ int nfsp_engine_tabular_q(nfsp_engine* e, int sweeps, const float* dev_fill /*[n
 int nfsp_group_tabular_q(nfsp_group* g, int sweeps, const float* dev_fill, float* dev_q, int64_t* dev_tab,
                          nfsp_memtab_info* info /*[R][2]*/, int32_t* changed /*[R]*/);
 
+/* ---- nets fitted to tables (csrc/fit_tables.hip k_fit_tables) ----
+ * The other direction of everything above: a [ndec][3][3] table over nfsp_tree_export's rows put
+ * into a packed 30-64-3 net, by deterministic, weighted, full-batch gradient descent with momentum.
+ * The reference only ever fits sampled minibatches (agent/agent.py:209-264; nfsp_mlp_fit above is
+ * that: one net, <= 64 rows, no weights, no mask).  Diagnostics: the approximation
+ * floors of the AR and Q nets, and warm starts of self-play from a solved table.
+ *
+ * Rows.  A job's rows are the (d, r) with legal[d] >> 1 == seat, ascending in (d, r): 195 per seat
+ * for Leduc, 12 for Kuhn.  A row's input is obs[d][r] expanded to 0/1, its target
+ * t = (float)dev_target[d][r][.], its weight what = (float)(w / W) with w = dev_weight[d][r] (1
+ * without) and W the sum of the seat's w in row order, both in double; its mask m_a = dev_mask's
+ * entry != 0, or without a mask 1 for a legal action (the raise 0 where legal[d] bit 0 is clear).
+ *
+ * One step, all f32 with fp contract off, every gradient from the weights before the step:
+ *   forward   z1_j = (sum over the inputs i ascending of x_i W1[i][j]) + b1_j, h = relu(z1),
+ *             z_a = (sum over j ascending of h_j W2[j][a]) + b2_a -- nfsp_mlp_fit's order
+ *   CE        c_a = z_a - max(max(z_0, z_1), z_2), e_a = expf(c_a), s = (e_0 + e_1) + e_2,
+ *             p_a = e_a / s, T = (t_0 + t_1) + t_2;  dz_a = what (p_a T - t_a);
+ *             row loss = what * -((t_0 l_0 + t_1 l_1) + t_2 l_2) with l_a = c_a - logf(s).
+ *             No clipping: this is NOT Keras' clipped cross-entropy that nfsp_mlp_fit and the
+ *             chains reproduce (p clipped to [1e-7, 1 - 1e-7]); l_a is finite for every finite z.
+ *   MSE/Huber y_a = z_a (linear head) or relu(z_a), e = y_a - t_a, g = e (MSE) or e clamped to
+ *             [-1, 1] (Huber, delta 1);  dz_a = (what m_a) g, and 0 where the ReLU head has
+ *             z_a <= 0;  row loss = what ((m_0 l_0 + m_1 l_1) + m_2 l_2), l = e e / 2, or |e| - 1/2
+ *             where Huber clamps.
+ *   backward  dW2[j][a] = sum over the rows ascending of h_j dz_a, db2_a = sum of dz_a;
+ *             dz1_j = z1_j > 0 ? (dz_0 W2[j][0] + dz_1 W2[j][1]) + dz_2 W2[j][2] : 0;
+ *             dW1[i][j] = sum over the rows ascending of x_i dz1_j, db1_j = sum of dz1_j
+ *   update    v <- momentum v + g,  w <- w - lr v
+ * Every sum starts at +0.  The kernel skips the inputs and rows with x_i = 0, which for finite
+ * values gives the bits of the full sums.  A row of weight 0 and a masked entry contribute +-0.
+ * Determinism: one thread owns one parameter and sums its rows in the order above, so a job's
+ * result is a function of the job alone -- not of the grid, the job's place in the list or their
+ * number; no atomics.  `steps` split over calls with dev_v carried gives the bits of one call.
+ * host_loss[k][0] / [1]: the sum of the row losses (f32 terms, summed in double in row order) at
+ * the weights before step 1 / at the final weights (one more forward).
+ *
+ * nfsp_fit_jobs_check is the validation that needs no device: n and steps >= 0, each job's seat,
+ * head and loss, their pairing (CE with the softmax head only, MSE and Huber with the ReLU or
+ * linear head), no mask with CE, lr finite and >= 0, 0 <= momentum < 1, dev_w and dev_target set.
+ * nfsp_fit_tables repeats it, requires game to be the ctx's, copies every job's net, momentum
+ * state, table and weights to the host once and checks, before anything is launched: every value
+ * finite (a target as float too), the seat's weights >= 0 with a positive sum, CE targets >= 0, no
+ * two jobs sharing dev_w / dev_v memory.  A violation is NFSP_EINVAL, nfsp_last_error names the
+ * job and the row, and nothing was changed.  The hidden width is 64.  One workgroup per job, all
+ * `steps` inside the launch, the net, v, the rows and the workspace in LDS; at most
+ * NFSP_FIT_MAX_JOBS jobs per launch, the host loops beyond.  Synchronises the ctx stream. */
+#define NFSP_FIT_CE 0      /* softmax head only */
+#define NFSP_FIT_MSE 1     /* ReLU or linear head */
+#define NFSP_FIT_HUBER 2   /* ReLU or linear head, delta 1 */
+#define NFSP_FIT_MAX_JOBS 64
+typedef struct {
+  float* dev_w;              /* packed net, NP f32, in and out */
+  float* dev_v;              /* momentum state, NP f32, in and out; NULL: zero at the call's start, dropped at its end */
+  const double* dev_target;  /* [ndec][3][3], rows of nfsp_tree_export */
+  const double* dev_weight;  /* [ndec][3] >= 0; NULL: 1 at every information set of the seat */
+  const uint8_t* dev_mask;   /* [ndec][3][3], 1 = this entry has a target; NULL: the legal actions.  Must be NULL with NFSP_FIT_CE */
+  int32_t seat, head, loss;  /* seat 0/1: the rows where that seat acts; head NFSP_ACT_*; loss NFSP_FIT_* */
+  float lr, momentum;        /* lr finite >= 0, 0 <= momentum < 1 */
+} nfsp_fit_job;
+int nfsp_fit_jobs_check(const nfsp_fit_job* jobs, int n, int64_t steps);   /* host only, no device */
+int nfsp_fit_tables(nfsp_ctx* ctx, int game, const nfsp_fit_job* jobs, int n, int64_t steps,
+                    double* host_loss /*[n][2] or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif

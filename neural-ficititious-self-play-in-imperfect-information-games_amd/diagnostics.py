@@ -214,3 +214,185 @@ def tabular_q_report(e, q, td, info, eta=None, tree=None) -> list:
     tree = tree or ev.GameTree.of(e.ctx.game)
     beta, qx, reach = (t.cpu().numpy() for t in best_response_table(e, eta, True))
     return [ev.q_report_from(tree, a, beta, qx, reach, q, td, True, float(e.cfg.gamma), info[a]) for a in (0, 1)]
+
+
+# -- nets fitted to tables: distillation and warm starts -------------------------------
+def _as_policy(ctx, table, tree):
+    """``table`` (a ``Policy`` or an array ``[ndec, 3, 3]``) as (``Policy``, its executed host table)."""
+    if isinstance(table, ev.Policy):
+        return table, ev.policy_table(ctx, table, tree).cpu().numpy()
+    t = tree.remap(table)
+    return ev.Policy.table(t), t
+
+
+def _fit_weights(ctx, pol, weights, tree):
+    """``weights`` of a distillation as float64 ``[ndec, 3]``, None for "uniform"."""
+    if isinstance(weights, str):
+        if weights == "uniform":
+            return None
+        if weights == "visit":
+            return ev.visit_weights(ctx, pol, pol, tree)
+        raise ValueError('weights must be "visit", "uniform" or an array [ndec, 3]')
+    return np.asarray(weights, np.float64).reshape(tree.ndec, 3)
+
+
+def _init_pairs(init, n):
+    """``init`` of a distillation as n pairs of packed nets: a seed (seat 0's net, then seat 1's,
+    Glorot, from one stream), a pair of nets, or a list of either."""
+    items = list(init) if isinstance(init, (list, tuple)) and not (len(init) == 2 and np.ndim(init[0]) == 1) else [init]
+    if len(items) == 1:
+        items = items * n
+    if len(items) != n:
+        raise ValueError(f"{len(items)} inits for {n} variants")
+    out = []
+    for it in items:
+        if np.ndim(it) == 0:
+            rng = np.random.RandomState(int(it))
+            out.append((ev.glorot_net(rng), ev.glorot_net(rng)))
+        else:
+            out.append((np.asarray(it[0], np.float32), np.asarray(it[1], np.float32)))
+    return out
+
+
+def _variants(lr, momentum, init):
+    ls = list(lr) if isinstance(lr, (list, tuple)) else [lr]
+    ms = list(momentum) if isinstance(momentum, (list, tuple)) else [momentum]
+    n = max(len(ls), len(ms), len(init) if isinstance(init, list) else 1)
+    ls, ms = (x * n if len(x) == 1 else x for x in (ls, ms))
+    if len(ls) != n or len(ms) != n:
+        raise ValueError("lr, momentum and init lists must have one length")
+    many = any(isinstance(x, (list, tuple)) for x in (lr, momentum)) or isinstance(init, list)
+    return ls, ms, _init_pairs(init, n), many
+
+
+def q_targets(ctx, policy, tree=None):
+    """What a Q net is to hold against ``policy`` at both seats: ``(qx, reach, (beta, q, reach))``
+    with qx = q / reach of ``best_response(values=True)`` (0 where the information set is not
+    reached: its weight ``reach`` is 0 there)."""
+    tree = tree or ev.GameTree.of(ctx.game)
+    pol, _ = _as_policy(ctx, policy, tree)
+    beta, q, reach = (t.cpu().numpy() for t in ev.best_response(ctx, pol, pol, values=True, tree=tree))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        qx = np.where(reach[:, :, None] > 0, q / reach[:, :, None], 0.0)
+    return qx, reach, (beta, q, reach)
+
+
+def distill_policy(ctx, table, weights="visit", steps: int = 2000, lr=0.5, momentum=0.9, init=0, tree=None):
+    """The approximation floor of the AR net: two 30-64-3 softmax nets, one per seat, fitted to
+    ``table`` (a ``Policy`` or ``[ndec, 3, 3]``; as executed) by ``evaluation.fit_tables`` with
+    cross-entropy.  ``weights``: "visit" (``evaluation.visit_weights`` of the table against itself:
+    fitted where it is played), "uniform", or ``[ndec, 3]``.  ``init``: a seed for Glorot nets, or
+    the pair of packed nets to start from.  Returns ``{"nets": [w0, w1] (float32 device tensors),
+    "losses": [2, 2] (seat; before, after), "entropy": [2] (the targets' own weighted entropy: the
+    loss's floor), "scores": {"table", "softmax", "argmax"}}``, the scores being the exact
+    exploitability of the table and of the nets in both modes, from one ``evaluate_batch``.
+
+    ``lr``, ``momentum`` and ``init`` may be lists of one length (``init`` a list of seeds or
+    pairs): that many variants in ONE ``fit_tables`` call and one ``evaluate_batch``; the result is
+    then the list of the variants' dicts."""
+    tree = tree or ev.GameTree.of(ctx.game)
+    pol, tab = _as_policy(ctx, table, tree)
+    wt = _fit_weights(ctx, pol, weights, tree)
+    ls, ms, inits, many = _variants(lr, momentum, init)
+    jobs = [ev.FitJob(inits[k][s], tab, s, native.ACT_SOFTMAX, "ce", ls[k], ms[k], wt)
+            for k in range(len(ls)) for s in (0, 1)]
+    losses = ev.fit_tables(ctx, jobs, steps, tree)
+    pairs = [(pol, pol)]
+    for k in range(len(ls)):
+        for mode in (0, 1):
+            pairs.append((ev.Policy.ar(jobs[2 * k].w, mode), ev.Policy.ar(jobs[2 * k + 1].w, mode)))
+    res = ev.evaluate_batch(ctx, pairs)
+    w = np.ones((tree.ndec, 3)) if wt is None else wt
+    ent = []
+    for s in (0, 1):
+        rows = tree.seat == s
+        ws = w[rows] / w[rows].sum()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ent.append(float((ws * -np.where(tab[rows] > 0, tab[rows] * np.log(tab[rows]), 0.0).sum(axis=2)).sum()))
+    out = [{"nets": [jobs[2 * k].w, jobs[2 * k + 1].w], "losses": losses[2 * k:2 * k + 2], "entropy": ent,
+            "scores": {"table": res[0]["exploitability"], "softmax": res[1 + 2 * k]["exploitability"],
+                       "argmax": res[2 + 2 * k]["exploitability"]}} for k in range(len(ls))]
+    return out if many else out[0]
+
+
+def distill_q(ctx, policy, linear: bool = False, loss: str = "mse", steps: int = 2000, lr=0.05, momentum=0.9,
+              init=0, tree=None):
+    """The approximation floor of the Q net: two 30-64-3 nets, one per seat, with the ReLU head
+    (the reference's) or the ``linear`` one, fitted to the exact action values against ``policy``
+    -- qx = q / reach of ``best_response(values=True)`` -- with weight ``reach`` and the legal
+    actions as the mask, by "mse" or "huber".  Returns ``{"nets", "losses" [2, 2], "reports":
+    [per seat ``evaluation.q_report_from``'s q_rmse_exact, greedy_mismatch_share and
+    relu_blind_share], "br_gap": [per seat br_exact, br_learned, gap of the fitted net played
+    greedily against ``policy``]}``; lists of ``lr`` / ``momentum`` / ``init`` as ``distill_policy``."""
+    tree = tree or ev.GameTree.of(ctx.game)
+    pol, _ = _as_policy(ctx, policy, tree)
+    qx, reach, (beta, q, _) = q_targets(ctx, pol, tree)
+    head = native.ACT_LINEAR if linear else native.ACT_RELU
+    ls, ms, inits, many = _variants(lr, momentum, init)
+    jobs = [ev.FitJob(inits[k][s], qx, s, head, loss, ls[k], ms[k], reach) for k in range(len(ls)) for s in (0, 1)]
+    losses = ev.fit_tables(ctx, jobs, steps, tree)
+    heads = ev.head_tables(ctx, [j.w for j in jobs], [head] * len(jobs), tree).cpu().numpy()
+    pairs = []
+    for k in range(len(ls)):
+        pairs += [(ev.Policy.br(jobs[2 * k].w, linear), pol), (pol, ev.Policy.br(jobs[2 * k + 1].w, linear))]
+    res = ev.evaluate_batch(ctx, pairs)
+    none = np.zeros((tree.ndec, 3, 3, 3), np.int64)
+    out = []
+    for k in range(len(ls)):
+        rep = []
+        for s in (0, 1):
+            r = ev.q_report_from(tree, s, beta, q, reach, heads[2 * k + s], none, linear)
+            rep.append({key: r[key] for key in ("q_rmse_exact", "greedy_mismatch_share", "relu_blind_share")})
+        r0, r1 = res[2 * k], res[2 * k + 1]
+        out.append({"nets": [jobs[2 * k].w, jobs[2 * k + 1].w], "losses": losses[2 * k:2 * k + 2], "reports": rep,
+                    "br_gap": [{"br_exact": r0["br0"], "br_learned": r0["value0"], "gap": r0["br0"] - r0["value0"]},
+                               {"br_exact": r1["br1"], "br_learned": -r1["value0"], "gap": r1["br1"] + r1["value0"]}]})
+    return out if many else out[0]
+
+
+def warm_start(engines, policy, q="exact", steps: int = 2000, lr=(0.5, 0.05), momentum=0.9, weights="visit") -> list:
+    """``SelfPlayEngine.warm_start`` of every engine (one ctx, one game), all of their jobs -- up to
+    four per engine -- in ONE ``fit_tables`` call: the AR nets fitted in place to ``policy`` as
+    ``distill_policy`` fits them, from the nets as they are; with ``q`` the BR nets to the action
+    values (``q_targets`` against ``policy`` for "exact", or an array ``[ndec, 3, 3]``) with weight
+    ``reach``, the head and loss the engine's quirks train, then copied to the target nets.
+    ``lr``: one rate or (AR, BR)."""
+    import torch
+    e0 = engines[0]
+    ctx = e0.ctx
+    tree = ev.GameTree.of(ctx.game)
+    for e in engines:
+        e.state_digest()                       # refused off a step boundary
+    pol, tab = _as_policy(ctx, policy, tree)
+    wt = _fit_weights(ctx, pol, weights, tree)
+    lr_ar, lr_br = (lr if isinstance(lr, (list, tuple)) else (lr, lr))
+    before = ev.evaluate_batch(ctx, [(e.policy(0, NET_AR), e.policy(1, NET_AR)) for e in engines])
+    if q is not None:
+        qx, reach, _ = q_targets(ctx, pol, tree)
+        if not isinstance(q, str):
+            qx = np.asarray(q, np.float64).reshape(tree.ndec, 3, 3)
+        elif q != "exact":
+            raise ValueError('q must be "exact", None or an array [ndec, 3, 3]')
+        qd, rd = torch.as_tensor(qx, device=e0.dev), torch.as_tensor(reach, device=e0.dev)
+    td = torch.as_tensor(tab, device=e0.dev)
+    wd = None if wt is None else torch.as_tensor(wt, device=e0.dev)
+    jobs = []
+    for e in engines:
+        for s in (0, 1):
+            jobs.append(ev.FitJob(e._wptr(s, NET_AR), td, s, native.ACT_SOFTMAX, "ce", lr_ar, momentum, wd))
+        if q is not None:
+            head = native.ACT_LINEAR if e.cfg.quirks & native.EXT_LINEAR_Q else native.ACT_RELU
+            loss = "mse" if e.cfg.quirks & native.EXT_MSE_Q else "huber"
+            for s in (0, 1):
+                jobs.append(ev.FitJob(e._wptr(s, NET_BR), qd, s, head, loss, lr_br, momentum, rd))
+    losses = ev.fit_tables(ctx, jobs, steps, tree)
+    if q is not None:
+        for e in engines:
+            for s in (0, 1):
+                e.weights_tensor(s, native.NET_TARGET).copy_(e.weights_tensor(s, NET_BR))
+        torch.cuda.synchronize(e0.dev)
+    after = ev.evaluate_batch(ctx, [(e.policy(0, NET_AR), e.policy(1, NET_AR)) for e in engines])
+    per = 2 if q is None else 4
+    return [{"losses_ar": losses[per * k:per * k + 2], "losses_br": None if q is None else losses[per * k + 2:per * k + 4],
+             "exploitability_before": before[k]["exploitability"], "exploitability_after": after[k]["exploitability"]}
+            for k in range(len(engines))]

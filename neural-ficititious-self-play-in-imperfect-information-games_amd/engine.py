@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import checkpoint, diagnostics, evaluation, native
-from .evaluation import exploitability, exploitability_batch  # noqa: F401  (engine.exploitability is public API)
+from .evaluation import exploitability, exploitability_batch, glorot_net  # noqa: F401  (engine.exploitability is public API)
 from .native import NET_AR, NET_BR, NET_TARGET, NP
 
 PRESETS = {
@@ -28,15 +28,6 @@ PRESETS = {
     "c2": dict(n_lanes=65_536, rl_capacity=40_000, sl_capacity=40_000),
     "c3": dict(n_lanes=1_048_576, rl_capacity=200_000, sl_capacity=2_000_000),
 }
-
-
-def glorot_net(rng: np.random.RandomState, hidden: int = 64) -> np.ndarray:
-    """Keras defaults: glorot_uniform kernels, zero biases; packed like nfsp.h."""
-    def g(fi, fo):
-        lim = np.sqrt(6.0 / (fi + fo))
-        return rng.uniform(-lim, lim, size=(fi, fo)).astype(np.float32)
-    return np.concatenate([g(30, hidden).ravel(), np.zeros(hidden, np.float32),
-                           g(hidden, 3).ravel(), np.zeros(3, np.float32)])
 
 
 def make_cfg(L, **cfg) -> native.EngineCfg:
@@ -428,6 +419,23 @@ class SelfPlayEngine(native.Handle):
             self._set_act_table(a, NET_AR, rows)
         return rows
 
+    # -- nets fitted to tables ---------------------------------------------
+    def warm_start(self, policy, q="exact", steps: int = 2000, lr=(0.5, 0.05), momentum: float = 0.9,
+                   weights="visit") -> dict:
+        """Self-play started from a solved table, at a step boundary only: the two AR nets are
+        fitted to ``policy`` (an ``evaluation.Policy`` or ``[ndec, 3, 3]``, e.g. a ``CfrSolver``
+        average) with cross-entropy under ``weights`` ("visit", "uniform" or ``[ndec, 3]``), from
+        the nets as they are; with ``q`` "exact" the BR nets to the exact action values against
+        ``policy`` (q / reach of ``evaluation.best_response``, weight reach, the legal actions), or
+        to the array ``q``; ``q`` None leaves the BR and target nets alone.  The BR head and loss
+        are the ones ``cfg.quirks`` trains: linear with ``EXT_LINEAR_Q``, else ReLU; MSE with
+        ``EXT_MSE_Q``, else Huber.  The target nets become copies of the BR nets.  ``lr``: one rate,
+        or (AR, BR).  All jobs run in one ``evaluation.fit_tables`` call (deterministic).  Memories,
+        counters and schedules are untouched; the nets are in the state blob, so save and resume
+        need nothing new.  Returns ``{"losses_ar", "losses_br" ([seat][before, after]),
+        "exploitability_before", "exploitability_after"}``."""
+        return diagnostics.warm_start([self], policy, q, steps, lr, momentum, weights)[0]
+
     # -- checkpoints (checkpoint.py, DESIGN.md §10) ----------------------------------
     def save(self, path):
         """Save the engine at a step boundary (nfsp_engine_save_state); returns the bytes written."""
@@ -687,6 +695,13 @@ class EngineGroup(native.Handle):
             for a in (0, 1):
                 self.set_act_table(r, a, NET_AR, rows[r])
         return rows
+
+    def warm_start_all(self, policy, q="exact", steps: int = 2000, lr=(0.5, 0.05), momentum: float = 0.9,
+                       weights="visit") -> list:
+        """``SelfPlayEngine.warm_start`` for every replica, all of their jobs (4R with ``q``) in
+        one ``evaluation.fit_tables`` call of 64-job launches; a replica's nets are the bits a
+        standalone engine's warm start gives.  Returns the replicas' dicts."""
+        return diagnostics.warm_start(self.replicas, policy, q, steps, lr, momentum, weights)
 
     # -- checkpoints (checkpoint.py, DESIGN.md §10) ----------------------------------
     def save(self, path):

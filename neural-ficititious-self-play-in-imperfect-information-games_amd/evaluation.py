@@ -34,6 +34,10 @@ fitted to per (information set, action) over M_RL where it lies, and ``q_report_
 BR net's error against ``best_response``'s exact action values in two: what the data say against
 the truth, and what the net makes of its data.
 
+``fit_tables`` (``nfsp_fit_tables``, csrc/fit_tables.hip) goes the other way: ``FitJob``s put a
+table into a packed net by weighted full-batch gradient descent on the device, and
+``visit_weights`` gives the exact visit distribution to weight them with.
+
 Nothing here knows an engine: what needs both an engine and this module is ``diagnostics``.
 """
 from __future__ import annotations
@@ -526,6 +530,96 @@ def act_rows(table):
     if not bool(torch.isfinite(t).all()):
         raise ValueError("act_rows: the table has values that are not finite (as float32)")
     return t
+
+
+def glorot_net(rng: np.random.RandomState, hidden: int = 64) -> np.ndarray:
+    """Keras defaults: glorot_uniform kernels, zero biases; packed like nfsp.h."""
+    def g(fi, fo):
+        lim = np.sqrt(6.0 / (fi + fo))
+        return rng.uniform(-lim, lim, size=(fi, fo)).astype(np.float32)
+    return np.concatenate([g(30, hidden).ravel(), np.zeros(hidden, np.float32),
+                           g(hidden, 3).ravel(), np.zeros(3, np.float32)])
+
+
+FIT_LOSSES = {"ce": native.FIT_CE, "mse": native.FIT_MSE, "huber": native.FIT_HUBER}
+
+
+class FitJob:
+    """One job of ``fit_tables`` (``nfsp_fit_job``): the packed net ``w`` fitted to ``seat``'s rows
+    of ``target`` (float64 ``[ndec, 3, 3]`` over ``GameTree``'s rows) by full-batch gradient descent
+    with momentum.  ``head``: ``native.ACT_SOFTMAX`` with ``loss`` "ce", ``ACT_RELU`` or
+    ``ACT_LINEAR`` with "mse" or "huber".  ``weight``: float64 ``[ndec, 3]`` >= 0 per information
+    set (None: 1); ``mask``: ``[ndec, 3, 3]``, nonzero where an entry has a target (None: the legal
+    actions; not with "ce"); ``v``: the momentum state, float32 like ``w`` (None: zero at the
+    call's start, dropped at its end).  Every input is an array, a device tensor or a device
+    address, in the style of ``Policy``; ``w`` and ``v`` are updated in place where they are device
+    tensors or addresses, and ``self.w`` / ``self.v`` are the device tensors otherwise."""
+
+    def __init__(self, w, target, seat: int, head: int, loss, lr: float, momentum: float = 0.0, weight=None,
+                 mask=None, v=None):
+        import torch
+
+        def dev(x, dtype, numel=None):
+            if x is None:
+                return None, None
+            t, p = Policy._dev(x, dtype, numel)
+            return t, int(t.data_ptr() if p is None else p)
+        self.w, self._w = dev(w, torch.float32, native.NP)
+        self.v, self._v = dev(v, torch.float32, native.NP)
+        self.target, self._t = dev(target, torch.float64)
+        self.weight, self._wt = dev(weight, torch.float64)
+        self.mask, self._m = dev(mask, torch.uint8)
+        self.seat, self.head = int(seat), int(head)
+        self.loss = int(FIT_LOSSES.get(loss, loss))
+        self.lr, self.momentum = float(lr), float(momentum)
+
+    def spec(self) -> native.FitJob:
+        return native.FitJob(self._w, self._v, self._t, self._wt, self._m, self.seat, self.head, self.loss,
+                             self.lr, self.momentum)
+
+
+def fit_tables(ctx, jobs, steps: int, tree: GameTree | None = None) -> np.ndarray:
+    """``nfsp_fit_tables``: every job's net takes ``steps`` full-batch steps on its seat's rows, one
+    workgroup per job (64 per launch), deterministic: a job's result depends on the job alone, and
+    ``steps`` split over calls with ``v`` carried gives the bits of one call.  Returns the
+    weighted losses ``[n, 2]``: at the weights before step 1 and at the final weights."""
+    tree = tree or GameTree.of(ctx.game)
+    for k, j in enumerate(jobs):
+        for name, t, numel in (("target", j.target, tree.ndec * 9), ("weight", j.weight, tree.ndec * 3),
+                               ("mask", j.mask, tree.ndec * 9)):
+            if t is not None and t.numel() != numel:
+                raise ValueError(f"fit_tables: job {k}: {name} has {t.numel()} values, expected {numel}")
+    n = len(jobs)
+    arr = (native.FitJob * max(n, 1))(*[j.spec() for j in jobs])
+    out = np.zeros((n, 2))
+    native.check(ctx.L.nfsp_fit_tables(ctx.h, tree.game, arr, n, int(steps), out.ctypes.data_as(native.P)),
+                 "nfsp_fit_tables")
+    return out
+
+
+def joint_table(ctx, seat0, seat1, tree: GameTree | None = None) -> np.ndarray:
+    """The two seats' policies (``Policy`` or table) as one executed table: seat i's rows from
+    seat i's."""
+    tree = tree or GameTree.of(ctx.game)
+
+    def host(p):
+        return policy_table(ctx, p, tree).cpu().numpy() if isinstance(p, Policy) else tree.remap(p)
+    t0 = host(seat0)
+    t1 = t0 if seat1 is seat0 else host(seat1)
+    return np.where((tree.seat == 0)[:, None, None], t0, t1)
+
+
+def visit_weights(ctx, seat0, seat1, tree: GameTree | None = None) -> np.ndarray:
+    """``[ndec, 3]``: the probability that a hand reaches each information set when ``seat0``
+    plays seat 0 and ``seat1`` seat 1 (``Policy`` or table each): ``best_response(values=True)``'s
+    ``reach`` (chance and the other seat) times the acting seat's own reach
+    (``GameTree.own_reach``).  The exact visit distribution of the two policies' self-play: the
+    weights under which a net fitted to a table is fitted where the table is played."""
+    tree = tree or GameTree.of(ctx.game)
+    p0 = seat0 if isinstance(seat0, Policy) else Policy.table(tree.remap(seat0))
+    p1 = p0 if seat1 is seat0 else seat1 if isinstance(seat1, Policy) else Policy.table(tree.remap(seat1))
+    _, _, reach = best_response(ctx, p0, p1, values=True, tree=tree)
+    return reach.cpu().numpy() * tree.own_reach(joint_table(ctx, p0, p1, tree))
 
 
 def _rms(err, weight):

@@ -117,6 +117,12 @@ class TdArgs(C.Structure):
     _fields_ = [("dev_target_w", P), ("gamma", F64), ("quirks", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class FitJob(C.Structure):
+    """``nfsp_fit_job``: one net fitted to one seat's rows of a table (nfsp_fit_tables)"""
+    _fields_ = [("dev_w", P), ("dev_v", P), ("dev_target", P), ("dev_weight", P), ("dev_mask", P),
+                ("seat", C.c_int32), ("head", C.c_int32), ("loss", C.c_int32), ("lr", F32), ("momentum", F32)]
+
+
 PP = C.POINTER(P)
 # name -> (restype, argtypes); must list every symbol include/nfsp.h declares
 SIGNATURES = {
@@ -235,6 +241,9 @@ SIGNATURES = {
     "nfsp_table_rows": (I32, [P, I32, I32, P, P, P, I32, P, P]),
     "nfsp_engine_tabular_q": (I32, [P, I32, P, P, P, C.POINTER(MemtabInfo), C.POINTER(C.c_int32)]),
     "nfsp_group_tabular_q": (I32, [P, I32, P, P, P, C.POINTER(MemtabInfo), C.POINTER(C.c_int32)]),
+    # nets fitted to tables: weighted full-batch descent, one workgroup per job
+    "nfsp_fit_jobs_check": (I32, [C.POINTER(FitJob), I32, I64]),
+    "nfsp_fit_tables": (I32, [P, I32, C.POINTER(FitJob), I32, I64, P]),
 }
 # int (*nfsp_exchange_fn)(void* user, float* dev_sum, int64_t n)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, P, P, I64)
@@ -257,6 +266,9 @@ TABQ_MAX_SWEEPS = 64
 TABLE_ROWS_MAX = 65535
 MEMTAB_FIX_SHIFT = 24
 MEMTAB_MAX_SEGMENTS = 8
+# losses of nfsp_fit_tables (NFSP_FIT_*) and its jobs per launch
+FIT_CE, FIT_MSE, FIT_HUBER = 0, 1, 2
+FIT_MAX_JOBS = 64
 
 _LIB = None
 
