@@ -208,11 +208,19 @@ int nfsp_br_targets(nfsp_ctx* ctx, const float* dev_target_w, int hidden,
 /* ---------------------------------------------------------------- memories */
 /* ReplayBuffer.add / ReservoirBuffer.add (utils/replay_buffer.py:30-41,
  * utils/ReservoirBuffer.py:18-28): copy n records src[i] -> dst[dev_slots[i]].  The slot
- * policy (FIFO head, reservoir j) is the caller's; duplicate slots: last i wins. */
+ * policy (FIFO head, reservoir j) is the caller's; duplicate slots: last i wins, for every
+ * n and whatever the order the device works in (the result is the sequential loop's).  Only
+ * the columns that are non-NULL in both tables are copied.  A record whose slot lies outside
+ * [0, dst->cap) is skipped: nothing is read or written for it.  NFSP_EINVAL, with nothing
+ * launched: a NULL argument, n < 0, dst->cap <= 0 or src->cap <= 0, n > src->cap.  n == 0
+ * succeeds and launches nothing.  The ctx keeps one word per row of the largest dst seen. */
 int nfsp_buf_insert(nfsp_ctx* ctx, const nfsp_records* dst, const nfsp_records* src,
                     const int64_t* dev_slots, int64_t n);
 /* sample_batch (utils/replay_buffer.py:46-59, utils/ReservoirBuffer.py:33-43): gather
- * dst[i] = src[dev_idx[i]] for i < k (columns that are NULL in dst are skipped). */
+ * dst[i] = src[dev_idx[i]] for i < k (columns that are NULL in dst or in src are skipped;
+ * indices may repeat).  A row whose index lies outside [0, src->cap) is skipped: nothing is
+ * read, and dst[i] keeps what it held.  NFSP_EINVAL, with nothing launched: a NULL argument,
+ * k < 0, dst->cap <= 0 or src->cap <= 0, k > dst->cap.  k == 0 succeeds and launches nothing. */
 int nfsp_buf_sample(nfsp_ctx* ctx, const nfsp_records* src, const int64_t* dev_idx,
                     int64_t k, const nfsp_records* dst);
 

@@ -238,18 +238,9 @@ extern "C" int nfsp_env_export(nfsp_ctx* c, void* out) {
 // ---------------------------------------------------------------------------
 // memories: row copies between record tables (one lane per 4-byte word)
 // ---------------------------------------------------------------------------
-// Row layout of one record seen as 65 words: s[30] a[3] r s2[30] t.  `scatter` selects
-// insert (dst row = idx[i]) vs sample (src row = idx[i]).
-__global__ void k_rows_copy(nfsp_records dst, nfsp_records src, const int64_t* __restrict__ idx,
-                            int64_t n, int scatter) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  constexpr int W = 65;
-  if (e >= n * W) return;
-  const int64_t i = e / W;
-  const int w = (int)(e - i * W);
-  const int64_t j = idx[i];
-  const int64_t di = scatter ? j : i;
-  const int64_t si = scatter ? i : j;
+// Row layout of one record seen as 65 words: s[30] a[3] r s2[30] t.
+__device__ __forceinline__ void copy_word(const nfsp_records& dst, int64_t di, const nfsp_records& src,
+                                          int64_t si, int w) {
   if (w < 30) {
     if (dst.s && src.s) dst.s[di * 30 + w] = src.s[si * 30 + w];
   } else if (w < 33) {
@@ -263,65 +254,78 @@ __global__ void k_rows_copy(nfsp_records dst, nfsp_records src, const int64_t* _
   }
 }
 
-// Duplicate destination slots in one insert batch: the reference applies adds one at a
-// time, so the LAST record aimed at a slot must win.  Mark the earlier ones dead first.
-__global__ void k_last_writer(const int64_t* __restrict__ slots, int64_t n, int64_t* __restrict__ live) {
+// sample: dst row i = src row idx[i]; an index outside [0, src.cap) leaves dst row i alone
+__global__ void k_rows_gather(nfsp_records dst, nfsp_records src, const int64_t* __restrict__ idx,
+                              int64_t k) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  constexpr int W = 65;
+  if (e >= k * W) return;
+  const int64_t i = e / W;
+  const int64_t j = idx[i];
+  if (j < 0 || j >= src.cap) return;
+  copy_word(dst, i, src, j, (int)(e - i * W));
+}
+
+// Duplicate destination slots in one insert batch: the reference applies adds one at a time, so
+// the LAST record aimed at a slot must win, whatever the order the lanes run in.  owner[slot]
+// (one word per row of dst, -1 between calls) takes the largest i aimed at the slot; then only
+// the lanes of that record copy, and the words they used are set back to -1.  A slot outside
+// [0, cap) owns nothing and copies nothing.
+__global__ void k_slot_owner(const int64_t* __restrict__ slots, int64_t n, int64_t cap,
+                             long long* __restrict__ owner) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int64_t s = slots[i];
-  int64_t out = s;
-  for (int64_t k = i + 1; k < n; ++k)
-    if (slots[k] == s) { out = -1; break; }
-  live[i] = out;
+  if (s < 0 || s >= cap) return;
+  atomicMax(owner + s, (long long)i);
 }
 
-__global__ void k_rows_insert_live(nfsp_records dst, nfsp_records src, const int64_t* __restrict__ live,
-                                   int64_t n) {
+__global__ void k_rows_insert_owned(nfsp_records dst, nfsp_records src, const int64_t* __restrict__ slots,
+                                    int64_t n, const long long* __restrict__ owner) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   constexpr int W = 65;
   if (e >= n * W) return;
   const int64_t i = e / W;
-  const int64_t di = live[i];
-  if (di < 0) return;
-  const int w = (int)(e - i * W);
-  if (w < 30) {
-    if (dst.s && src.s) dst.s[di * 30 + w] = src.s[i * 30 + w];
-  } else if (w < 33) {
-    if (dst.a && src.a) dst.a[di * 3 + (w - 30)] = src.a[i * 3 + (w - 30)];
-  } else if (w == 33) {
-    if (dst.r && src.r) dst.r[di] = src.r[i];
-  } else if (w < 64) {
-    if (dst.s2 && src.s2) dst.s2[di * 30 + (w - 34)] = src.s2[i * 30 + (w - 34)];
-  } else {
-    if (dst.t && src.t) dst.t[di] = src.t[i];
-  }
+  const int64_t s = slots[i];
+  if (s < 0 || s >= dst.cap) return;
+  if (owner[s] != i) return;
+  copy_word(dst, s, src, i, (int)(e - i * W));
+}
+
+__global__ void k_slot_owner_clear(const int64_t* __restrict__ slots, int64_t n, int64_t cap,
+                                   long long* __restrict__ owner) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t s = slots[i];
+  if (s < 0 || s >= cap) return;
+  owner[s] = -1;
 }
 
 extern "C" int nfsp_buf_insert(nfsp_ctx* c, const nfsp_records* dst, const nfsp_records* src,
                                const int64_t* slots, int64_t n) {
   NFSP_REQUIRE(c && dst && src && slots, "null argument");
   NFSP_REQUIRE(n >= 0, "n < 0");
+  NFSP_REQUIRE(dst->cap > 0 && src->cap > 0, "cap <= 0");
+  NFSP_REQUIRE(n <= src->cap, "n > src->cap");
   if (n == 0) return NFSP_OK;
-  if (n <= 4096) {
-    // small batches (the drop-in's per-call adds): resolve duplicates on device, no host sync
-    if (c->scratch_i64_cap < n) {
-      NFSP_HIP(hipStreamSynchronize(c->stream));
-      if (c->scratch_i64) NFSP_HIP(hipFree(c->scratch_i64));
-      c->scratch_i64 = nullptr;
-      c->scratch_i64_cap = 0;
-      NFSP_HIP(hipMalloc(&c->scratch_i64, sizeof(int64_t) * 4096));
-      c->scratch_i64_cap = 4096;
-    }
-    int64_t* live = c->scratch_i64;
-    k_last_writer<<<nfsp_blocks(n, 256), 256, 0, c->stream>>>(slots, n, live);
-    NFSP_LAUNCHED("k_last_writer");
-    k_rows_insert_live<<<nfsp_blocks(n * 65, 256), 256, 0, c->stream>>>(*dst, *src, live, n);
-    NFSP_LAUNCHED("k_rows_insert_live");
-  } else {
-    // large batches: caller guarantees distinct slots (FIFO ring segments)
-    k_rows_copy<<<nfsp_blocks(n * 65, 256), 256, 0, c->stream>>>(*dst, *src, slots, n, 1);
-    NFSP_LAUNCHED("k_rows_copy(insert)");
+  // one owner word per row of dst; every call leaves the words it used at -1 again
+  if (c->scratch_i64_cap < dst->cap) {
+    NFSP_HIP(hipStreamSynchronize(c->stream));
+    if (c->scratch_i64) NFSP_HIP(hipFree(c->scratch_i64));
+    c->scratch_i64 = nullptr;
+    c->scratch_i64_cap = 0;
+    const int64_t words = dst->cap > 4096 ? dst->cap : 4096;
+    NFSP_HIP(hipMalloc(&c->scratch_i64, sizeof(int64_t) * (size_t)words));
+    c->scratch_i64_cap = words;
+    NFSP_HIP(hipMemsetAsync(c->scratch_i64, 0xFF, sizeof(int64_t) * (size_t)words, c->stream));
   }
+  long long* owner = (long long*)c->scratch_i64;
+  k_slot_owner<<<nfsp_blocks(n, 256), 256, 0, c->stream>>>(slots, n, dst->cap, owner);
+  NFSP_LAUNCHED("k_slot_owner");
+  k_rows_insert_owned<<<nfsp_blocks(n * 65, 256), 256, 0, c->stream>>>(*dst, *src, slots, n, owner);
+  NFSP_LAUNCHED("k_rows_insert_owned");
+  k_slot_owner_clear<<<nfsp_blocks(n, 256), 256, 0, c->stream>>>(slots, n, dst->cap, owner);
+  NFSP_LAUNCHED("k_slot_owner_clear");
   return NFSP_OK;
 }
 
@@ -329,8 +333,10 @@ extern "C" int nfsp_buf_sample(nfsp_ctx* c, const nfsp_records* src, const int64
                                const nfsp_records* dst) {
   NFSP_REQUIRE(c && dst && src && idx, "null argument");
   NFSP_REQUIRE(k >= 0, "k < 0");
+  NFSP_REQUIRE(dst->cap > 0 && src->cap > 0, "cap <= 0");
+  NFSP_REQUIRE(k <= dst->cap, "k > dst->cap");
   if (k == 0) return NFSP_OK;
-  k_rows_copy<<<nfsp_blocks(k * 65, 256), 256, 0, c->stream>>>(*dst, *src, idx, k, 0);
-  NFSP_LAUNCHED("k_rows_copy(sample)");
+  k_rows_gather<<<nfsp_blocks(k * 65, 256), 256, 0, c->stream>>>(*dst, *src, idx, k);
+  NFSP_LAUNCHED("k_rows_gather");
   return NFSP_OK;
 }

@@ -20,8 +20,8 @@ struct nfsp_ctx {
   bool has_pending_deal = false;
   uint64_t resets = 0;                // reset index (Philox counter word)
   double* scratch_f64 = nullptr;      // small device scratch
-  int64_t* scratch_i64 = nullptr;     // insert de-duplication scratch
-  int64_t scratch_i64_cap = 0;
+  int64_t* scratch_i64 = nullptr;     // nfsp_buf_insert: the last writer of each dst row (-1 between calls)
+  int64_t scratch_i64_cap = 0;        // its words: the largest dst->cap seen
   void* deal_mt = nullptr;            // nfsp_env_set_deal_mode's MT19937 state (deal_mt.hip)
 };
 
