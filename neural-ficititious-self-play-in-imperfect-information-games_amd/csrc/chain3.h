@@ -164,9 +164,9 @@ struct Chain3Smem {
   float po[2][4][64][4];     // per-wave partial layer-2 outputs by sample (rows 0..31 used),
                              // double-buffered by step parity
   float4 w2t[4][64];         // wave-private: W2[h][0..2] of the slice (rows 0..15: the layer-2
-                             // weights live here, each component written by the lanes owning it)
-  float b2s[4][4];           // wave-private: b2
-  StepRec ring[4];           // step records t .. t + 2 (slot t & 3), a quarter per wave
+                             // weights live here, each component written by the lanes owning it;
+                             // b2 lives in registers, chain3_body.inc)
+  StepRec ring[4];          // step records t .. t + 2 (slot t & 3), a quarter per wave
   uint4 rec_sink[64];
 };
 constexpr int REC_CHUNKS = (int)(sizeof(StepRec) / 16);    // 160 x 16 B

@@ -5,7 +5,9 @@
 // One wave per SIMD issues in order and LDS returns a wave's reads in order, so a read parks the
 // serial chain when its s_waitcnt is reached early, and it delays every read queued behind it:
 // hence the comments below on where each LDS read sits.  The placements that lost are in
-// DESIGN.md Appendix A.0b / A.2 and profiles/r07_chain_reads/.
+// DESIGN.md Appendix A.0b / A.0c / A.2 and profiles/r07_chain_reads/, profiles/r08_chain_b2/.
+// The schedule is sensitive to the source's statement order well beyond what the data flow
+// explains (A.0c): after any edit here, time both chains (tools/bench_chain.hip).
   // the loss-log build (a diagnostic, tests/test_gpu_nn / observability) runs the scalar forms:
   // its extra loss code put packed writes near MFMA registers (tools/mfma_hazards.py rule 2);
   // the packed forms round exactly as the scalar ones, so its weights are the same either way
@@ -79,20 +81,55 @@
     sm.w2t[w][l] = make_float4(W2_0, W2_1, W2_2, 0.f);
   };
   const SplitK SK = split_consts();
-  // W2 and b2 live in the wave's LDS (w2t rows 0..15, b2s); the cross-lane reductions leave
-  // each gradient total in one row of lanes (see the update), and that row owns the value:
-  //   row 0: W2[c][0]   row 1: W2[c][2]   row 2: W2[c][1]   row 3: b2[0]  (own1; row 3's total
-  //   is 4 gb2[0], scaled by 1/4 -- exact)        rows 0, 1: b2[1]   rows 2, 3: b2[2]  (own2)
-  float* const own1 = g == 3 ? &sm.b2s[w][0] : reinterpret_cast<float*>(&sm.w2t[w][c]) + (g == 0 ? 0 : g == 1 ? 2 : 1);
-  float* const own2 = &sm.b2s[w][g < 2 ? 1 : 2];
-  const float own1_sc = g == 3 ? 0.25f : 1.0f;
-  // The lane's two owned values stay in registers across the steps (ov1, ov2: what publish()
-  // and the b2s stores below put into the own1 / own2 slots).  Each lane is the only writer of
-  // the value it holds (the lanes that share a b2 slot compute bit-identical totals, see `ls`),
-  // so nothing is read back; LDS keeps its copy for the other rows' reads next step and for
-  // the epilogue
-  float ov1 = g == 3 ? b2_0 : g == 0 ? W2_0 : g == 1 ? W2_2 : W2_1;
-  float ov2 = g < 2 ? b2_1 : b2_2;
+  // W2 lives in the wave's LDS (w2t rows 0..15); the cross-lane reductions leave each W2
+  // gradient total in one row of lanes (see the update), and that row owns the value:
+  //   row 0: W2[c][0]   row 1: W2[c][2]   row 2: W2[c][1]   (own1; row 3 stores to a sink row)
+  float* const own1 = g == 3 ? &sm.w2t[w][48 + c].x : reinterpret_cast<float*>(&sm.w2t[w][c]) + (g == 0 ? 0 : g == 1 ? 2 : 1);
+  // The lane's owned value stays in a register across the steps (ov1: what publish() puts into
+  // the own1 slot).  Each lane is the only writer of the value it holds, so nothing is read
+  // back; LDS keeps its copy for the other rows' reads next step and for the epilogue
+  float ov1 = g == 0 ? W2_0 : g == 1 ? W2_2 : W2_1;
+  // b2 lives in registers, a copy in every lane (b2_0 .. b2_2), and its update is carried across
+  // the step boundary: nothing on dz -> dW1 -> W1 -> the next W split reads gb2, and b2 is first
+  // needed after the NEXT step's barrier.  Step t leaves its loss gradients and lr pending (pd0 ..
+  // pd2, plr); step t + 1 takes their 32-sample totals (tot32's order, every total in every
+  // lane: the lanes compute bit-identical totals, see `ls`) and applies b2 -= lr gb2 where the
+  // wave has issue slots to spare -- BR: the totals' first levels in the gaps of the Z1 MFMAs
+  // between the partial stores and the barrier, the rest behind the partial-sum reads after
+  // it; AR: at the head of layer 2, beside the last Z1^T MFMAs (each where it measured fastest,
+  // DESIGN.md Appendix A.0c).  Pending starts as 0 (b2 - 0 * 0 is b2), and the epilogue applies
+  // the last one.
+  float pd0 = 0.f, pd1 = 0.f, pd2 = 0.f, plr = 0.f;
+  float ph0 = 0.f, ph12 = 0.f;      // BR: the totals after their first three levels
+  // gb2[0]'s partial in every lane; gb2[1]'s in rows 0 / 1 and gb2[2]'s in rows 2 / 3 (tot32_pair)
+  auto b2_head = [&]() {
+    ph0 = sum_x32(pd0);
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(pd1), __float_as_uint(pd2), false, false);
+    ph12 = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    ph0 = ph0 + dpp_bc<0x128>(ph0);
+    ph12 = ph12 + dpp_bc<0x128>(ph12);
+    ph0 = ph0 + dpp_bc<0x4E>(ph0);
+    ph12 = ph12 + dpp_bc<0x4E>(ph12);
+  };
+  // U = gb2[1] in rows 0 / 1, gb2[2] in rows 2 / 3: one swap leaves each in every lane
+  auto b2_tail = [&](float G0, float U) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(U), __float_as_uint(U), false, false);
+    b2_0 = b2_0 - plr * G0;
+    b2_1 = b2_1 - plr * __uint_as_float(r[0]);
+    b2_2 = b2_2 - plr * __uint_as_float(r[1]);
+  };
+  auto b2_rest = [&]() {            // the totals' last two levels (tot_rows) and the update
+    float x = ph0 + dpp_bc<0xB1>(ph0), y = ph12 + dpp_bc<0xB1>(ph12);
+    b2_tail(x + dpp_bc<0x124>(x), y + dpp_bc<0x124>(y));
+  };
+  auto apply_b2 = [&]() {           // the whole pending update (AR's step; both epilogues)
+    if constexpr (RELU) b2_tail(tot32(pd0), tot32_pair(pd1, pd2));
+    else {
+      b2_0 = b2_0 - plr * tot32(pd0);
+      b2_1 = b2_1 - plr * tot32(pd1);
+      b2_2 = b2_2 - plr * tot32(pd2);
+    }
+  };
 #ifdef NFSP_CHAIN_STAMPS
   unsigned long long st_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last = 0;
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_last)::"memory");
@@ -120,9 +157,9 @@
     // ---- layer 1, both orientations
     bf16x8 whi, wmid, wlo;
     split3(wr, whi, wmid, wlo, SK);
-    // W2 / b2 after the W split.  The reads need no barrier: w2t[w] / b2s[w] are this wave's own
-    // rows, last written by its own-stores at the end of the previous step (or the prologue), and
-    // LDS executes a wave's operations in order
+    // W2 after the W split.  The reads need no barrier: w2t[w] is this wave's own rows, last
+    // written by its own-stores at the end of the previous step (or the prologue), and LDS
+    // executes a wave's operations in order
     float W2h[4][3];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -131,17 +168,29 @@
     }
     const floatx4 w2c = lds4(&sm.w2t[w][c]);     // W2 of this lane's hidden unit (backward)
     const float W2_0 = w2c[0], W2_1 = w2c[1], W2_2 = w2c[2];
-    const floatx4 b2v = lds4(&sm.b2s[w][0]);
-    const float b2_0 = b2v[0], b2_1 = b2v[1], b2_2 = b2v[2];
     // Z1^T first (layer 2 waits on it); Z1 (needed only by the backward) is issued after
     // layer 2, so its matrix-core time overlaps the barrier wait
-    const floatx4 zh0 = mfma3t(whi, wmid, wlo, fa0);     // Z1^T: hidden 16w+4g+r, sample c
-    const floatx4 zh1 = mfma3t(whi, wmid, wlo, fa1);     //                      sample 16+c
+    floatx4 zh0, zh1;
+    if constexpr (!RELU) {     // AR: the two tiles' lo terms first, pinned by a fence (each tile
+      const floatx4 z = {};    // still accumulates lo, mid, hi); BR is faster as mfma3t leaves it
+      zh0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, fa0, z, 0, 0, 0);
+      zh1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, fa1, z, 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      zh0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wmid, fa0, zh0, 0, 0, 0);
+      zh1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wmid, fa1, zh1, 0, 0, 0);
+      zh0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi, fa0, zh0, 0, 0, 0);
+      zh1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi, fa1, zh1, 0, 0, 0);
+    } else {
+      zh0 = mfma3t(whi, wmid, wlo, fa0);     // Z1^T: hidden 16w+4g+r, sample c
+      zh1 = mfma3t(whi, wmid, wlo, fa1);     //                      sample 16+c
+    }
     __builtin_amdgcn_sched_barrier(0);
     CHAIN_STAMP(0);
     // X^T: ring slot `slot` was published by the previous step's barrier, so it is readable before
     // this step's; here the ~45 VALU instructions of layer 2 cover the reads, and the partial sums
-    // are the first reads in the LDS queue after the barrier
+    // are the first reads in the LDS queue after the barrier.  AR: the pending b2 update first,
+    // beside the last Z1^T MFMAs
+    if constexpr (!RELU) apply_b2();
     ba0 = tr_pair(rtr, rtr + 256);
     ba1 = tr_pair(rtr + 8, rtr + 264);
     // ---- layer 2 partial over the slice, from Z1^T
@@ -196,6 +245,16 @@
     const floatx4 zs0 = mfma3(fa0, whi, wmid, wlo);      // Z1: sample 4g+r, hidden 16w+c
     const floatx4 zs1 = mfma3(fa1, whi, wmid, wlo);      //     sample 16+4g+r
     if constexpr (!RELU) tg = R.tg[ls];                  // AR: read before the barrier pins it early
+    if constexpr (RELU) {
+      // BR: the pending totals' first levels, one VALU instruction behind each Z1 MFMA (a
+      // 16x16x32 MFMA holds the issue port for half of its 16 cycles)
+      b2_head();
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     // 1 MFMA
+        __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);     // 1 VALU
+      }
+    }
     if (fenced) __builtin_amdgcn_sched_barrier(0);       // ... and the Z1 MFMAs issue before it
     CHAIN_STAMP(1);
     __syncthreads();
@@ -203,11 +262,23 @@
     // ---- output + loss of sample ls (every wave redundantly, identical results)
     float d0, d1, d2, lr_step;
     float o_keep[3], tt_keep[3], p_keep[3];     // for the optional loss log
+    // Z1, its ReLU and its derivative mask (filled in the backward block).  Declared here: with
+    // them inside that block the same data flow compiled to a slower BR schedule (A.0c)
+    const float zz[8] = {zs0[0], zs0[1], zs0[2], zs0[3], zs1[0], zs1[1], zs1[2], zs1[3]};
+    float hz[8];
+    bool mz[8];
     {
       const floatx4 a0 = lds4(&sm.po[buf][0][ls][0]);
       const floatx4 a1 = lds4(&sm.po[buf][1][ls][0]);
       const floatx4 a2 = lds4(&sm.po[buf][2][ls][0]);
       const floatx4 a3 = lds4(&sm.po[buf][3][ls][0]);
+      // BR: the rest of the pending b2 update, fenced behind the partial-sum reads, where the
+      // wave waits for them
+      if constexpr (RELU) {
+        __builtin_amdgcn_sched_barrier(0);
+        b2_rest();
+        __builtin_amdgcn_sched_barrier(0);
+      }
       const float o0 = (((a0[0] + a1[0]) + a2[0]) + a3[0]) + b2_0;
       const float o1 = (((a0[1] + a1[1]) + a2[1]) + a3[1]) + b2_1;
       const float o2 = (((a0[2] + a1[2]) + a2[2]) + a3[2]) + b2_2;
@@ -295,48 +366,46 @@
         }
       }
     }
-    // gb2 = the 32-sample sums of d (tot32's order): gb2[0] in every lane, gb2[1] in rows 0 / 1
-    // and gb2[2] in rows 2 / 3 (U, the rows that own b2[1] / b2[2])
-    const float G0 = tot32(d0);
-    const float U = tot32_pair(d1, d2);
+    // gb2 (the 32-sample sums of d) and b2's update are left pending for the next step, or the
+    // epilogue: the dW1 MFMAs issue directly behind the dz split
+    pd0 = d0; pd1 = d1; pd2 = d2; plr = lr_step;
     CHAIN_STAMP(3);
     // ---- backward in the sample-major layout: samples 16 mt + 4g + r, hidden 16w + c
     float dz[8];
     float g2_0, g2_1, g2_2;          // started by slot 0 (bwd_dpp<0>)
     {
-      const float zz[8] = {zs0[0], zs0[1], zs0[2], zs0[3], zs1[0], zs1[1], zs1[2], zs1[3]};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { hz[j] = fmaxf(zz[j], 0.f); mz[j] = zz[j] > 0.f; }
       float dh[8];
-#define NFSP_BWD_SLOT(J) dh[J] = bwd_dpp<J>(g2_0, g2_1, g2_2, d0, d1, d2, fmaxf(zz[J], 0.f), W2_0, W2_1, W2_2)
+#define NFSP_BWD_SLOT(J) dh[J] = bwd_dpp<J>(g2_0, g2_1, g2_2, d0, d1, d2, hz[J], W2_0, W2_1, W2_2)
       NFSP_BWD_SLOT(0); NFSP_BWD_SLOT(1); NFSP_BWD_SLOT(2); NFSP_BWD_SLOT(3);
       NFSP_BWD_SLOT(4); NFSP_BWD_SLOT(5); NFSP_BWD_SLOT(6); NFSP_BWD_SLOT(7);
 #undef NFSP_BWD_SLOT
 #pragma unroll
-      for (int j = 0; j < 8; ++j) dz[j] = zz[j] > 0.f ? dh[j] : 0.f;
+      for (int j = 0; j < 8; ++j) dz[j] = mz[j] ? dh[j] : 0.f;
     }
     bf16x8 dhi, dmid, dlo;
     split3(dz, dhi, dmid, dlo, SK);
     // dW1[16 it + 4g + r][16w + c] = sum over the 32 samples in dz's K order (row 30: gb1)
     const floatx4 gA = mfma3(ba0, dhi, dmid, dlo);
     const floatx4 gB = mfma3(ba1, dhi, dmid, dlo);
-    // The four row totals of (g2_0, g2_1, g2_2, gb2[0]) in one transpose: two swaps across
-    // rows g ^ 2, one across g ^ 1 leave g2_0's total in row 0, g2_2's in row 1, g2_1's in row 2
-    // and 4 gb2[0] in row 3 (gb2[0] is in every row), each added (r0 + r2) + (r1 + r3) as
-    // sum_x16(sum_x32(.)) did.  Each row updates the values it holds (own1, own2).
+    // The row totals of (g2_0, g2_1, g2_2) in one transpose: two swaps across rows g ^ 2, one
+    // across g ^ 1 leave g2_0's total in row 0, g2_2's in row 1 and g2_1's in row 2, each added
+    // (r0 + r2) + (r1 + r3) as sum_x16(sum_x32(.)) did (row 3 gets g2_2's again and stores it to
+    // a sink row).  Each row updates the value it holds (own1).
     float V;
     {
       const auto ab = __builtin_amdgcn_permlane32_swap(__float_as_uint(g2_0), __float_as_uint(g2_1), false, false);
       const float tab = __uint_as_float(ab[0]) + __uint_as_float(ab[1]);
-      const auto cd = __builtin_amdgcn_permlane32_swap(__float_as_uint(g2_2), __float_as_uint(G0), false, false);
+      const auto cd = __builtin_amdgcn_permlane32_swap(__float_as_uint(g2_2), __float_as_uint(g2_2), false, false);
       const float tcd = __uint_as_float(cd[0]) + __uint_as_float(cd[1]);
       const auto z = __builtin_amdgcn_permlane16_swap(__float_as_uint(tab), __float_as_uint(tcd), false, false);
       V = __uint_as_float(z[0]) + __uint_as_float(z[1]);
     }
     CHAIN_STAMP(4);
     const float lr = lr_step;
-    ov1 = ov1 - (lr * own1_sc) * V;
-    ov2 = ov2 - lr * U;
+    ov1 = ov1 - lr * V;
     *own1 = ov1;
-    *own2 = ov2;
     if constexpr (PK & PK_W) {      // W1 -= lr dW1, two rows per instruction
       const floatx2 nl = {-lr, -lr};
 #pragma unroll
@@ -364,7 +433,6 @@
       stash(t + 1, va);
     }
     publish();
-    if (l < 3) sm.b2s[w][l] = l == 0 ? b2_0 : l == 1 ? b2_1 : b2_2;
     __syncthreads();
     // drain the prologue's loads: the loop header then merges no pending load into the
     // registers the loop reuses (else every step waits on its fresh record load)
@@ -397,10 +465,10 @@
     }
   }
 #endif
-  if (t > (int)(u0 * spu)) {             // the loop ran: W2 / b2 as the last step left them
+  if (t > (int)(u0 * spu)) {   // the loop ran: W2 as the last step left it, and its pending b2 update
     const float4 fw = sm.w2t[w][c];
     W2_0 = fw.x; W2_1 = fw.y; W2_2 = fw.z;
-    b2_0 = sm.b2s[w][0]; b2_1 = sm.b2s[w][1]; b2_2 = sm.b2s[w][2];
+    apply_b2();
   }
   float* dsts[3] = {gw, J.sync_to, J.snap_to};
   for (int k = 0; k < 3; ++k) {
