@@ -730,6 +730,74 @@ int nfsp_xfp_state(nfsp_xfp* h, int run, double* host_S /*[ndec][3][3]*/, double
                    double* W);
 int nfsp_xfp_destroy(nfsp_xfp* h);
 
+/* ---- external-sampling MCCFR on the evaluator's tree (csrc/mccfr.hip k_mccfr_walk, k_mccfr_apply) ----
+ * ES-MCCFR (Lanctot, Waugh, Zinkevich and Bowling 2009): the sampled counterpart of CFR+ as
+ * tabular NFSP is XFP's -- a plain sampled tabular learner whose cost is counted in traversals
+ * and terminals visited, the yardstick beside the engine's curves in hands (the reference has no
+ * solver).  A handle holds n independent runs, each with a seed and W walkers (W even).
+ * Per run: R and S [ndec][3][3], int64 fixed point with NFSP_MCCFR_Q per chip (R) or per unit of
+ * probability (S), and t, the completed iterations; all 0 at creation.  The tables are integers,
+ * so sums over walkers do not depend on their order and the tables are bit-reproducible whatever
+ * the grid, as the memory tables are.
+ * Iteration t + 1 is seat i = 0, then seat 1; the half-iteration index is h = 2 t + i.
+ *   1. sigma from R, every row and rank: rp_a = (double)max(R_a, 0), 0 at an illegal raise;
+ *      s = (rp_0 + rp_1) + rp_2; sigma_a = rp_a / s, uniform over the legal actions where s = 0.
+ *      Plain regret matching: R itself is NOT floored.  sigma is frozen for the whole
+ *      half-iteration and all W walkers share it: a declared mini-batch form of MCCFR.
+ *   2. walker w = 0 .. W - 1: dealer = w & 1, from root[dealer].
+ *      u(node) = (x >> 8) 2^-24, x the first word of philox4x32(counter = (h low 32, h high 32,
+ *      w, node), key = (seed low 32, seed high 32)): the draw depends on the node id, not on the
+ *      order of the visit (a traversal visits a node at most once).
+ *      A choice among probabilities p_0 .. p_k with a draw u: the first j with u < c_j and
+ *      p_j > 0, c the running double sum from 0 in ascending order; the last j with p_j > 0 if
+ *      there is none.
+ *      The deal: drawn at the pseudo-node id nn over deal[a][b] in row-major order; seat i holds
+ *      rank a, the other seat rank b.
+ *      Traverse(n):
+ *        terminal             returns (double)pay[row][i][r_i][r_o];
+ *        chance               the child chosen by u(n) over p_public(c, r_0, r_1), c ascending;
+ *        the opponent's       for each a, dS[row][r_o][a] += llrint(sigma_a Q); the child chosen by
+ *        decision             u(n) over sigma[row][r_o];
+ *        seat i's decision    v_a = Traverse(child_a) for the legal a, ascending; v = 0, then
+ *                             v = v + sigma_a v_a, ascending, no contraction;
+ *                             dR[row][r_i][a] += llrint((v_a - v) Q); returns v.
+ *   3. R += dR, S += dS.
+ * Two counts per run: traversals (2 W t) and terminals visited -- a traversal touches a whole
+ * own-action subtree, not one hand.  |v_a - v| <= 2 max|pay| (10 chips on Leduc's tables, 4 on
+ * Kuhn's), so a run whose W x (iterations done + to come) could carry an entry past 2^62 is
+ * refused: W x iterations <= 2^62 / (NFSP_MCCFR_Q x 2 max|pay|), and the message names the bound.
+ * One lane runs one traversal, NFSP_MCCFR_WG_WALKERS of them per workgroup, which adds into int64
+ * tables in LDS and flushes its non-zero entries with 64-bit atomic adds; k_mccfr_apply, one
+ * small launch per half-iteration, does step 3, zeroes the deltas and writes the next sigma and
+ * the average.  No workgroup waits for another: the order is the stream's.  tests/mccfr_ref.py
+ * restates the rule in numpy, and R, S and the counts agree to the bit. */
+#define NFSP_MCCFR_Q 16777216        /* 2^24 */
+#define NFSP_MCCFR_MAX_RUNS 64
+#define NFSP_MCCFR_MAX_WALKERS 4194304   /* 2^22 */
+#define NFSP_MCCFR_WG_WALKERS 1024   /* traversals of one workgroup (256 lanes, 4 each in turn) */
+typedef struct {
+  uint64_t seed;
+  int32_t walkers;                      /* W: even, 2 .. NFSP_MCCFR_MAX_WALKERS */
+  int32_t reserved;                     /* 0 */
+} nfsp_mccfr_cfg;                       /* 16 bytes */
+typedef struct nfsp_mccfr nfsp_mccfr;
+/* Host only (no device, no ctx): every cfg's fields, n in 1 .. NFSP_MCCFR_MAX_RUNS, and that
+ * every run may reach `iters` iterations in all on `game`'s tables without overflow. */
+int nfsp_mccfr_cfgs_check(int game, const nfsp_mccfr_cfg* cfgs /*[n]*/, int n, int64_t iters);
+int nfsp_mccfr_create(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs /*[n]*/, int n, nfsp_mccfr** out);
+/* Continues every run by iters iterations: 2 iters (walk, apply) pairs on the ctx stream, then
+ * one synchronisation. */
+int nfsp_mccfr_run(nfsp_mccfr* h, int64_t iters);
+int nfsp_mccfr_iterations(nfsp_mccfr* h, int64_t* out);
+/* out[0] traversals (2 W t), out[1] terminals visited.  Synchronises the ctx stream. */
+int nfsp_mccfr_counts(nfsp_mccfr* h, int run, int64_t* out /*[2]*/);
+/* The average strategy of a run: S normalised per row, uniform over the legal actions where a
+ * row's sum is 0 (every row before any iteration).  A device table usable as NFSP_POL_TABLE;
+ * owned by the handle. */
+int nfsp_mccfr_average(nfsp_mccfr* h, int run, const double** dev_table);
+int nfsp_mccfr_state(nfsp_mccfr* h, int run, int64_t* host_R /*[ndec][3][3]*/, int64_t* host_S /*[ndec][3][3]*/);
+int nfsp_mccfr_destroy(nfsp_mccfr* h);
+
 /* ---- the memories as tables (csrc/memtab.hip k_memtab, k_memtab_sum) ----
  * M_SL (utils/ReservoirBuffer.py:18-28) and M_RL (utils/replay_buffer.py:30-41) counted per
  * information set where they lie, from the packed device records (SlRec 16 B {obs bits, a[3]},

@@ -1,0 +1,465 @@
+// External-sampling Monte-Carlo CFR (Lanctot, Waugh, Zinkevich and Bowling 2009) on the
+// evaluator's public tree (exploit_tree.h): the sampled counterpart of cfr.hip's CFR+, as tabular
+// NFSP is xfp.hip's -- what a plain sampled tabular learner reaches per traversal on exactly the
+// game nfsp_evaluate_batch scores.  The rule is in include/nfsp.h; tests/mccfr_ref.py restates it
+// in numpy, and R, S and the counts agree to the bit.
+//
+// The first solver here that is a throughput kernel, not one barrier-bound workgroup.  n
+// independent runs (seed, W walkers).  A half-iteration (seat i updates) is two launches:
+//   k_mccfr_walk   grid (workgroups over walkers, run), 256 lanes.  A workgroup stages the run's
+//                  sigma (f64), the node table and seat i's half of pay into LDS beside zeroed
+//                  int64 dR / dS (Leduc: 45 KB, so three workgroups share a CU's LDS), then each
+//                  lane runs WG_WALKERS / 256 traversals in turn.  A traversal is a depth-first
+//                  walk of seat i's own-action subtree with chance and the opponent sampled
+//                  (Philox keyed by the node, so no draw depends on the order of the visit); its
+//                  frames at seat i's decisions -- at most MAX_FRAMES on a path, checked against
+//                  the tree at creation -- are the levels of a recursion the compiler unrolls into
+//                  registers, and every loop is bounded by the tree's depth.  Lanes add
+//                  llrint(x Q) into the LDS tables with 64-bit LDS atomics; after a barrier the
+//                  workgroup adds its non-zero entries to the run's dR / dS in device memory with
+//                  64-bit atomic adds (relaxed, agent scope).  Integer sums: the bits do not
+//                  depend on the grid or on the order of arrival.
+//   k_mccfr_apply  R += dR, S += dS, the deltas zeroed, the next sigma (regret matching on R+;
+//                  R itself is not floored), the average of S, the counts.
+// No workgroup waits for another -- no flags, no tickets, no spinning: the stream orders the
+// launches, and nfsp_mccfr_run synchronises once at its end.
+// All f64 arithmetic is in tree_walk.h's style (no FMA contraction, the sums ascending).
+#include <stdio.h>
+
+#include <vector>
+
+#include "tree_walk.h"
+
+struct nfsp_mccfr {
+  nfsp_ctx* ctx = nullptr;
+  int ndec = 0, nterm = 0, n = 0, max_walkers = 0;
+  int64_t iterations = 0;
+  std::vector<nfsp_mccfr_cfg> cfgs;
+  long long* state = nullptr;             // per run R | S | dR | dS, [ndec][3][3] each
+  double* tabs = nullptr;                 // per run sigma | average, [ndec][3][3] each
+  unsigned long long* counts = nullptr;   // per run traversals, terminals, terminals of the walk in flight
+  nfsp_mccfr_cfg* dev_cfg = nullptr;      // [n]
+};
+
+namespace {
+
+using namespace nfsp::ex;
+
+constexpr int WALK_THREADS = 256;
+constexpr int MAX_FRAMES = 4;             // seat i's decisions on one path (Leduc: 4, Kuhn: 2)
+constexpr double Q = (double)NFSP_MCCFR_Q;
+static_assert(NFSP_MCCFR_WG_WALKERS % WALK_THREADS == 0, "a lane runs a whole number of traversals");
+
+struct WalkArgs {
+  ExTables T;
+  const nfsp_mccfr_cfg* cfg;              // [n]
+  const double* tabs;                     // [n][2][ndec][3][3]: sigma first
+  long long* state;                       // [n][4][ndec][3][3]: dR, dS are the last two
+  unsigned long long* counts;             // [n][3]
+  uint32_t h_lo, h_hi;                    // the half-iteration index
+  int seat, nterm;
+};
+
+struct ApplyArgs {
+  const uint8_t* legal;
+  const nfsp_mccfr_cfg* cfg;
+  long long* state;
+  double* tabs;
+  unsigned long long* counts;
+  int ndec;
+  int walked;                             // 1: a walk went before (0: the tables of creation)
+};
+
+// dynamic LDS: sigma f64, dR and dS int64, the terminal count, then the node table and pay
+__host__ __device__ inline size_t walk_lds(int nn, int ndec, int nterm) {
+  return 8 * ((size_t)ndec * 27 + 1) + sizeof(DevNode) * (size_t)nn + 4 * 9 * (size_t)nterm;
+}
+
+struct Walker {
+  const double* sg;                       // LDS
+  const DevNode* nodes;
+  const float* pay;                       // [nterm][r_i][r_o], seat i's
+  unsigned long long *dR, *dS;
+  uint32_t h_lo, h_hi, w, k0, k1;
+  int i, ri, ro, nlev;
+  uint32_t terminals;
+};
+
+__device__ __forceinline__ double draw(const Walker& X, int node) {
+  const uint32_t x = nfsp::philox4x32({X.h_lo, X.h_hi, X.w, (uint32_t)node}, X.k0, X.k1).x;
+  return (double)(x >> 8) * 5.9604644775390625e-08;
+}
+
+// One step of the rule's choice: c is the running sum, pick the first j with u < c_j and p_j > 0,
+// last the last j with p_j > 0.
+__device__ __forceinline__ void choice_step(double p, int j, double u, double& c, int& pick, int& last) {
+#pragma clang fp contract(off)
+  c = c + p;
+  if (p > 0.0) {
+    last = j;
+    if (pick < 0 && u < c) pick = j;
+  }
+}
+
+__device__ __forceinline__ int choose3(double p0, double p1, double p2, double u) {
+  double c = 0.0;
+  int pick = -1, last = -1;
+  choice_step(p0, 0, u, c, pick, last);
+  choice_step(p1, 1, u, c, pick, last);
+  choice_step(p2, 2, u, c, pick, last);
+  return pick >= 0 ? pick : last;
+}
+
+__device__ __forceinline__ void add_fixed(unsigned long long* p, double x) {
+  const long long v = (long long)__builtin_rint(x);    // llrint: |x| <= 2 max|pay| Q, far inside int64
+  if (v != 0) atomicAdd(p, (unsigned long long)v);
+}
+
+// Traverse(n) with D of seat i's decisions above it.  The node is read where it lies in LDS (a
+// copy indexed by the action would go to scratch).
+template <int D>
+__device__ __forceinline__ double traverse(Walker& X, int n) {
+#pragma clang fp contract(off)
+  for (int d = 0; d < X.nlev; ++d) {
+    const DevNode& N = X.nodes[n];
+    if (N.kind == TNode::TERMINAL) {
+      ++X.terminals;
+      return (double)X.pay[(size_t)N.row * 9 + X.ri * 3 + X.ro];
+    }
+    if (N.kind == TNode::DECISION && N.p == X.i) {
+      if constexpr (D < MAX_FRAMES) {
+        double v0 = 0.0, v1 = 0.0, v2 = 0.0;
+#pragma nounroll
+        for (int a = 0; a < 3; ++a) {
+          const int c = N.child[a];
+          if (c < 0) continue;
+          const double x = traverse<D + 1>(X, c);
+          if (a == 0) v0 = x;
+          else if (a == 1) v1 = x;
+          else v2 = x;
+        }
+        const size_t row = (size_t)N.row * 9 + X.ri * 3;
+        const bool l0 = N.child[0] >= 0, l1 = N.child[1] >= 0, l2 = N.child[2] >= 0;
+        double v = 0.0;
+        if (l0) v = v + X.sg[row + 0] * v0;
+        if (l1) v = v + X.sg[row + 1] * v1;
+        if (l2) v = v + X.sg[row + 2] * v2;
+        if (l0) add_fixed(X.dR + row + 0, (v0 - v) * Q);
+        if (l1) add_fixed(X.dR + row + 1, (v1 - v) * Q);
+        if (l2) add_fixed(X.dR + row + 2, (v2 - v) * Q);
+        return v;
+      } else {
+        return 0.0;                       // unreachable: nfsp_mccfr_create counted the frames
+      }
+    }
+    const double u = draw(X, n);
+    double p0, p1, p2;
+    if (N.kind == TNode::CHANCE) {
+      const int r0 = X.i == 0 ? X.ri : X.ro, r1 = X.i == 0 ? X.ro : X.ri;
+      p0 = p_public(0, r0, r1);
+      p1 = p_public(1, r0, r1);
+      p2 = p_public(2, r0, r1);
+    } else {
+      const size_t row = (size_t)N.row * 9 + X.ro * 3;
+      p0 = X.sg[row + 0];
+      p1 = X.sg[row + 1];
+      p2 = X.sg[row + 2];
+      add_fixed(X.dS + row + 0, p0 * Q);
+      add_fixed(X.dS + row + 1, p1 * Q);
+      add_fixed(X.dS + row + 2, p2 * Q);
+    }
+    const int a = choose3(p0, p1, p2, u);
+    if (a < 0) return 0.0;                // no positive probability: not a strategy
+    n = N.child[a];
+    if (n < 0) return 0.0;
+  }
+  return 0.0;
+}
+
+__global__ void __launch_bounds__(WALK_THREADS) k_mccfr_walk(WalkArgs A) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const ExTables& T = A.T;
+  const int run = blockIdx.y;
+  const int W = A.cfg[run].walkers;
+  const int w0 = blockIdx.x * NFSP_MCCFR_WG_WALKERS;
+  if (w0 >= W) return;                    // the grid is sized for the run with the most walkers
+  const int nn = T.nn, n9 = T.ndec * 9;
+  double* sg = reinterpret_cast<double*>(smem_raw);
+  unsigned long long* dR = reinterpret_cast<unsigned long long*>(sg + n9);
+  unsigned long long* dS = dR + n9;
+  unsigned long long* terms = dS + n9;
+  DevNode* nodes = reinterpret_cast<DevNode*>(terms + 1);
+  float* pay = reinterpret_cast<float*>(nodes + nn);
+  const int tid = threadIdx.x;
+  const double* gsg = A.tabs + (size_t)run * 2 * n9;
+  for (int k = tid; k < n9; k += WALK_THREADS) {
+    sg[k] = gsg[k];
+    dR[k] = 0;
+    dS[k] = 0;
+  }
+  if (tid == 0) *terms = 0;
+  for (int k = tid; k < nn; k += WALK_THREADS) nodes[k] = T.nodes[k];
+  for (int k = tid; k < A.nterm * 9; k += WALK_THREADS) pay[k] = T.pay[(size_t)(k / 9) * 18 + A.seat * 9 + k % 9];
+  __syncthreads();
+
+  Walker X;
+  X.sg = sg;
+  X.nodes = nodes;
+  X.pay = pay;
+  X.dR = dR;
+  X.dS = dS;
+  X.h_lo = A.h_lo;
+  X.h_hi = A.h_hi;
+  X.k0 = (uint32_t)A.cfg[run].seed;
+  X.k1 = (uint32_t)(A.cfg[run].seed >> 32);
+  X.i = A.seat;
+  X.nlev = T.nlev;
+  X.terminals = 0;
+  for (int k = 0; k < NFSP_MCCFR_WG_WALKERS / WALK_THREADS; ++k) {
+    const int w = w0 + k * WALK_THREADS + tid;
+    if (w >= W) continue;
+    X.w = (uint32_t)w;
+    // the deal, at the pseudo-node nn over deal[a][b] in row-major order
+    const double u = draw(X, nn);
+    double c = 0.0;
+    int pick = -1, last = -1;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) choice_step(T.deal[j / 3][j % 3], j, u, c, pick, last);
+    const int j = pick >= 0 ? pick : last;
+    if (j < 0) continue;                  // no deal has a positive probability: not a game
+    X.ri = j / 3;
+    X.ro = j % 3;
+    (void)traverse<0>(X, T.root[w & 1]);
+  }
+  if (X.terminals) atomicAdd(terms, (unsigned long long)X.terminals);
+  __syncthreads();
+
+  long long* gd = A.state + ((size_t)run * 4 + 2) * n9;    // dR | dS, as in LDS
+  for (int k = tid; k < 2 * n9; k += WALK_THREADS) {
+    const unsigned long long v = dR[k];
+    if (v)
+      __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(gd) + k, v, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (tid == 0 && *terms)
+    __hip_atomic_fetch_add(A.counts + (size_t)run * 3 + 2, *terms, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// One thread per (row, rank) of a run.
+__global__ void __launch_bounds__(256) k_mccfr_apply(ApplyArgs A) {
+#pragma clang fp contract(off)
+  const int run = blockIdx.y;
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t n9 = (size_t)A.ndec * 9;
+  if (k == 0 && A.walked) {
+    unsigned long long* c = A.counts + (size_t)run * 3;
+    c[0] += (unsigned long long)A.cfg[run].walkers;
+    c[1] += c[2];
+    c[2] = 0;
+  }
+  if (k >= A.ndec * 3) return;
+  long long* R = A.state + (size_t)run * 4 * n9 + 3 * (size_t)k;
+  long long* S = R + n9;
+  long long* dR = S + n9;
+  long long* dS = dR + n9;
+  const bool legal_raise = A.legal[k / 3] & 1;
+  double rp[3], s[3];
+  for (int a = 0; a < 3; ++a) {
+    const long long r = R[a] + dR[a], t = S[a] + dS[a];
+    R[a] = r;
+    S[a] = t;
+    dR[a] = 0;
+    dS[a] = 0;
+    rp[a] = (double)(r > 0 ? r : 0);
+    s[a] = (double)t;
+  }
+  if (!legal_raise) rp[2] = 0.0;
+  double* sg = A.tabs + (size_t)run * 2 * n9 + 3 * (size_t)k;
+  average_row(rp, legal_raise, sg);
+  average_row(s, legal_raise, sg + n9);
+}
+
+// seat i's decisions on the longest path below n
+int frames_below(const HostTables& H, int n, int i) {
+  if (n < 0) return 0;
+  const DevNode& N = H.nodes[n];
+  int m = 0;
+  for (int a = 0; a < 3; ++a) m = std::max(m, frames_below(H, N.child[a], i));
+  return m + (N.kind == TNode::DECISION && N.p == i);
+}
+
+int launch_apply(nfsp_mccfr* h, const ExTables& T, int walked) {
+  ApplyArgs A{};
+  A.legal = T.legal;
+  A.cfg = h->dev_cfg;
+  A.state = h->state;
+  A.tabs = h->tabs;
+  A.counts = h->counts;
+  A.ndec = h->ndec;
+  A.walked = walked;
+  k_mccfr_apply<<<dim3(nfsp_blocks(3 * (int64_t)h->ndec, 256), h->n), 256, 0, h->ctx->stream>>>(A);
+  NFSP_LAUNCHED("k_mccfr_apply");
+  return NFSP_OK;
+}
+
+}  // namespace
+
+extern "C" int nfsp_mccfr_cfgs_check(int game, const nfsp_mccfr_cfg* cfgs, int n, int64_t iters) {
+  NFSP_REQUIRE(cfgs, "null argument");
+  NFSP_REQUIRE(n >= 1 && n <= NFSP_MCCFR_MAX_RUNS, "n must be in 1 .. NFSP_MCCFR_MAX_RUNS");
+  NFSP_REQUIRE(iters >= 0, "iters must be >= 0");
+  const HostTables* H = nullptr;
+  const int rc = host_tables(game, &H);
+  if (rc != NFSP_OK) return rc;
+  float maxpay = 1.f;                     // max|pay| of the game's table (taken as at least a chip)
+  for (float p : H->pay) maxpay = std::max(maxpay, p < 0 ? -p : p);
+  // an entry moves by at most 2 max|pay| Q per traversal: keep W x iterations x that <= 2^62
+  const int64_t bound = (int64_t)((double)(1ll << 62) / (Q * 2.0 * (double)maxpay));
+  for (int k = 0; k < n; ++k) {
+    const nfsp_mccfr_cfg& c = cfgs[k];
+    NFSP_REQUIRE(c.walkers >= 2 && c.walkers <= NFSP_MCCFR_MAX_WALKERS,
+                 "nfsp_mccfr_cfg.walkers must be in 2 .. NFSP_MCCFR_MAX_WALKERS");
+    NFSP_REQUIRE(c.walkers % 2 == 0, "nfsp_mccfr_cfg.walkers must be even (one dealer each in turn)");
+    NFSP_REQUIRE(c.reserved == 0, "nfsp_mccfr_cfg.reserved must be 0");
+    if (iters > bound / c.walkers) {
+      char msg[200];
+      snprintf(msg, sizeof msg,
+               "overflow: walkers x iterations = %d x %lld would pass the bound %lld (2^62 / (2^24 x 2 max|pay|), "
+               "max|pay| = %g chips)", c.walkers, (long long)iters, (long long)bound, (double)maxpay);
+      return nfsp::fail(NFSP_EINVAL, msg);
+    }
+  }
+  return NFSP_OK;
+}
+
+// Checks that need no handle or device come first, so that every rule answers without a GPU.
+extern "C" int nfsp_mccfr_create(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, int n, nfsp_mccfr** out) {
+  NFSP_REQUIRE(cfgs && out, "null argument");
+  NFSP_REQUIRE(n >= 1 && n <= NFSP_MCCFR_MAX_RUNS, "n must be in 1 .. NFSP_MCCFR_MAX_RUNS");
+  NFSP_REQUIRE(ctx, "null argument");
+  int rc = nfsp_mccfr_cfgs_check(ctx->game, cfgs, n, 0);
+  if (rc != NFSP_OK) return rc;
+  const HostTables* H = nullptr;
+  rc = host_tables(ctx->game, &H);
+  if (rc != NFSP_OK) return rc;
+  for (int d = 0; d < 2; ++d)
+    for (int i = 0; i < 2; ++i)
+      NFSP_REQUIRE(frames_below(*H, H->root[d], i) <= MAX_FRAMES, "a seat decides more than 4 times on a path");
+  const ExTables* T = nullptr;
+  rc = device_tables(ctx, &T);
+  if (rc != NFSP_OK) return rc;
+  const int nterm = (int)(H->pay.size() / 18);
+  NFSP_REQUIRE(walk_lds(T->nn, T->ndec, nterm) <= 64 * 1024, "MCCFR tables exceed 64 KB of LDS");
+  nfsp_mccfr* h = new nfsp_mccfr;
+  h->ctx = ctx;
+  h->ndec = T->ndec;
+  h->nterm = nterm;
+  h->n = n;
+  h->cfgs.assign(cfgs, cfgs + n);
+  for (int k = 0; k < n; ++k) h->max_walkers = std::max(h->max_walkers, (int)cfgs[k].walkers);
+  const size_t n9 = 9 * (size_t)h->ndec;
+  const size_t b_state = sizeof(long long) * 4 * n9 * n, b_counts = sizeof(unsigned long long) * 3 * n;
+  hipError_t e = hipMalloc(&h->state, b_state);
+  if (e == hipSuccess) e = hipMalloc(&h->tabs, sizeof(double) * 2 * n9 * n);
+  if (e == hipSuccess) e = hipMalloc(&h->counts, b_counts);
+  if (e == hipSuccess) e = hipMalloc(&h->dev_cfg, sizeof(nfsp_mccfr_cfg) * n);
+  if (e == hipSuccess) e = hipMemsetAsync(h->state, 0, b_state, ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(h->counts, 0, b_counts, ctx->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(h->dev_cfg, h->cfgs.data(), sizeof(nfsp_mccfr_cfg) * n, hipMemcpyHostToDevice, ctx->stream);
+  if (e != hipSuccess) {
+    (void)nfsp_mccfr_destroy(h);
+    return nfsp::hip_fail(e, "nfsp_mccfr_create");
+  }
+  rc = launch_apply(h, *T, 0);            // sigma and the average before any iteration: uniform
+  if (rc == NFSP_OK && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess)
+    rc = nfsp::hip_fail(e, "nfsp_mccfr_create");
+  if (rc != NFSP_OK) {
+    (void)nfsp_mccfr_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_mccfr_run(nfsp_mccfr* h, int64_t iters) {
+  NFSP_REQUIRE(iters >= 0, "iters must be >= 0");
+  NFSP_REQUIRE(h, "null argument");
+  NFSP_REQUIRE(iters <= INT64_MAX - h->iterations, "overflow: iters too large");
+  int rc = nfsp_mccfr_cfgs_check(h->ctx->game, h->cfgs.data(), h->n, h->iterations + iters);
+  if (rc != NFSP_OK) return rc;
+  const ExTables* T = nullptr;
+  rc = device_tables(h->ctx, &T);
+  if (rc != NFSP_OK) return rc;
+  const dim3 grid(nfsp_blocks(h->max_walkers, NFSP_MCCFR_WG_WALKERS), h->n);
+  const size_t lds = walk_lds(T->nn, T->ndec, h->nterm);
+  for (int64_t it = 0; it < iters; ++it) {
+    for (int i = 0; i < 2; ++i) {
+      const uint64_t hh = 2 * (uint64_t)h->iterations + i;
+      WalkArgs A{};
+      A.T = *T;
+      A.cfg = h->dev_cfg;
+      A.tabs = h->tabs;
+      A.state = h->state;
+      A.counts = h->counts;
+      A.h_lo = (uint32_t)hh;
+      A.h_hi = (uint32_t)(hh >> 32);
+      A.seat = i;
+      A.nterm = h->nterm;
+      k_mccfr_walk<<<grid, WALK_THREADS, lds, h->ctx->stream>>>(A);
+      NFSP_LAUNCHED("k_mccfr_walk");
+      rc = launch_apply(h, *T, 1);
+      if (rc != NFSP_OK) return rc;
+    }
+    h->iterations += 1;
+  }
+  NFSP_HIP(hipStreamSynchronize(h->ctx->stream));
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_mccfr_iterations(nfsp_mccfr* h, int64_t* out) {
+  NFSP_REQUIRE(h && out, "null argument");
+  *out = h->iterations;
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_mccfr_counts(nfsp_mccfr* h, int run, int64_t* out) {
+  NFSP_REQUIRE(run >= 0, "run out of range");
+  NFSP_REQUIRE(h && out, "null argument");
+  NFSP_REQUIRE(run < h->n, "run out of range");
+  NFSP_HIP(hipMemcpyAsync(out, h->counts + 3 * (size_t)run, 2 * sizeof(int64_t), hipMemcpyDeviceToHost,
+                          h->ctx->stream));
+  NFSP_HIP(hipStreamSynchronize(h->ctx->stream));
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_mccfr_average(nfsp_mccfr* h, int run, const double** dev_table) {
+  NFSP_REQUIRE(run >= 0, "run out of range");
+  NFSP_REQUIRE(h && dev_table, "null argument");
+  NFSP_REQUIRE(run < h->n, "run out of range");
+  *dev_table = h->tabs + ((size_t)run * 2 + 1) * 9 * (size_t)h->ndec;
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_mccfr_state(nfsp_mccfr* h, int run, int64_t* host_R, int64_t* host_S) {
+  NFSP_REQUIRE(run >= 0, "run out of range");
+  NFSP_REQUIRE(h && host_R && host_S, "null argument");
+  NFSP_REQUIRE(run < h->n, "run out of range");
+  const size_t n9 = 9 * (size_t)h->ndec;
+  const long long* s = h->state + (size_t)run * 4 * n9;
+  NFSP_HIP(hipMemcpyAsync(host_R, s, sizeof(int64_t) * n9, hipMemcpyDeviceToHost, h->ctx->stream));
+  NFSP_HIP(hipMemcpyAsync(host_S, s + n9, sizeof(int64_t) * n9, hipMemcpyDeviceToHost, h->ctx->stream));
+  NFSP_HIP(hipStreamSynchronize(h->ctx->stream));
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_mccfr_destroy(nfsp_mccfr* h) {
+  NFSP_REQUIRE(h, "null argument");
+  if (h->state) (void)hipFree(h->state);
+  if (h->tabs) (void)hipFree(h->tabs);
+  if (h->counts) (void)hipFree(h->counts);
+  if (h->dev_cfg) (void)hipFree(h->dev_cfg);
+  delete h;
+  return NFSP_OK;
+}

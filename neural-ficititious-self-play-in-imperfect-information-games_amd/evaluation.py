@@ -11,8 +11,8 @@ policy the project meets, on the same public tree and with the same f64 walk
                             the reference left commented out (main.py:82-120);
 * ``Policy.table(t)``       a behavioural strategy ``[ndec][3 ranks][3 actions]`` over the rows of
                             ``GameTree``: a net read out with ``policy_table``, a ``mix`` of
-                            tables, a ``CfrSolver`` or ``XfpSolver`` average, a ``best_response``,
-                            anything written by hand.
+                            tables, a ``CfrSolver``, ``XfpSolver`` or ``MccfrSolver`` average, a
+                            ``best_response``, anything written by hand.
 
 ``best_response`` (``nfsp_best_response_table``) gives the exact best responses the scores
 are the values of as a table, with the exact action values at every information set: where a
@@ -22,7 +22,9 @@ learned BR net deviates, and by how much.
 (``nfsp_cfr_*``, csrc/cfr.hip), which anchors the Leduc variant the way the analytic Nash
 family anchors Kuhn.  ``XfpSolver`` runs full-width fictitious play on it (``nfsp_xfp_*``,
 csrc/xfp.hip), n runs over eta and the weighting at once: the curve of the algorithm NFSP
-approximates, with an exact best response and exact averaging.
+approximates, with an exact best response and exact averaging.  ``MccfrSolver`` runs
+external-sampling MCCFR on it (``nfsp_mccfr_*``, csrc/mccfr.hip): the sampled tabular yardstick,
+counted in traversals and terminals visited, to set beside the engine's curves in hands.
 
 ``MemoryTable`` is a memory counted per information set on the device (``nfsp_memory_table``,
 csrc/memtab.hip): M_SL as the tabular average strategy the AR net is a fit of, M_RL as what the
@@ -707,7 +709,7 @@ def q_report_from(tree: GameTree, seat: int, beta, q, reach, head, td, linear: b
 
 
 class _Solver(native.Handle):
-    """What the two solvers share: the tree, a device table read to the host, the handle's release."""
+    """What the solvers share: the tree, a device table read to the host, the handle's release."""
     DESTROY = None
 
     def __init__(self, ctx):
@@ -774,6 +776,58 @@ class XfpSolver(_Solver):
         native.check(self.ctx.L.nfsp_xfp_state(self.h, int(run), S.ctypes.data_as(native.P),
                                                B.ctypes.data_as(native.P), C.byref(W)), "nfsp_xfp_state")
         return S, B, W.value
+
+
+class MccfrSolver(_Solver):
+    """External-sampling MCCFR on the evaluator's tree (``nfsp_mccfr_*``): the sampled tabular
+    yardstick, counted in traversals and terminals visited.  ``cfgs`` is one ``(seed, walkers)``
+    per independent run; all runs advance together.  ``run(n)`` continues them by n iterations
+    (each one half-iteration of ``walkers`` traversals per seat), ``counts(k)`` is run k's
+    (traversals, terminals visited), ``average(k)`` its average strategy as a ``Policy`` and
+    ``state(k)`` its int64 fixed-point tables (``native.MCCFR_Q`` per chip / per unit)."""
+
+    DESTROY = "nfsp_mccfr_destroy"
+
+    def __init__(self, ctx, cfgs=((1, 1024),)):
+        super().__init__(ctx)
+        self.cfgs = [(int(seed) & (2**64 - 1), int(w)) for seed, w in cfgs]
+        self.n = len(self.cfgs)
+        arr = (native.MccfrCfg * max(self.n, 1))(*[native.MccfrCfg(seed, w, 0) for seed, w in self.cfgs])
+        h = native.P()
+        native.check(ctx.L.nfsp_mccfr_create(ctx.h, arr, self.n, C.byref(h)), "nfsp_mccfr_create")
+        self.h = h
+
+    def run(self, iters: int) -> "MccfrSolver":
+        native.check(self.ctx.L.nfsp_mccfr_run(self.h, int(iters)), "nfsp_mccfr_run")
+        return self
+
+    @property
+    def iterations(self) -> int:
+        n = native.I64(0)
+        native.check(self.ctx.L.nfsp_mccfr_iterations(self.h, C.byref(n)), "nfsp_mccfr_iterations")
+        return n.value
+
+    def counts(self, run: int = 0) -> tuple:
+        """(traversals, terminals visited) of a run."""
+        out = (native.I64 * 2)()
+        native.check(self.ctx.L.nfsp_mccfr_counts(self.h, int(run), out), "nfsp_mccfr_counts")
+        return int(out[0]), int(out[1])
+
+    def average(self, run: int = 0) -> Policy:
+        p = native.P()
+        native.check(self.ctx.L.nfsp_mccfr_average(self.h, int(run), C.byref(p)), "nfsp_mccfr_average")
+        return Policy(native.POL_TABLE, None, p.value, self)
+
+    def average_table(self, run: int = 0) -> np.ndarray:
+        return self._host_table(self.average(run))
+
+    def state(self, run: int = 0) -> tuple:
+        """(R, S) of a run: the regrets and the strategy sums, int64 ``[ndec, 3, 3]`` each."""
+        R = np.zeros((self.tree.ndec, 3, 3), np.int64)
+        S = np.zeros((self.tree.ndec, 3, 3), np.int64)
+        native.check(self.ctx.L.nfsp_mccfr_state(self.h, int(run), R.ctypes.data_as(native.P),
+                                                 S.ctypes.data_as(native.P)), "nfsp_mccfr_state")
+        return R, S
 
 
 class CfrSolver(_Solver):

@@ -99,6 +99,11 @@ class XfpCfg(C.Structure):
     _fields_ = [("eta", C.c_double), ("weight", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MccfrCfg(C.Structure):
+    """``nfsp_mccfr_cfg``: one external-sampling MCCFR run's seed and walkers per half-iteration"""
+    _fields_ = [("seed", C.c_uint64), ("walkers", C.c_int32), ("reserved", C.c_int32)]
+
+
 class MemSegment(C.Structure):
     """``nfsp_mem_segment``: n packed records (SlRec 16 B / RlRec 32 B) at a device address"""
     _fields_ = [("dev_recs", P), ("n", I64)]
@@ -181,6 +186,14 @@ SIGNATURES = {
     "nfsp_xfp_average": (I32, [P, I32, C.POINTER(P)]),
     "nfsp_xfp_state": (I32, [P, I32, P, P, C.POINTER(F64)]),
     "nfsp_xfp_destroy": (I32, [P]),
+    "nfsp_mccfr_cfgs_check": (I32, [I32, C.POINTER(MccfrCfg), I32, I64]),
+    "nfsp_mccfr_create": (I32, [P, C.POINTER(MccfrCfg), I32, C.POINTER(P)]),
+    "nfsp_mccfr_run": (I32, [P, I64]),
+    "nfsp_mccfr_iterations": (I32, [P, C.POINTER(I64)]),
+    "nfsp_mccfr_counts": (I32, [P, I32, C.POINTER(I64)]),
+    "nfsp_mccfr_average": (I32, [P, I32, C.POINTER(P)]),
+    "nfsp_mccfr_state": (I32, [P, I32, P, P]),
+    "nfsp_mccfr_destroy": (I32, [P]),
     "nfsp_engine_set_loss_log": (I32, [P, I32]),
     "nfsp_engine_losses": (I32, [P, P]),
     "nfsp_engine_set_timing": (I32, [P, I32]),
@@ -258,6 +271,12 @@ CFR_LAUNCH_ITERS = 1024
 XFP_WEIGHT_UNIFORM, XFP_WEIGHT_LINEAR = 0, 1
 XFP_LAUNCH_ITERS = 1024
 XFP_MAX_RUNS = 1024
+# external-sampling MCCFR (NFSP_MCCFR_*): the fixed point of R and S, the most runs of a handle, the
+# most walkers of a run and the traversals of one workgroup
+MCCFR_Q = 1 << 24
+MCCFR_MAX_RUNS = 64
+MCCFR_MAX_WALKERS = 1 << 22
+MCCFR_WG_WALKERS = 1024
 # the memories as tables (NFSP_MEM_*, NFSP_MEMTAB_*)
 MEM_SL, MEM_RL, MEM_TD, MEM_TDQ = 0, 1, 2, 3
 # what nfsp_table_rows makes of a table (NFSP_ROWS_*), and the most sweeps and tables of a call

@@ -7,6 +7,8 @@ csrc/xfp.hip): the algorithm NFSP approximates, with an exact best response and 
     python tools/solve_game.py --game leduc --iters 4096 --out eq.npz
     python tools/solve_game.py --game leduc --solver xfp --weight linear --eta 0.1 --iters 4096
     python tools/solve_game.py --game leduc --solver xfp --eta 0.5 --runs 64 --every 1024
+    python tools/solve_game.py --game leduc --solver mccfr --walkers 1024 --seeds 4 --iters 32768
+    python tools/solve_game.py --solver mccfr --time
 
 eq.npz holds ``table`` [ndec, 3 ranks, 3 actions] (rows as evaluation.GameTree's; usable as
 evaluation.Policy.table), ``game``, and per checkpoint (--every, doubling by default)
@@ -20,6 +22,13 @@ solver's milliseconds per iteration.
 runs N independent runs in the one launch, eta evenly spaced over [0, --eta]; the fields above
 are then the last run's (eta = --eta), ``eta_runs`` / ``exploitability_runs`` list every run's,
 and eq.npz also holds ``tables`` [N, ndec, 3, 3].  The milliseconds are the whole handle's.
+
+--solver mccfr: external-sampling MCCFR (evaluation.MccfrSolver, csrc/mccfr.hip), the sampled
+tabular yardstick.  --walkers W traversals per seat and iteration, --seeds K independent runs
+(seeds 1 .. K) in the one handle.  Its cost is counted in ``traversals`` and ``terminals``
+visited, which each checkpoint's line carries beside ``exploitability_runs``; the fields above
+are the first seed's.  --time instead reports traversals/s and terminals/s for Leduc at
+W = 2^20: one iteration timed with HIP events on the solver's stream, best of 5 after a warm-up.
 """
 import argparse
 import json
@@ -33,24 +42,59 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 
+def time_mccfr(ev, nat, walkers=1 << 20, repeats=5):
+    """Best of ``repeats`` single iterations (2 W traversals each) after a warm-up."""
+    import torch
+    ctx = nat.Context(1, game=nat.GAME_LEDUC)
+    solver = ev.MccfrSolver(ctx, [(1, walkers)]).run(1)
+    best = None
+    for _ in range(repeats):
+        before = solver.counts(0)
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        solver.run(1)
+        t1.record()
+        t1.synchronize()
+        ms = t0.elapsed_time(t1)
+        after = solver.counts(0)
+        rec = {"ms": ms, "traversals": after[0] - before[0], "terminals": after[1] - before[1]}
+        if best is None or ms < best["ms"]:
+            best = rec
+    best.update(game="leduc", solver="mccfr", walkers=walkers, repeats=repeats,
+                traversals_per_s=best["traversals"] / (best["ms"] * 1e-3),
+                terminals_per_s=best["terminals"] / (best["ms"] * 1e-3))
+    print(json.dumps(best), flush=True)
+    solver.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--game", default="leduc", choices=["leduc", "kuhn"])
-    ap.add_argument("--solver", default="cfr", choices=["cfr", "xfp"])
+    ap.add_argument("--solver", default="cfr", choices=["cfr", "xfp", "mccfr"])
     ap.add_argument("--iters", type=int, default=1024)
     ap.add_argument("--every", type=int, default=0, help="checkpoint every K iterations (default: 1, 2, 4, ...)")
     ap.add_argument("--eta", type=float, default=0.0, help="xfp: anticipatory parameter, in [0, 1)")
     ap.add_argument("--weight", default="uniform", choices=["uniform", "linear"], help="xfp: averaging weights")
     ap.add_argument("--runs", type=int, default=1, help="xfp: runs in one launch, eta spaced over [0, --eta]")
+    ap.add_argument("--walkers", type=int, default=1024, help="mccfr: traversals per seat and iteration (even)")
+    ap.add_argument("--seeds", type=int, default=1, help="mccfr: independent runs, seeds 1 .. K")
+    ap.add_argument("--time", action="store_true", help="mccfr: traversals/s and terminals/s, Leduc at W = 2^20")
     ap.add_argument("--out", default=None, metavar="PATH")
     args = ap.parse_args()
     import __graft_entry__
     pkg = __graft_entry__.load_package()
     ev, nat = pkg.evaluation, pkg.native
     game = nat.GAME_KUHN if args.game == "kuhn" else nat.GAME_LEDUC
+    if args.time:
+        if args.solver != "mccfr":
+            ap.error("--time is for --solver mccfr")
+        return time_mccfr(ev, nat)
     ctx = nat.Context(1, game=game)
     xfp = args.solver == "xfp"
-    if xfp:
+    mccfr = args.solver == "mccfr"
+    if mccfr:
+        solver = ev.MccfrSolver(ctx, [(seed, args.walkers) for seed in range(1, args.seeds + 1)])
+    elif xfp:
         etas = [args.eta] if args.runs == 1 else [float(e) for e in np.linspace(0.0, args.eta, args.runs)]
         solver = ev.XfpSolver(ctx, [(e, args.weight) for e in etas])
     else:
@@ -63,7 +107,11 @@ def main():
         solver.run(nxt - done)
         ms = (time.perf_counter() - t0) * 1e3 / (nxt - done)
         done = nxt
-        if xfp:
+        if mccfr:
+            avgs = [solver.average(k) for k in range(solver.n)]
+            res = ev.evaluate_batch(ctx, [(a, a) for a in avgs])
+            r = res[0]
+        elif xfp:
             avgs = [solver.average(k) for k in range(len(etas))]
             res = ev.evaluate_batch(ctx, [(a, a) for a in avgs])
             r = res[-1]
@@ -73,6 +121,10 @@ def main():
         rec = {"game": args.game, "iterations": done, "exploitability": r["exploitability"], "br0": r["br0"],
                "br1": r["br1"], "value0": r["value0"],
                "value0_dealer": [r["value0_dealer0"], r["value0_dealer1"]], "ms_per_iteration": ms}
+        if mccfr:
+            counts = [solver.counts(k) for k in range(solver.n)]
+            rec.update(solver="mccfr", walkers=args.walkers, traversals=counts[0][0],
+                       terminals=[c[1] for c in counts], exploitability_runs=[x["exploitability"] for x in res])
         if xfp:
             rec.update(solver="xfp", weight=args.weight, eta=etas[-1])
             if len(etas) > 1:
@@ -81,6 +133,10 @@ def main():
         print(json.dumps(rec), flush=True)
     if args.out:
         extra = {}
+        if mccfr:
+            extra = {"tables": np.stack([solver.average_table(k) for k in range(solver.n)]),
+                     "traversals": np.array([r["traversals"] for r in rows]),
+                     "terminals": np.array([r["terminals"] for r in rows])}
         if xfp:
             extra = {"tables": np.stack([solver.average_table(k) for k in range(len(etas))]), "eta": np.array(etas),
                      "weight": args.weight}
