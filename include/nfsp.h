@@ -798,6 +798,62 @@ int nfsp_mccfr_average(nfsp_mccfr* h, int run, const double** dev_table);
 int nfsp_mccfr_state(nfsp_mccfr* h, int run, int64_t* host_R /*[ndec][3][3]*/, int64_t* host_S /*[ndec][3][3]*/);
 int nfsp_mccfr_destroy(nfsp_mccfr* h);
 
+/* ---- outcome-sampling MCCFR on the same handle (csrc/mccfr.hip k_mccfr_os_walk, k_mccfr_apply) ----
+ * OS-MCCFR (the same paper): one traversal is one sampled hand and one terminal, the regret-
+ * minimising tabular learner that consumes exactly what NFSP consumes, a trajectory per sample --
+ * the rung of the ladder counted in the engine's own unit, hands.
+ * A run has a seed, W walkers (even) and an exploration rate epsilon.  R, S, t and NFSP_MCCFR_Q,
+ * step 1 (sigma from R by plain regret matching, frozen for the half-iteration), step 3 and
+ * k_mccfr_apply, the draw u(node), the choice rule, the dealer w & 1 and the deal at the
+ * pseudo-node nn are exactly external sampling's, above.  Step 2 for walker w of half-iteration
+ * h = 2 t + i is one path; all f64, no FMA contraction, the operations in the order written:
+ *   start with q = 1.0;
+ *   chance               the child chosen by u(n) over p_public(c, r_0, r_1), c ascending;
+ *   the opponent's       winv = Q / q (one division); for each a,
+ *   decision             dS[row][r_o][a] += llrint(sigma_a * winv); then the child chosen by u(n)
+ *                        over sigma[row][r_o];
+ *   seat i's decision,   xi_a = eps / (double)L + (1.0 - eps) * sigma_a for the legal a, 0 at an
+ *   L legal actions      illegal raise; a* = choice(xi, u(n)); push the frame (row, a*);
+ *                        q = q * xi_{a*}; go to child a*;
+ *   terminal             c = (double)pay[row][i][r_i][r_o] / q and x = 1.0;
+ *   then the frames, deepest first:
+ *                        s = sigma[row][r_i][a*] and g = c * x; for the legal a ascending,
+ *                        dR[row][r_i][a] += llrint((g * (1.0 - s)) * Q) if a == a*,
+ *                        dR[row][r_i][a] += llrint((-(g * s)) * Q) otherwise; then x = x * s.
+ * The standard estimator with chance and the opponent sampled on-policy: their probabilities
+ * cancel, and only seat i's sampling product q remains.  The average is the "simple" one external
+ * sampling uses, at the opponent's nodes, with 1 / q undoing seat i's exploration above the node.
+ * Traversals are 2 W t and terminals visited are 2 W t: equal by construction.
+ * Overflow.  Let omega(game, eps) be the largest, over both seats and all root-to-terminal paths,
+ * of the product of L_k / eps over that seat's decisions on the path (in doubles: from 1.0,
+ * times ((double)L_k / eps) from the root down; computed on the host from the tree, not taken as
+ * (3 / eps)^4).  1 / q <= omega, so per traversal an R entry moves by at most max|pay| omega Q and
+ * an S entry by at most omega Q, and a run is refused when
+ *   W x iterations > floor(2^62 / ((Q x max(max|pay|, 1)) x omega)),
+ * the message naming the bound.  This is a worst-case bound and it is tight on budget: Leduc
+ * (omega = 36 / eps^4, max|pay| = 5) at eps = 0.6 allows 197,912,092 walker-iterations, at
+ * eps = 0.0625 23,301; Kuhn (omega = 6 / eps^2, max|pay| = 2) 8,246,337,208 and 89,478,485.
+ * There is one NFSP_MCCFR_Q; small eps costs budget, not a second fixed point.
+ * epsilon must lie in [NFSP_MCCFR_OS_EPS_MIN, 1]; NaN is refused.
+ * A lane runs one path: the frames are packed into one 64-bit scalar (no scratch), sigma is
+ * re-read from LDS by row on the way back, and the one pay entry of a traversal is read from
+ * device memory, so the workgroup's LDS holds sigma, dR, dS and the node table only.
+ * tests/mccfr_os_ref.py restates the rule in numpy, and R, S and the counts agree to the bit. */
+#define NFSP_MCCFR_OS_EPS_MIN 0.0625
+typedef struct {
+  uint64_t seed;
+  int32_t walkers;                      /* W: even, 2 .. NFSP_MCCFR_MAX_WALKERS */
+  int32_t reserved;                     /* 0 */
+  double epsilon;                       /* in [NFSP_MCCFR_OS_EPS_MIN, 1] */
+} nfsp_mccfr_os_cfg;                    /* 24 bytes */
+/* Host only, as nfsp_mccfr_cfgs_check, with outcome sampling's fields and overflow bound. */
+int nfsp_mccfr_os_cfgs_check(int game, const nfsp_mccfr_os_cfg* cfgs /*[n]*/, int n, int64_t iters);
+/* The handle is an nfsp_mccfr: nfsp_mccfr_run / _iterations / _counts / _average / _state /
+ * _destroy serve it unchanged, and run re-checks outcome sampling's own bound. */
+int nfsp_mccfr_os_create(nfsp_ctx* ctx, const nfsp_mccfr_os_cfg* cfgs /*[n]*/, int n, nfsp_mccfr** out);
+/* out: 0 external sampling (nfsp_mccfr_create), 1 outcome sampling (nfsp_mccfr_os_create). */
+int nfsp_mccfr_sampling(nfsp_mccfr* h, int* out);
+
 /* ---- the memories as tables (csrc/memtab.hip k_memtab, k_memtab_sum) ----
  * M_SL (utils/ReservoirBuffer.py:18-28) and M_RL (utils/replay_buffer.py:30-41) counted per
  * information set where they lie, from the packed device records (SlRec 16 B {obs bits, a[3]},

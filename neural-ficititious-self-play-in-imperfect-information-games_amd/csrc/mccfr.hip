@@ -21,6 +21,14 @@
 //                  depend on the grid or on the order of arrival.
 //   k_mccfr_apply  R += dR, S += dS, the deltas zeroed, the next sigma (regret matching on R+;
 //                  R itself is not floored), the average of S, the counts.
+// Outcome sampling (nfsp_mccfr_os_*, the same handle) swaps the walk for
+//   k_mccfr_os_walk  the same grid, lane-to-walker mapping, LDS tables and flush.  A traversal is
+//                  one sampled hand: a straight path down (seat i samples its own action from
+//                  eps uniform + (1 - eps) sigma and carries the product q of what it sampled with),
+//                  one terminal, then the path's frames back, deepest first, with importance
+//                  weights 1 / q.  The frames are 16 bits each in one 64-bit scalar, sigma is
+//                  re-read from LDS by row, and the one pay entry comes from device memory, so pay
+//                  is not staged (Leduc: 36,824 B of LDS, four workgroups to a CU).
 // No workgroup waits for another -- no flags, no tickets, no spinning: the stream orders the
 // launches, and nfsp_mccfr_run synchronises once at its end.
 // All f64 arithmetic is in tree_walk.h's style (no FMA contraction, the sums ascending).
@@ -39,6 +47,10 @@ struct nfsp_mccfr {
   double* tabs = nullptr;                 // per run sigma | average, [ndec][3][3] each
   unsigned long long* counts = nullptr;   // per run traversals, terminals, terminals of the walk in flight
   nfsp_mccfr_cfg* dev_cfg = nullptr;      // [n]
+  int sampling = 0;                       // 0 external, 1 outcome
+  std::vector<nfsp_mccfr_os_cfg> os_cfgs; // outcome sampling: the cfgs as given (cfgs holds their seed and walkers)
+  std::vector<double> eps;                // outcome sampling: [n][3] epsilon, epsilon / 2.0, epsilon / 3.0
+  double* dev_eps = nullptr;              // eps on the device
 };
 
 namespace {
@@ -111,7 +123,7 @@ __device__ __forceinline__ int choose3(double p0, double p1, double p2, double u
 }
 
 __device__ __forceinline__ void add_fixed(unsigned long long* p, double x) {
-  const long long v = (long long)__builtin_rint(x);    // llrint: |x| <= 2 max|pay| Q, far inside int64
+  const long long v = (long long)__builtin_rint(x);    // llrint: |x| <= 2 max|pay| Q (omega max|pay| Q), far inside int64
   if (v != 0) atomicAdd(p, (unsigned long long)v);
 }
 
@@ -246,6 +258,167 @@ __global__ void __launch_bounds__(WALK_THREADS) k_mccfr_walk(WalkArgs A) {
     __hip_atomic_fetch_add(A.counts + (size_t)run * 3 + 2, *terms, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+struct OsArgs {
+  ExTables T;
+  const nfsp_mccfr_cfg* cfg;              // [n]
+  const double* eps;                      // [n][3]: epsilon, epsilon / 2.0, epsilon / 3.0 (divided on the host)
+  const double* tabs;
+  long long* state;
+  unsigned long long* counts;
+  uint32_t h_lo, h_hi;
+  int seat;
+};
+
+// dynamic LDS of the outcome-sampling walk: as walk_lds without pay
+__host__ __device__ inline size_t os_lds(int nn, int ndec) {
+  return 8 * ((size_t)ndec * 27 + 1) + sizeof(DevNode) * (size_t)nn;
+}
+
+// A frame of the path, 16 bits: row << 3 | raise legal << 2 | a*.  MAX_FRAMES of them are one
+// 64-bit scalar, the deepest in the low bits (nfsp_mccfr_os_create checks the rows fit).
+constexpr int FRAME_BITS = 16;
+constexpr int FRAME_MAX_ROWS = 1 << (FRAME_BITS - 3);
+static_assert(MAX_FRAMES * FRAME_BITS <= 64, "the frames of a path are one scalar");
+
+// Outcome sampling: the grid, the lane-to-walker mapping, the LDS tables and the flush are
+// k_mccfr_walk's; a traversal is one path down (nlev steps at most) and its frames back
+// (MAX_FRAMES at most).  Two kinds of division: Q / q at an opponent's node, pay / q at the end.
+// The staging, the deal and the flush are written out again here: shared with k_mccfr_walk as
+// inlined helpers they moved that kernel's registers (91 -> 94 VGPRs), and its code is to stay
+// the parent's, instruction for instruction (profiles/mccfr/resources_os.txt).
+__global__ void __launch_bounds__(WALK_THREADS) k_mccfr_os_walk(OsArgs A) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const ExTables& T = A.T;
+  const int run = blockIdx.y;
+  const int W = A.cfg[run].walkers;
+  const int w0 = blockIdx.x * NFSP_MCCFR_WG_WALKERS;
+  if (w0 >= W) return;
+  const int nn = T.nn, n9 = T.ndec * 9;
+  double* sg = reinterpret_cast<double*>(smem_raw);
+  unsigned long long* dR = reinterpret_cast<unsigned long long*>(sg + n9);
+  unsigned long long* dS = dR + n9;
+  unsigned long long* terms = dS + n9;
+  DevNode* nodes = reinterpret_cast<DevNode*>(terms + 1);
+  const int tid = threadIdx.x;
+  const double* gsg = A.tabs + (size_t)run * 2 * n9;
+  for (int k = tid; k < n9; k += WALK_THREADS) {
+    sg[k] = gsg[k];
+    dR[k] = 0;
+    dS[k] = 0;
+  }
+  if (tid == 0) *terms = 0;
+  for (int k = tid; k < nn; k += WALK_THREADS) nodes[k] = T.nodes[k];
+  __syncthreads();
+
+  Walker X;
+  X.sg = sg;
+  X.nodes = nodes;
+  X.pay = T.pay + A.seat * 9;             // device memory: a traversal reads one entry
+  X.dR = dR;
+  X.dS = dS;
+  X.h_lo = A.h_lo;
+  X.h_hi = A.h_hi;
+  X.k0 = (uint32_t)A.cfg[run].seed;
+  X.k1 = (uint32_t)(A.cfg[run].seed >> 32);
+  X.i = A.seat;
+  X.nlev = T.nlev;
+  X.terminals = 0;
+  const double eps = A.eps[run * 3], eps2 = A.eps[run * 3 + 1], eps3 = A.eps[run * 3 + 2];
+  const double keep = 1.0 - eps;
+  for (int k = 0; k < NFSP_MCCFR_WG_WALKERS / WALK_THREADS; ++k) {
+    const int w = w0 + k * WALK_THREADS + tid;
+    if (w >= W) continue;
+    X.w = (uint32_t)w;
+    const double ud = draw(X, nn);
+    double cd = 0.0;
+    int pick = -1, last = -1;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) choice_step(T.deal[j / 3][j % 3], j, ud, cd, pick, last);
+    const int j = pick >= 0 ? pick : last;
+    if (j < 0) continue;
+    X.ri = j / 3;
+    X.ro = j % 3;
+    // the path down
+    int n = T.root[w & 1], nf = 0, end = -1;
+    double q = 1.0;
+    uint64_t frames = 0;
+    for (int d = 0; d < X.nlev; ++d) {
+      const DevNode& N = X.nodes[n];
+      if (N.kind == TNode::TERMINAL) {
+        end = N.row;
+        break;
+      }
+      const double u = draw(X, n);
+      const bool own = N.kind == TNode::DECISION && N.p == X.i;
+      const bool l2 = N.child[2] >= 0;
+      double p0, p1, p2;
+      if (N.kind == TNode::CHANCE) {
+        const int r0 = X.i == 0 ? X.ri : X.ro, r1 = X.i == 0 ? X.ro : X.ri;
+        p0 = p_public(0, r0, r1);
+        p1 = p_public(1, r0, r1);
+        p2 = p_public(2, r0, r1);
+      } else {
+        const size_t row = (size_t)N.row * 9 + (own ? X.ri : X.ro) * 3;
+        p0 = X.sg[row + 0];
+        p1 = X.sg[row + 1];
+        p2 = X.sg[row + 2];
+        if (own) {
+          const double e = l2 ? eps3 : eps2;
+          p0 = e + keep * p0;
+          p1 = e + keep * p1;
+          p2 = l2 ? e + keep * p2 : 0.0;
+        } else {
+          const double winv = Q / q;
+          add_fixed(X.dS + row + 0, p0 * winv);
+          add_fixed(X.dS + row + 1, p1 * winv);
+          add_fixed(X.dS + row + 2, p2 * winv);
+        }
+      }
+      const int a = choose3(p0, p1, p2, u);
+      if (a < 0) break;                   // no positive probability: not a strategy
+      if (own) {
+        if (nf >= MAX_FRAMES) break;      // unreachable: nfsp_mccfr_os_create counted the frames
+        frames = frames << FRAME_BITS | (uint64_t)(N.row << 3 | (l2 ? 4 : 0) | a);
+        ++nf;
+        q = q * (a == 0 ? p0 : a == 1 ? p1 : p2);
+      }
+      n = N.child[a];
+      if (n < 0) break;
+    }
+    if (end < 0) continue;
+    ++X.terminals;
+    // the frames back, deepest first
+    const double c = (double)X.pay[(size_t)end * 18 + X.ri * 3 + X.ro] / q;
+    double x = 1.0;
+    for (int f = 0; f < MAX_FRAMES; ++f) {
+      if (f >= nf) break;
+      const uint32_t fr = (uint32_t)frames & ((1u << FRAME_BITS) - 1);
+      frames >>= FRAME_BITS;
+      const int a = fr & 3;
+      const size_t row = (size_t)(fr >> 3) * 9 + X.ri * 3;
+      const double s = X.sg[row + a], g = c * x;
+      const double hit = (g * (1.0 - s)) * Q, miss = (-(g * s)) * Q;
+      add_fixed(X.dR + row + 0, a == 0 ? hit : miss);
+      add_fixed(X.dR + row + 1, a == 1 ? hit : miss);
+      if (fr & 4) add_fixed(X.dR + row + 2, a == 2 ? hit : miss);
+      x = x * s;
+    }
+  }
+  if (X.terminals) atomicAdd(terms, (unsigned long long)X.terminals);
+  __syncthreads();
+
+  long long* gd = A.state + ((size_t)run * 4 + 2) * n9;    // dR | dS, as in LDS
+  for (int k = tid; k < 2 * n9; k += WALK_THREADS) {
+    const unsigned long long v = dR[k];
+    if (v)
+      __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(gd) + k, v, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (tid == 0 && *terms)
+    __hip_atomic_fetch_add(A.counts + (size_t)run * 3 + 2, *terms, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // One thread per (row, rank) of a run.
 __global__ void __launch_bounds__(256) k_mccfr_apply(ApplyArgs A) {
 #pragma clang fp contract(off)
@@ -287,6 +460,17 @@ int frames_below(const HostTables& H, int n, int i) {
   int m = 0;
   for (int a = 0; a < 3; ++a) m = std::max(m, frames_below(H, N.child[a], i));
   return m + (N.kind == TNode::DECISION && N.p == i);
+}
+
+// The rule's omega: the largest product of L_k / eps over seat i's decisions on a path from n
+// down, w the product above n.  Every factor is >= 1, so the largest is at a terminal.
+double omega_below(const HostTables& H, int n, int i, double eps, double w) {
+  if (n < 0) return 0.0;
+  const DevNode& N = H.nodes[n];
+  if (N.kind == TNode::DECISION && N.p == i) w = w * ((double)N.nchild / eps);
+  double m = w;
+  for (int a = 0; a < 3; ++a) m = std::max(m, omega_below(H, N.child[a], i, eps, w));
+  return m;
 }
 
 int launch_apply(nfsp_mccfr* h, const ExTables& T, int walked) {
@@ -333,15 +517,47 @@ extern "C" int nfsp_mccfr_cfgs_check(int game, const nfsp_mccfr_cfg* cfgs, int n
   return NFSP_OK;
 }
 
-// Checks that need no handle or device come first, so that every rule answers without a GPU.
-extern "C" int nfsp_mccfr_create(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, int n, nfsp_mccfr** out) {
-  NFSP_REQUIRE(cfgs && out, "null argument");
+extern "C" int nfsp_mccfr_os_cfgs_check(int game, const nfsp_mccfr_os_cfg* cfgs, int n, int64_t iters) {
+  NFSP_REQUIRE(cfgs, "null argument");
   NFSP_REQUIRE(n >= 1 && n <= NFSP_MCCFR_MAX_RUNS, "n must be in 1 .. NFSP_MCCFR_MAX_RUNS");
-  NFSP_REQUIRE(ctx, "null argument");
-  int rc = nfsp_mccfr_cfgs_check(ctx->game, cfgs, n, 0);
-  if (rc != NFSP_OK) return rc;
+  NFSP_REQUIRE(iters >= 0, "iters must be >= 0");
   const HostTables* H = nullptr;
-  rc = host_tables(ctx->game, &H);
+  const int rc = host_tables(game, &H);
+  if (rc != NFSP_OK) return rc;
+  float maxpay = 1.f;
+  for (float p : H->pay) maxpay = std::max(maxpay, p < 0 ? -p : p);
+  for (int k = 0; k < n; ++k) {
+    const nfsp_mccfr_os_cfg& c = cfgs[k];
+    NFSP_REQUIRE(c.walkers >= 2 && c.walkers <= NFSP_MCCFR_MAX_WALKERS,
+                 "nfsp_mccfr_os_cfg.walkers must be in 2 .. NFSP_MCCFR_MAX_WALKERS");
+    NFSP_REQUIRE(c.walkers % 2 == 0, "nfsp_mccfr_os_cfg.walkers must be even (one dealer each in turn)");
+    NFSP_REQUIRE(c.reserved == 0, "nfsp_mccfr_os_cfg.reserved must be 0");
+    NFSP_REQUIRE(c.epsilon >= NFSP_MCCFR_OS_EPS_MIN && c.epsilon <= 1.0,       // false for a NaN
+                 "nfsp_mccfr_os_cfg.epsilon must be in NFSP_MCCFR_OS_EPS_MIN .. 1");
+    double omega = 1.0;
+    for (int d = 0; d < 2; ++d)
+      for (int i = 0; i < 2; ++i) omega = std::max(omega, omega_below(*H, H->root[d], i, c.epsilon, 1.0));
+    // per traversal an R entry moves by at most max|pay| omega Q, an S entry by at most omega Q
+    const int64_t bound = (int64_t)((double)(1ll << 62) / ((Q * (double)maxpay) * omega));
+    if (iters > bound / c.walkers) {
+      char msg[256];
+      snprintf(msg, sizeof msg,
+               "overflow: walkers x iterations = %d x %lld would pass the bound %lld (2^62 / (2^24 x max|pay| x omega), "
+               "max|pay| = %g chips, omega = %g at epsilon = %g)", c.walkers, (long long)iters, (long long)bound,
+               (double)maxpay, omega, c.epsilon);
+      return nfsp::fail(NFSP_EINVAL, msg);
+    }
+  }
+  return NFSP_OK;
+}
+
+namespace {
+
+// What both kinds of handle are made of, after their checks: cfgs holds every run's seed and
+// walkers; os is null for external sampling.
+int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os_cfg* os, int n, nfsp_mccfr** out) {
+  const HostTables* H = nullptr;
+  int rc = host_tables(ctx->game, &H);
   if (rc != NFSP_OK) return rc;
   for (int d = 0; d < 2; ++d)
     for (int i = 0; i < 2; ++i)
@@ -350,7 +566,12 @@ extern "C" int nfsp_mccfr_create(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, int 
   rc = device_tables(ctx, &T);
   if (rc != NFSP_OK) return rc;
   const int nterm = (int)(H->pay.size() / 18);
-  NFSP_REQUIRE(walk_lds(T->nn, T->ndec, nterm) <= 64 * 1024, "MCCFR tables exceed 64 KB of LDS");
+  if (os) {
+    NFSP_REQUIRE(os_lds(T->nn, T->ndec) <= 64 * 1024, "MCCFR tables exceed 64 KB of LDS");
+    NFSP_REQUIRE(T->ndec <= FRAME_MAX_ROWS, "a decision row does not fit a frame");
+  } else {
+    NFSP_REQUIRE(walk_lds(T->nn, T->ndec, nterm) <= 64 * 1024, "MCCFR tables exceed 64 KB of LDS");
+  }
   nfsp_mccfr* h = new nfsp_mccfr;
   h->ctx = ctx;
   h->ndec = T->ndec;
@@ -358,16 +579,25 @@ extern "C" int nfsp_mccfr_create(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, int 
   h->n = n;
   h->cfgs.assign(cfgs, cfgs + n);
   for (int k = 0; k < n; ++k) h->max_walkers = std::max(h->max_walkers, (int)cfgs[k].walkers);
+  std::vector<double>& eps = h->eps;
+  if (os) {
+    h->sampling = 1;
+    h->os_cfgs.assign(os, os + n);
+    for (int k = 0; k < n; ++k) eps.insert(eps.end(), {os[k].epsilon, os[k].epsilon / 2.0, os[k].epsilon / 3.0});
+  }
   const size_t n9 = 9 * (size_t)h->ndec;
   const size_t b_state = sizeof(long long) * 4 * n9 * n, b_counts = sizeof(unsigned long long) * 3 * n;
   hipError_t e = hipMalloc(&h->state, b_state);
   if (e == hipSuccess) e = hipMalloc(&h->tabs, sizeof(double) * 2 * n9 * n);
   if (e == hipSuccess) e = hipMalloc(&h->counts, b_counts);
   if (e == hipSuccess) e = hipMalloc(&h->dev_cfg, sizeof(nfsp_mccfr_cfg) * n);
+  if (e == hipSuccess && os) e = hipMalloc(&h->dev_eps, sizeof(double) * eps.size());
   if (e == hipSuccess) e = hipMemsetAsync(h->state, 0, b_state, ctx->stream);
   if (e == hipSuccess) e = hipMemsetAsync(h->counts, 0, b_counts, ctx->stream);
   if (e == hipSuccess)
     e = hipMemcpyAsync(h->dev_cfg, h->cfgs.data(), sizeof(nfsp_mccfr_cfg) * n, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess && os)
+    e = hipMemcpyAsync(h->dev_eps, eps.data(), sizeof(double) * eps.size(), hipMemcpyHostToDevice, ctx->stream);
   if (e != hipSuccess) {
     (void)nfsp_mccfr_destroy(h);
     return nfsp::hip_fail(e, "nfsp_mccfr_create");
@@ -383,32 +613,77 @@ extern "C" int nfsp_mccfr_create(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, int 
   return NFSP_OK;
 }
 
+}  // namespace
+
+// Checks that need no handle or device come first, so that every rule answers without a GPU.
+extern "C" int nfsp_mccfr_create(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, int n, nfsp_mccfr** out) {
+  NFSP_REQUIRE(cfgs && out, "null argument");
+  NFSP_REQUIRE(n >= 1 && n <= NFSP_MCCFR_MAX_RUNS, "n must be in 1 .. NFSP_MCCFR_MAX_RUNS");
+  NFSP_REQUIRE(ctx, "null argument");
+  const int rc = nfsp_mccfr_cfgs_check(ctx->game, cfgs, n, 0);
+  if (rc != NFSP_OK) return rc;
+  return create_handle(ctx, cfgs, nullptr, n, out);
+}
+
+extern "C" int nfsp_mccfr_os_create(nfsp_ctx* ctx, const nfsp_mccfr_os_cfg* cfgs, int n, nfsp_mccfr** out) {
+  NFSP_REQUIRE(cfgs && out, "null argument");
+  NFSP_REQUIRE(n >= 1 && n <= NFSP_MCCFR_MAX_RUNS, "n must be in 1 .. NFSP_MCCFR_MAX_RUNS");
+  NFSP_REQUIRE(ctx, "null argument");
+  const int rc = nfsp_mccfr_os_cfgs_check(ctx->game, cfgs, n, 0);
+  if (rc != NFSP_OK) return rc;
+  std::vector<nfsp_mccfr_cfg> plain(n);
+  for (int k = 0; k < n; ++k) plain[k] = nfsp_mccfr_cfg{cfgs[k].seed, cfgs[k].walkers, 0};
+  return create_handle(ctx, plain.data(), cfgs, n, out);
+}
+
+extern "C" int nfsp_mccfr_sampling(nfsp_mccfr* h, int* out) {
+  NFSP_REQUIRE(h && out, "null argument");
+  *out = h->sampling;
+  return NFSP_OK;
+}
+
 extern "C" int nfsp_mccfr_run(nfsp_mccfr* h, int64_t iters) {
   NFSP_REQUIRE(iters >= 0, "iters must be >= 0");
   NFSP_REQUIRE(h, "null argument");
   NFSP_REQUIRE(iters <= INT64_MAX - h->iterations, "overflow: iters too large");
-  int rc = nfsp_mccfr_cfgs_check(h->ctx->game, h->cfgs.data(), h->n, h->iterations + iters);
+  int rc = h->sampling ? nfsp_mccfr_os_cfgs_check(h->ctx->game, h->os_cfgs.data(), h->n, h->iterations + iters)
+                       : nfsp_mccfr_cfgs_check(h->ctx->game, h->cfgs.data(), h->n, h->iterations + iters);
   if (rc != NFSP_OK) return rc;
   const ExTables* T = nullptr;
   rc = device_tables(h->ctx, &T);
   if (rc != NFSP_OK) return rc;
   const dim3 grid(nfsp_blocks(h->max_walkers, NFSP_MCCFR_WG_WALKERS), h->n);
-  const size_t lds = walk_lds(T->nn, T->ndec, h->nterm);
+  const size_t lds = h->sampling ? os_lds(T->nn, T->ndec) : walk_lds(T->nn, T->ndec, h->nterm);
   for (int64_t it = 0; it < iters; ++it) {
     for (int i = 0; i < 2; ++i) {
       const uint64_t hh = 2 * (uint64_t)h->iterations + i;
-      WalkArgs A{};
-      A.T = *T;
-      A.cfg = h->dev_cfg;
-      A.tabs = h->tabs;
-      A.state = h->state;
-      A.counts = h->counts;
-      A.h_lo = (uint32_t)hh;
-      A.h_hi = (uint32_t)(hh >> 32);
-      A.seat = i;
-      A.nterm = h->nterm;
-      k_mccfr_walk<<<grid, WALK_THREADS, lds, h->ctx->stream>>>(A);
-      NFSP_LAUNCHED("k_mccfr_walk");
+      if (h->sampling) {
+        OsArgs A{};
+        A.T = *T;
+        A.cfg = h->dev_cfg;
+        A.eps = h->dev_eps;
+        A.tabs = h->tabs;
+        A.state = h->state;
+        A.counts = h->counts;
+        A.h_lo = (uint32_t)hh;
+        A.h_hi = (uint32_t)(hh >> 32);
+        A.seat = i;
+        k_mccfr_os_walk<<<grid, WALK_THREADS, lds, h->ctx->stream>>>(A);
+        NFSP_LAUNCHED("k_mccfr_os_walk");
+      } else {
+        WalkArgs A{};
+        A.T = *T;
+        A.cfg = h->dev_cfg;
+        A.tabs = h->tabs;
+        A.state = h->state;
+        A.counts = h->counts;
+        A.h_lo = (uint32_t)hh;
+        A.h_hi = (uint32_t)(hh >> 32);
+        A.seat = i;
+        A.nterm = h->nterm;
+        k_mccfr_walk<<<grid, WALK_THREADS, lds, h->ctx->stream>>>(A);
+        NFSP_LAUNCHED("k_mccfr_walk");
+      }
       rc = launch_apply(h, *T, 1);
       if (rc != NFSP_OK) return rc;
     }
@@ -460,6 +735,7 @@ extern "C" int nfsp_mccfr_destroy(nfsp_mccfr* h) {
   if (h->tabs) (void)hipFree(h->tabs);
   if (h->counts) (void)hipFree(h->counts);
   if (h->dev_cfg) (void)hipFree(h->dev_cfg);
+  if (h->dev_eps) (void)hipFree(h->dev_eps);
   delete h;
   return NFSP_OK;
 }

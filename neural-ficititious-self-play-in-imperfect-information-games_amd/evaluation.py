@@ -24,7 +24,9 @@ family anchors Kuhn.  ``XfpSolver`` runs full-width fictitious play on it (``nfs
 csrc/xfp.hip), n runs over eta and the weighting at once: the curve of the algorithm NFSP
 approximates, with an exact best response and exact averaging.  ``MccfrSolver`` runs
 external-sampling MCCFR on it (``nfsp_mccfr_*``, csrc/mccfr.hip): the sampled tabular yardstick,
-counted in traversals and terminals visited, to set beside the engine's curves in hands.
+counted in traversals and terminals visited, to set beside the engine's curves in hands;
+``MccfrOsSolver`` runs outcome sampling on the same handle (``nfsp_mccfr_os_*``), whose traversal
+is one sampled hand, so its cost is in the engine's own unit.
 
 ``MemoryTable`` is a memory counted per information set on the device (``nfsp_memory_table``,
 csrc/memtab.hip): M_SL as the tabular average strategy the AR net is a fit of, M_RL as what the
@@ -828,6 +830,30 @@ class MccfrSolver(_Solver):
         native.check(self.ctx.L.nfsp_mccfr_state(self.h, int(run), R.ctypes.data_as(native.P),
                                                  S.ctypes.data_as(native.P)), "nfsp_mccfr_state")
         return R, S
+
+    @property
+    def sampling(self) -> int:
+        """0 external sampling, 1 outcome sampling (``nfsp_mccfr_sampling``)."""
+        k = native.I32(-1)
+        native.check(self.ctx.L.nfsp_mccfr_sampling(self.h, C.byref(k)), "nfsp_mccfr_sampling")
+        return k.value
+
+
+class MccfrOsSolver(MccfrSolver):
+    """Outcome-sampling MCCFR on the same handle (``nfsp_mccfr_os_create``): a traversal is one
+    sampled hand and one terminal, so ``counts(k)`` is (hands, hands) -- the sampled tabular
+    learner counted in the engine's own unit.  ``cfgs`` is one ``(seed, walkers, epsilon)`` per
+    independent run, epsilon the exploration rate of the updating seat's own actions
+    (``native.MCCFR_OS_EPS_MIN`` .. 1).  Everything else is ``MccfrSolver``'s."""
+
+    def __init__(self, ctx, cfgs=((1, 1024, 0.6),)):
+        _Solver.__init__(self, ctx)
+        self.cfgs = [(int(seed) & (2**64 - 1), int(w), float(eps)) for seed, w, eps in cfgs]
+        self.n = len(self.cfgs)
+        arr = (native.MccfrOsCfg * max(self.n, 1))(*[native.MccfrOsCfg(seed, w, 0, eps) for seed, w, eps in self.cfgs])
+        h = native.P()
+        native.check(ctx.L.nfsp_mccfr_os_create(ctx.h, arr, self.n, C.byref(h)), "nfsp_mccfr_os_create")
+        self.h = h
 
 
 class CfrSolver(_Solver):

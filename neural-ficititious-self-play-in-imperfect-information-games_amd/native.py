@@ -104,6 +104,12 @@ class MccfrCfg(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("walkers", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MccfrOsCfg(C.Structure):
+    """``nfsp_mccfr_os_cfg``: one outcome-sampling MCCFR run's seed, walkers per half-iteration and
+    exploration rate"""
+    _fields_ = [("seed", C.c_uint64), ("walkers", C.c_int32), ("reserved", C.c_int32), ("epsilon", C.c_double)]
+
+
 class MemSegment(C.Structure):
     """``nfsp_mem_segment``: n packed records (SlRec 16 B / RlRec 32 B) at a device address"""
     _fields_ = [("dev_recs", P), ("n", I64)]
@@ -194,6 +200,9 @@ SIGNATURES = {
     "nfsp_mccfr_average": (I32, [P, I32, C.POINTER(P)]),
     "nfsp_mccfr_state": (I32, [P, I32, P, P]),
     "nfsp_mccfr_destroy": (I32, [P]),
+    "nfsp_mccfr_os_cfgs_check": (I32, [I32, C.POINTER(MccfrOsCfg), I32, I64]),
+    "nfsp_mccfr_os_create": (I32, [P, C.POINTER(MccfrOsCfg), I32, C.POINTER(P)]),
+    "nfsp_mccfr_sampling": (I32, [P, C.POINTER(I32)]),
     "nfsp_engine_set_loss_log": (I32, [P, I32]),
     "nfsp_engine_losses": (I32, [P, P]),
     "nfsp_engine_set_timing": (I32, [P, I32]),
@@ -277,6 +286,7 @@ MCCFR_Q = 1 << 24
 MCCFR_MAX_RUNS = 64
 MCCFR_MAX_WALKERS = 1 << 22
 MCCFR_WG_WALKERS = 1024
+MCCFR_OS_EPS_MIN = 0.0625       # outcome sampling's least exploration rate (NFSP_MCCFR_OS_EPS_MIN)
 # the memories as tables (NFSP_MEM_*, NFSP_MEMTAB_*)
 MEM_SL, MEM_RL, MEM_TD, MEM_TDQ = 0, 1, 2, 3
 # what nfsp_table_rows makes of a table (NFSP_ROWS_*), and the most sweeps and tables of a call

@@ -9,6 +9,8 @@ csrc/xfp.hip): the algorithm NFSP approximates, with an exact best response and 
     python tools/solve_game.py --game leduc --solver xfp --eta 0.5 --runs 64 --every 1024
     python tools/solve_game.py --game leduc --solver mccfr --walkers 1024 --seeds 4 --iters 32768
     python tools/solve_game.py --solver mccfr --time
+    python tools/solve_game.py --game leduc --solver mccfr-os --epsilon 0.6 --walkers 1024 --seeds 4 --iters 32768
+    python tools/solve_game.py --solver mccfr-os --time
 
 eq.npz holds ``table`` [ndec, 3 ranks, 3 actions] (rows as evaluation.GameTree's; usable as
 evaluation.Policy.table), ``game``, and per checkpoint (--every, doubling by default)
@@ -29,6 +31,12 @@ tabular yardstick.  --walkers W traversals per seat and iteration, --seeds K ind
 visited, which each checkpoint's line carries beside ``exploitability_runs``; the fields above
 are the first seed's.  --time instead reports traversals/s and terminals/s for Leduc at
 W = 2^20: one iteration timed with HIP events on the solver's stream, best of 5 after a warm-up.
+
+--solver mccfr-os: outcome-sampling MCCFR (evaluation.MccfrOsSolver, k_mccfr_os_walk) on the same
+handle, --epsilon the exploration rate of the updating seat's own actions.  A traversal is one
+sampled hand and one terminal, so its lines carry ``hands`` (= traversals) and ``epsilon`` beside
+what mccfr's carry, and --time adds ``hands_per_s``.  W x iterations is bounded by the int64
+fixed point (include/nfsp.h): 197,912,092 on Leduc at --epsilon 0.6.
 """
 import argparse
 import json
@@ -42,11 +50,15 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 
-def time_mccfr(ev, nat, walkers=1 << 20, repeats=5):
-    """Best of ``repeats`` single iterations (2 W traversals each) after a warm-up."""
+def time_mccfr(ev, nat, epsilon=None, walkers=1 << 20, repeats=5):
+    """Best of ``repeats`` single iterations (2 W traversals each) after a warm-up; outcome
+    sampling where ``epsilon`` is given."""
     import torch
     ctx = nat.Context(1, game=nat.GAME_LEDUC)
-    solver = ev.MccfrSolver(ctx, [(1, walkers)]).run(1)
+    if epsilon is None:
+        solver = ev.MccfrSolver(ctx, [(1, walkers)]).run(1)
+    else:
+        solver = ev.MccfrOsSolver(ctx, [(1, walkers, epsilon)]).run(1)
     best = None
     for _ in range(repeats):
         before = solver.counts(0)
@@ -60,9 +72,11 @@ def time_mccfr(ev, nat, walkers=1 << 20, repeats=5):
         rec = {"ms": ms, "traversals": after[0] - before[0], "terminals": after[1] - before[1]}
         if best is None or ms < best["ms"]:
             best = rec
-    best.update(game="leduc", solver="mccfr", walkers=walkers, repeats=repeats,
+    best.update(game="leduc", solver="mccfr" if epsilon is None else "mccfr-os", walkers=walkers, repeats=repeats,
                 traversals_per_s=best["traversals"] / (best["ms"] * 1e-3),
                 terminals_per_s=best["terminals"] / (best["ms"] * 1e-3))
+    if epsilon is not None:
+        best.update(epsilon=epsilon, hands=best["traversals"], hands_per_s=best["traversals_per_s"])
     print(json.dumps(best), flush=True)
     solver.close()
 
@@ -70,7 +84,7 @@ def time_mccfr(ev, nat, walkers=1 << 20, repeats=5):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--game", default="leduc", choices=["leduc", "kuhn"])
-    ap.add_argument("--solver", default="cfr", choices=["cfr", "xfp", "mccfr"])
+    ap.add_argument("--solver", default="cfr", choices=["cfr", "xfp", "mccfr", "mccfr-os"])
     ap.add_argument("--iters", type=int, default=1024)
     ap.add_argument("--every", type=int, default=0, help="checkpoint every K iterations (default: 1, 2, 4, ...)")
     ap.add_argument("--eta", type=float, default=0.0, help="xfp: anticipatory parameter, in [0, 1)")
@@ -78,7 +92,9 @@ def main():
     ap.add_argument("--runs", type=int, default=1, help="xfp: runs in one launch, eta spaced over [0, --eta]")
     ap.add_argument("--walkers", type=int, default=1024, help="mccfr: traversals per seat and iteration (even)")
     ap.add_argument("--seeds", type=int, default=1, help="mccfr: independent runs, seeds 1 .. K")
-    ap.add_argument("--time", action="store_true", help="mccfr: traversals/s and terminals/s, Leduc at W = 2^20")
+    ap.add_argument("--epsilon", type=float, default=0.6, help="mccfr-os: exploration rate, in [0.0625, 1]")
+    ap.add_argument("--time", action="store_true",
+                    help="mccfr, mccfr-os: traversals/s and terminals/s, Leduc at W = 2^20")
     ap.add_argument("--out", default=None, metavar="PATH")
     args = ap.parse_args()
     import __graft_entry__
@@ -86,13 +102,16 @@ def main():
     ev, nat = pkg.evaluation, pkg.native
     game = nat.GAME_KUHN if args.game == "kuhn" else nat.GAME_LEDUC
     if args.time:
-        if args.solver != "mccfr":
-            ap.error("--time is for --solver mccfr")
-        return time_mccfr(ev, nat)
+        if args.solver not in ("mccfr", "mccfr-os"):
+            ap.error("--time is for --solver mccfr and mccfr-os")
+        return time_mccfr(ev, nat, args.epsilon if args.solver == "mccfr-os" else None)
     ctx = nat.Context(1, game=game)
     xfp = args.solver == "xfp"
-    mccfr = args.solver == "mccfr"
-    if mccfr:
+    outcome = args.solver == "mccfr-os"
+    mccfr = args.solver == "mccfr" or outcome
+    if outcome:
+        solver = ev.MccfrOsSolver(ctx, [(seed, args.walkers, args.epsilon) for seed in range(1, args.seeds + 1)])
+    elif mccfr:
         solver = ev.MccfrSolver(ctx, [(seed, args.walkers) for seed in range(1, args.seeds + 1)])
     elif xfp:
         etas = [args.eta] if args.runs == 1 else [float(e) for e in np.linspace(0.0, args.eta, args.runs)]
@@ -123,8 +142,10 @@ def main():
                "value0_dealer": [r["value0_dealer0"], r["value0_dealer1"]], "ms_per_iteration": ms}
         if mccfr:
             counts = [solver.counts(k) for k in range(solver.n)]
-            rec.update(solver="mccfr", walkers=args.walkers, traversals=counts[0][0],
+            rec.update(solver=args.solver, walkers=args.walkers, traversals=counts[0][0],
                        terminals=[c[1] for c in counts], exploitability_runs=[x["exploitability"] for x in res])
+        if outcome:
+            rec.update(hands=counts[0][0], epsilon=args.epsilon)
         if xfp:
             rec.update(solver="xfp", weight=args.weight, eta=etas[-1])
             if len(etas) > 1:
