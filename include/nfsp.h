@@ -851,8 +851,92 @@ int nfsp_mccfr_os_cfgs_check(int game, const nfsp_mccfr_os_cfg* cfgs /*[n]*/, in
 /* The handle is an nfsp_mccfr: nfsp_mccfr_run / _iterations / _counts / _average / _state /
  * _destroy serve it unchanged, and run re-checks outcome sampling's own bound. */
 int nfsp_mccfr_os_create(nfsp_ctx* ctx, const nfsp_mccfr_os_cfg* cfgs /*[n]*/, int n, nfsp_mccfr** out);
-/* out: 0 external sampling (nfsp_mccfr_create), 1 outcome sampling (nfsp_mccfr_os_create). */
+/* out: 0 external sampling (nfsp_mccfr_create), 1 outcome sampling (nfsp_mccfr_os_create),
+ * 2 outcome sampling with baselines (nfsp_mccfr_vr_create). */
 int nfsp_mccfr_sampling(nfsp_mccfr* h, int* out);
+
+/* ---- baseline-corrected outcome sampling on the same handle (csrc/mccfr.hip k_mccfr_vr_walk,
+ * k_mccfr_apply, k_mccfr_vr_apply) ----
+ * VR-MCCFR (Schmid et al. 2019; Davis, Schmid and Bowling 2020): outcome sampling with a control
+ * variate ("baseline") at every decision of the sampled path.  Still one trajectory and one
+ * terminal per sample; the pay / q estimate is replaced by values corrected on the way back up --
+ * the tabular analogue of what a critic does for a sampled learner.
+ * State per run: R and S as above, and the baseline sums Bs [ndec][3][3] (int64, NFSP_MCCFR_Q per
+ * chip) and counts Bn [ndec][3][3] (int64); all 0 at creation.  The baseline of a half-iteration
+ * is frozen as sigma is:
+ *   B[row][r][a] = clamp((double)Bs / ((double)Bn * Q), -P, P), and 0 where Bn == 0,
+ * P = max|pay| of the game's table.  B is in the perspective of the seat that acts at row, r that
+ * seat's rank.  Every true value lies in [-P, P], so the clamp costs nothing and keeps the
+ * overflow bound usable.
+ * Step 1 (sigma from R), step 3, the draw u(node), the choice rule, the dealer w & 1, the deal at
+ * the pseudo-node nn, xi_a = eps / (double)L + (1.0 - eps) * sigma_a at seat i's decisions, the
+ * on-policy sampling of chance and the opponent, q, and winv = Q / q with
+ * dS[row][r_o][a] += llrint(sigma_a * winv) at the opponent's decisions are outcome sampling's,
+ * above: with the same seed, eps and R the path of walker w, its deal and its dS are outcome
+ * sampling's bit for bit.  What changes is the pass back up; all f64, no FMA contraction, the
+ * operations in the order written:
+ *   on the way down      push a frame at every decision, both seats'.  At seat i's keep xi_{a*}
+ *                        and qk, the value of q before it is multiplied by xi_{a*}.
+ *   terminal             v = (double)pay[row][i][r_i][r_o].  No division.
+ *   then the frames, deepest first:
+ *   the opponent's       b_a = -B[row][r_o][a] for the legal a (seat i's perspective), 0 at an
+ *   (row, r_o, a*)       illegal raise;
+ *                        dBs[row][r_o][a*] += llrint((-v) * Q) and dBn[row][r_o][a*] += 1;
+ *                        v = ((sigma_0 * b_0 + sigma_1 * b_1) + sigma_2 * b_2) + (v - b_{a*}).
+ *                        No division by sigma: the opponent is sampled on-policy and it cancels.
+ *   seat i's             b_a = B[row][r_i][a];
+ *   (row, r_i, a*,       dBs[row][r_i][a*] += llrint(v * Q) and dBn[row][r_i][a*] += 1;
+ *    xi_{a*}, qk)        u_a = b_a for the legal a != a*, u_{a*} = b_{a*} + (v - b_{a*}) / xi_{a*};
+ *                        vbar = 0, then vbar = vbar + sigma_a * u_a for the legal a ascending;
+ *                        dR[row][r_i][a] += llrint(((u_a - vbar) / qk) * Q) for each legal a;
+ *                        then v = vbar.
+ *   chance               passes v through: no baseline at chance nodes.
+ *   3. R += dR, S += dS, Bs += dBs, Bn += dBn, then the next sigma and the next B.
+ * ANY baseline leaves the estimator unbiased: E over a* of u_a is the value below a whatever b
+ * is.  The acting seat's perspective and the sign flip at the opponent's nodes serve only the
+ * baseline's quality on a zero-sum table -- one table then learns from both seats' half-iterations.
+ * Traversals are 2 W t and terminals visited are 2 W t, as outcome sampling's.
+ * Overflow.  With |B| <= P the host computes from the tree, for either seat as seat i, Vmax(n), a
+ * bound on |v| at node n:
+ *   terminal P; chance the most of its children's; the opponent's decision 2 P + the most of its
+ *   children's; seat i's decision with L legal actions P + (the most of its children's + P) *
+ *   ((double)L / eps).
+ * One traversal moves an R entry at seat i's node n by at most Rmax = (2 Vmax(n)) * (the product
+ * of L_k / eps over seat i's decisions above n), a Bs entry by at most Bmax = Vmax of a decision's
+ * child, and an S entry by omega (outcome sampling's), all times Q and each the most over nodes
+ * and seats.  A run is refused when
+ *   W x iterations > floor(2^62 / (Q x max(Rmax, Bmax, omega))),
+ * the message naming the bound.  Leduc at eps = 0.6 (Rmax = 9432.2 chips) allows 29,142,433
+ * walker-iterations, at eps = 0.0625 5,479; Kuhn 1,264,775,645 and 21,047,312: a seventh to a
+ * quarter of outcome sampling's, since a corrected value is bounded by the baseline's range at
+ * every level, not by one pay.  Bn grows by at most 1 per traversal and entry.
+ * A lane runs one path: up to 8 frames of 16 bits are two 64-bit scalars, qk for seat i's second
+ * to fourth decision are three registers chosen by compares, and xi_{a*} is formed again from
+ * sigma and eps on the way back by the same operations (no scratch).  The workgroup's LDS holds
+ * sigma, B, dR, dS, dBs, dBn and the node table.  k_mccfr_vr_apply, a third small launch per
+ * half-iteration, does the baseline's part of step 3.  tests/mccfr_vr_ref.py restates the rule in
+ * numpy, and R, S, Bs, Bn and the counts agree to the bit. */
+typedef struct {
+  uint64_t seed;
+  int32_t walkers;                      /* W: even, 2 .. NFSP_MCCFR_MAX_WALKERS */
+  int32_t reserved;                     /* 0 */
+  double epsilon;                       /* in [NFSP_MCCFR_OS_EPS_MIN, 1] */
+} nfsp_mccfr_vr_cfg;                    /* 24 bytes */
+/* Host only, as nfsp_mccfr_os_cfgs_check, with the overflow bound above. */
+int nfsp_mccfr_vr_cfgs_check(int game, const nfsp_mccfr_vr_cfg* cfgs /*[n]*/, int n, int64_t iters);
+/* The handle is an nfsp_mccfr: nfsp_mccfr_run / _iterations / _counts / _average / _state /
+ * _destroy serve it unchanged, run re-checks this kind's own bound, nfsp_mccfr_sampling gives 2. */
+int nfsp_mccfr_vr_create(nfsp_ctx* ctx, const nfsp_mccfr_vr_cfg* cfgs /*[n]*/, int n, nfsp_mccfr** out);
+/* The baseline's sums and counts of a run.  Synchronises the ctx stream.  Refused for a handle of
+ * another sampling kind. */
+int nfsp_mccfr_baseline(nfsp_mccfr* h, int run, int64_t* host_Bs /*[ndec][3][3]*/, int64_t* host_Bn /*[ndec][3][3]*/);
+/* Replaces the baseline's sums and counts of a run and recomputes its B: how a test pins an
+ * arbitrary baseline and how a user installs an informed one (a table of action values in the
+ * acting seat's perspective times Q, with count 1).  Refused: a negative count, a non-zero sum at
+ * a zero count, a sum or count beyond 2^61 (the run's budget is counted from 0), and a handle of
+ * another sampling kind.  R, S and the iteration count are left as they are. */
+int nfsp_mccfr_set_baseline(nfsp_mccfr* h, int run, const int64_t* host_Bs /*[ndec][3][3]*/,
+                            const int64_t* host_Bn /*[ndec][3][3]*/);
 
 /* ---- the memories as tables (csrc/memtab.hip k_memtab, k_memtab_sum) ----
  * M_SL (utils/ReservoirBuffer.py:18-28) and M_RL (utils/replay_buffer.py:30-41) counted per

@@ -29,6 +29,13 @@
 //                  weights 1 / q.  The frames are 16 bits each in one 64-bit scalar, sigma is
 //                  re-read from LDS by row, and the one pay entry comes from device memory, so pay
 //                  is not staged (Leduc: 36,824 B of LDS, four workgroups to a CU).
+// Baseline-corrected outcome sampling (nfsp_mccfr_vr_*, VR-MCCFR, the same handle) swaps it for
+//   k_mccfr_vr_walk  outcome sampling's grid, mapping, path down and flush.  Both seats' decisions
+//                  are frames (8 of 16 bits in two scalars); the terminal's pay is carried back up
+//                  them, corrected at each by the frozen baseline B (f64, staged beside sigma), and
+//                  every frame adds its sample to dBs / dBn beside dR / dS (Leduc: 64,904 B of LDS,
+//                  two workgroups to a CU).
+//   k_mccfr_vr_apply  after k_mccfr_apply: Bs += dBs, Bn += dBn, the deltas zeroed, the next B.
 // No workgroup waits for another -- no flags, no tickets, no spinning: the stream orders the
 // launches, and nfsp_mccfr_run synchronises once at its end.
 // All f64 arithmetic is in tree_walk.h's style (no FMA contraction, the sums ascending).
@@ -47,10 +54,14 @@ struct nfsp_mccfr {
   double* tabs = nullptr;                 // per run sigma | average, [ndec][3][3] each
   unsigned long long* counts = nullptr;   // per run traversals, terminals, terminals of the walk in flight
   nfsp_mccfr_cfg* dev_cfg = nullptr;      // [n]
-  int sampling = 0;                       // 0 external, 1 outcome
+  int sampling = 0;                       // 0 external, 1 outcome, 2 outcome with baselines
   std::vector<nfsp_mccfr_os_cfg> os_cfgs; // outcome sampling: the cfgs as given (cfgs holds their seed and walkers)
   std::vector<double> eps;                // outcome sampling: [n][3] epsilon, epsilon / 2.0, epsilon / 3.0
   double* dev_eps = nullptr;              // eps on the device
+  std::vector<nfsp_mccfr_vr_cfg> vr_cfgs; // with baselines: the cfgs as given (os_cfgs holds the same fields)
+  long long* bstate = nullptr;            // with baselines: per run Bs | Bn | dBs | dBn, [ndec][3][3] each
+  double* btab = nullptr;                 // with baselines: per run B, [ndec][3][3]
+  double maxpay = 0.0;                    // with baselines: P, the game's max|pay|
 };
 
 namespace {
@@ -419,6 +430,243 @@ __global__ void __launch_bounds__(WALK_THREADS) k_mccfr_os_walk(OsArgs A) {
     __hip_atomic_fetch_add(A.counts + (size_t)run * 3 + 2, *terms, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+struct VrArgs {
+  ExTables T;
+  const nfsp_mccfr_cfg* cfg;              // [n]
+  const double* eps;                      // [n][3], as OsArgs
+  const double* tabs;
+  const double* btab;                     // [n][ndec][3][3]: B, frozen for the half-iteration
+  long long* state;
+  long long* bstate;                      // [n][4][ndec][3][3]: dBs, dBn are the last two
+  unsigned long long* counts;
+  uint32_t h_lo, h_hi;
+  int seat;
+};
+
+// dynamic LDS of the baseline-corrected walk: sigma and B f64, dR, dS, dBs and dBn int64, the
+// terminal count, the node table
+__host__ __device__ inline size_t vr_lds(int nn, int ndec) {
+  return 8 * ((size_t)ndec * 54 + 1) + sizeof(DevNode) * (size_t)nn;
+}
+
+// A frame of the baseline-corrected path, 16 bits: row << 4 | seat i's << 3 | raise legal << 2 | a*.
+// Both seats' decisions are frames, 2 MAX_FRAMES of them at most: two 64-bit scalars, the deepest
+// in the low bits of the first (nfsp_mccfr_vr_create checks the rows fit).
+constexpr int VR_FRAME_MAX_ROWS = 1 << (FRAME_BITS - 4);
+static_assert(2 * MAX_FRAMES * FRAME_BITS <= 128, "the frames of a path are two scalars");
+
+// Baseline-corrected outcome sampling: the grid, the lane-to-walker mapping, the staging, the path
+// down with its dS and the flush are k_mccfr_os_walk's (written out again, as that kernel's are);
+// B is staged beside sigma and dBs / dBn lie beside dR / dS.  The way down pushes a frame at both
+// seats' decisions and keeps q before seat i's second, third and fourth factor (before the first
+// it is 1.0) in three registers chosen by compares, never by an index; xi_{a*} is formed again on
+// the way back from the same sigma and eps by the same two operations, so its bits are the
+// rule's.  Divisions: Q / q at an opponent's node on the way down; on the way back one by
+// xi_{a*} and one by qk per legal action at seat i's frames, none at the opponent's or the end.
+__global__ void __launch_bounds__(WALK_THREADS) k_mccfr_vr_walk(VrArgs A) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const ExTables& T = A.T;
+  const int run = blockIdx.y;
+  const int W = A.cfg[run].walkers;
+  const int w0 = blockIdx.x * NFSP_MCCFR_WG_WALKERS;
+  if (w0 >= W) return;
+  const int nn = T.nn, n9 = T.ndec * 9;
+  double* sg = reinterpret_cast<double*>(smem_raw);
+  double* B = sg + n9;
+  unsigned long long* dR = reinterpret_cast<unsigned long long*>(B + n9);
+  unsigned long long* dS = dR + n9;
+  unsigned long long* dBs = dS + n9;
+  unsigned long long* dBn = dBs + n9;
+  unsigned long long* terms = dBn + n9;
+  DevNode* nodes = reinterpret_cast<DevNode*>(terms + 1);
+  const int tid = threadIdx.x;
+  const double* gsg = A.tabs + (size_t)run * 2 * n9;
+  const double* gB = A.btab + (size_t)run * n9;
+  for (int k = tid; k < n9; k += WALK_THREADS) {
+    sg[k] = gsg[k];
+    B[k] = gB[k];
+    dR[k] = 0;
+    dS[k] = 0;
+    dBs[k] = 0;
+    dBn[k] = 0;
+  }
+  if (tid == 0) *terms = 0;
+  for (int k = tid; k < nn; k += WALK_THREADS) nodes[k] = T.nodes[k];
+  __syncthreads();
+
+  Walker X;
+  X.sg = sg;
+  X.nodes = nodes;
+  X.pay = T.pay + A.seat * 9;             // device memory: a traversal reads one entry
+  X.dR = dR;
+  X.dS = dS;
+  X.h_lo = A.h_lo;
+  X.h_hi = A.h_hi;
+  X.k0 = (uint32_t)A.cfg[run].seed;
+  X.k1 = (uint32_t)(A.cfg[run].seed >> 32);
+  X.i = A.seat;
+  X.nlev = T.nlev;
+  X.terminals = 0;
+  const double eps = A.eps[run * 3], eps2 = A.eps[run * 3 + 1], eps3 = A.eps[run * 3 + 2];
+  const double keep = 1.0 - eps;
+  for (int k = 0; k < NFSP_MCCFR_WG_WALKERS / WALK_THREADS; ++k) {
+    const int w = w0 + k * WALK_THREADS + tid;
+    if (w >= W) continue;
+    X.w = (uint32_t)w;
+    const double ud = draw(X, nn);
+    double cd = 0.0;
+    int pick = -1, last = -1;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) choice_step(T.deal[j / 3][j % 3], j, ud, cd, pick, last);
+    const int j = pick >= 0 ? pick : last;
+    if (j < 0) continue;
+    X.ri = j / 3;
+    X.ro = j % 3;
+    // the path down: outcome sampling's, with a frame at every decision
+    int n = T.root[w & 1], nf = 0, no = 0, end = -1;
+    double q = 1.0, qk1 = 1.0, qk2 = 1.0, qk3 = 1.0;
+    uint64_t flo = 0, fhi = 0;
+    for (int d = 0; d < X.nlev; ++d) {
+      const DevNode& N = X.nodes[n];
+      if (N.kind == TNode::TERMINAL) {
+        end = N.row;
+        break;
+      }
+      const double u = draw(X, n);
+      const bool dec = N.kind == TNode::DECISION;
+      const bool own = dec && N.p == X.i;
+      const bool l2 = N.child[2] >= 0;
+      double p0, p1, p2;
+      if (!dec) {
+        const int r0 = X.i == 0 ? X.ri : X.ro, r1 = X.i == 0 ? X.ro : X.ri;
+        p0 = p_public(0, r0, r1);
+        p1 = p_public(1, r0, r1);
+        p2 = p_public(2, r0, r1);
+      } else {
+        const size_t row = (size_t)N.row * 9 + (own ? X.ri : X.ro) * 3;
+        p0 = X.sg[row + 0];
+        p1 = X.sg[row + 1];
+        p2 = X.sg[row + 2];
+        if (own) {
+          const double e = l2 ? eps3 : eps2;
+          p0 = e + keep * p0;
+          p1 = e + keep * p1;
+          p2 = l2 ? e + keep * p2 : 0.0;
+        } else {
+          const double winv = Q / q;
+          add_fixed(X.dS + row + 0, p0 * winv);
+          add_fixed(X.dS + row + 1, p1 * winv);
+          add_fixed(X.dS + row + 2, p2 * winv);
+        }
+      }
+      const int a = choose3(p0, p1, p2, u);
+      if (a < 0) break;                   // no positive probability: not a strategy
+      if (dec) {
+        if (nf >= 2 * MAX_FRAMES || (own && no >= MAX_FRAMES)) break;    // unreachable: creation counted the frames
+        fhi = fhi << FRAME_BITS | flo >> (64 - FRAME_BITS);
+        flo = flo << FRAME_BITS | (uint64_t)(N.row << 4 | (own ? 8 : 0) | (l2 ? 4 : 0) | a);
+        ++nf;
+        if (own) {
+          qk1 = no == 1 ? q : qk1;        // qk of seat i's frame `no`; frame 0's is 1.0
+          qk2 = no == 2 ? q : qk2;
+          qk3 = no == 3 ? q : qk3;
+          ++no;
+          q = q * (a == 0 ? p0 : a == 1 ? p1 : p2);
+        }
+      }
+      n = N.child[a];
+      if (n < 0) break;
+    }
+    if (end < 0) continue;
+    ++X.terminals;
+    // the frames back, deepest first
+    double v = (double)X.pay[(size_t)end * 18 + X.ri * 3 + X.ro];
+    for (int f = 0; f < 2 * MAX_FRAMES; ++f) {
+      if (f >= nf) break;
+      const uint32_t fr = (uint32_t)flo & ((1u << FRAME_BITS) - 1);
+      flo = flo >> FRAME_BITS | fhi << (64 - FRAME_BITS);
+      fhi >>= FRAME_BITS;
+      const int a = fr & 3;
+      const bool own = fr & 8, l2 = fr & 4;
+      const size_t row = (size_t)(fr >> 4) * 9 + (own ? X.ri : X.ro) * 3;
+      const double s0 = X.sg[row + 0], s1 = X.sg[row + 1], s2 = X.sg[row + 2];
+      atomicAdd(dBn + row + a, 1ull);
+      if (!own) {
+        const double b0 = -B[row + 0], b1 = -B[row + 1], b2 = l2 ? -B[row + 2] : 0.0;
+        const double ba = a == 0 ? b0 : a == 1 ? b1 : b2;
+        add_fixed(dBs + row + a, (-v) * Q);
+        v = ((s0 * b0 + s1 * b1) + s2 * b2) + (v - ba);
+      } else {
+        const double b0 = B[row + 0], b1 = B[row + 1], b2 = B[row + 2];
+        const double ba = a == 0 ? b0 : a == 1 ? b1 : b2;
+        add_fixed(dBs + row + a, v * Q);
+        --no;
+        const double qk = no == 0 ? 1.0 : no == 1 ? qk1 : no == 2 ? qk2 : qk3;
+        const double xi = (l2 ? eps3 : eps2) + keep * (a == 0 ? s0 : a == 1 ? s1 : s2);
+        const double hit = ba + (v - ba) / xi;
+        const double u0 = a == 0 ? hit : b0, u1 = a == 1 ? hit : b1, u2 = a == 2 ? hit : b2;
+        double vbar = 0.0;
+        vbar = vbar + s0 * u0;
+        vbar = vbar + s1 * u1;
+        if (l2) vbar = vbar + s2 * u2;
+        add_fixed(X.dR + row + 0, ((u0 - vbar) / qk) * Q);
+        add_fixed(X.dR + row + 1, ((u1 - vbar) / qk) * Q);
+        if (l2) add_fixed(X.dR + row + 2, ((u2 - vbar) / qk) * Q);
+        v = vbar;
+      }
+    }
+  }
+  if (X.terminals) atomicAdd(terms, (unsigned long long)X.terminals);
+  __syncthreads();
+
+  long long* gd = A.state + ((size_t)run * 4 + 2) * n9;    // dR | dS, as in LDS
+  long long* gb = A.bstate + ((size_t)run * 4 + 2) * n9;   // dBs | dBn, as in LDS
+  for (int k = tid; k < 2 * n9; k += WALK_THREADS) {
+    const unsigned long long v = dR[k], b = dBs[k];
+    if (v)
+      __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(gd) + k, v, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+    if (b)
+      __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(gb) + k, b, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (tid == 0 && *terms)
+    __hip_atomic_fetch_add(A.counts + (size_t)run * 3 + 2, *terms, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+struct VrApplyArgs {
+  long long* bstate;
+  double* btab;
+  int ndec;
+  double maxpay;                          // P
+};
+
+// The baseline's step 3, one thread per entry of a run: Bs += dBs, Bn += dBn, the deltas zeroed,
+// and the next B = clamp((double)Bs / ((double)Bn * Q), -P, P), 0 where Bn is 0.
+__global__ void __launch_bounds__(256) k_mccfr_vr_apply(VrApplyArgs A) {
+#pragma clang fp contract(off)
+  const int run = blockIdx.y;
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t n9 = (size_t)A.ndec * 9;
+  if (k >= (int)n9) return;
+  long long* Bs = A.bstate + (size_t)run * 4 * n9 + k;
+  long long* Bn = Bs + n9;
+  long long* dBs = Bn + n9;
+  long long* dBn = dBs + n9;
+  const long long s = *Bs + *dBs, c = *Bn + *dBn;
+  *Bs = s;
+  *Bn = c;
+  *dBs = 0;
+  *dBn = 0;
+  double b = 0.0;
+  if (c > 0) {
+    b = (double)s / ((double)c * Q);
+    b = b < -A.maxpay ? -A.maxpay : b > A.maxpay ? A.maxpay : b;
+  }
+  A.btab[(size_t)run * n9 + k] = b;
+}
+
 // One thread per (row, rank) of a run.
 __global__ void __launch_bounds__(256) k_mccfr_apply(ApplyArgs A) {
 #pragma clang fp contract(off)
@@ -471,6 +719,49 @@ double omega_below(const HostTables& H, int n, int i, double eps, double w) {
   double m = w;
   for (int a = 0; a < 3; ++a) m = std::max(m, omega_below(H, N.child[a], i, eps, w));
   return m;
+}
+
+// The rule's overflow recursion of the baseline-corrected walk, |B| <= P, for seat i (the node
+// table is in depth order, parents first).  Vmax(n) bounds |v| at n:
+//   terminal P; chance the most of its children; the opponent's 2 P + the most of its children;
+//   seat i's with L legal actions P + (the most of its children + P) * ((double)L / eps).
+// rmax: the most of (2 Vmax(n)) * (the product of L_k / eps over seat i's decisions above n) over
+// seat i's decisions, what one traversal moves an R entry by; bmax: the most Vmax of a
+// decision's child (either seat's), what it moves a Bs entry by.  Both in chips, both only raised.
+void vr_bounds(const HostTables& H, int i, double P, double eps, double& rmax, double& bmax) {
+  const int nn = (int)H.nodes.size();
+  std::vector<double> vmax(nn, 0.0), w(nn, 1.0);
+  for (int n = nn - 1; n >= 0; --n) {
+    const DevNode& N = H.nodes[n];
+    double m = 0.0;
+    for (int a = 0; a < 3; ++a)
+      if (N.child[a] >= 0) m = std::max(m, vmax[N.child[a]]);
+    if (N.kind == TNode::TERMINAL) vmax[n] = P;
+    else if (N.kind == TNode::CHANCE) vmax[n] = m;
+    else if (N.p != i) vmax[n] = 2.0 * P + m;
+    else vmax[n] = P + (m + P) * ((double)N.nchild / eps);
+    if (N.kind == TNode::DECISION) bmax = std::max(bmax, m);
+  }
+  for (int n = 0; n < nn; ++n) {
+    const DevNode& N = H.nodes[n];
+    if (N.parent >= 0) {
+      const DevNode& U = H.nodes[N.parent];
+      w[n] = w[N.parent];
+      if (U.kind == TNode::DECISION && U.p == i) w[n] = w[N.parent] * ((double)U.nchild / eps);
+    }
+    if (N.kind == TNode::DECISION && N.p == i) rmax = std::max(rmax, (2.0 * vmax[n]) * w[n]);
+  }
+}
+
+int launch_vr_apply(nfsp_mccfr* h) {
+  VrApplyArgs A{};
+  A.bstate = h->bstate;
+  A.btab = h->btab;
+  A.ndec = h->ndec;
+  A.maxpay = h->maxpay;
+  k_mccfr_vr_apply<<<dim3(nfsp_blocks(9 * (int64_t)h->ndec, 256), h->n), 256, 0, h->ctx->stream>>>(A);
+  NFSP_LAUNCHED("k_mccfr_vr_apply");
+  return NFSP_OK;
 }
 
 int launch_apply(nfsp_mccfr* h, const ExTables& T, int walked) {
@@ -551,11 +842,48 @@ extern "C" int nfsp_mccfr_os_cfgs_check(int game, const nfsp_mccfr_os_cfg* cfgs,
   return NFSP_OK;
 }
 
+extern "C" int nfsp_mccfr_vr_cfgs_check(int game, const nfsp_mccfr_vr_cfg* cfgs, int n, int64_t iters) {
+  NFSP_REQUIRE(cfgs, "null argument");
+  NFSP_REQUIRE(n >= 1 && n <= NFSP_MCCFR_MAX_RUNS, "n must be in 1 .. NFSP_MCCFR_MAX_RUNS");
+  NFSP_REQUIRE(iters >= 0, "iters must be >= 0");
+  const HostTables* H = nullptr;
+  const int rc = host_tables(game, &H);
+  if (rc != NFSP_OK) return rc;
+  float maxpay = 0.f;                     // P: the clamp of B, so the table's own max|pay|
+  for (float p : H->pay) maxpay = std::max(maxpay, p < 0 ? -p : p);
+  for (int k = 0; k < n; ++k) {
+    const nfsp_mccfr_vr_cfg& c = cfgs[k];
+    NFSP_REQUIRE(c.walkers >= 2 && c.walkers <= NFSP_MCCFR_MAX_WALKERS,
+                 "nfsp_mccfr_vr_cfg.walkers must be in 2 .. NFSP_MCCFR_MAX_WALKERS");
+    NFSP_REQUIRE(c.walkers % 2 == 0, "nfsp_mccfr_vr_cfg.walkers must be even (one dealer each in turn)");
+    NFSP_REQUIRE(c.reserved == 0, "nfsp_mccfr_vr_cfg.reserved must be 0");
+    NFSP_REQUIRE(c.epsilon >= NFSP_MCCFR_OS_EPS_MIN && c.epsilon <= 1.0,       // false for a NaN
+                 "nfsp_mccfr_vr_cfg.epsilon must be in NFSP_MCCFR_OS_EPS_MIN .. 1");
+    double omega = 1.0, rmax = 0.0, bmax = 0.0;
+    for (int d = 0; d < 2; ++d)
+      for (int i = 0; i < 2; ++i) omega = std::max(omega, omega_below(*H, H->root[d], i, c.epsilon, 1.0));
+    for (int i = 0; i < 2; ++i) vr_bounds(*H, i, (double)maxpay, c.epsilon, rmax, bmax);
+    // per traversal an R entry moves by at most Rmax Q, a Bs entry by Bmax Q, an S entry by omega Q
+    const double most = std::max(std::max(rmax, bmax), omega);
+    const int64_t bound = (int64_t)((double)(1ll << 62) / (Q * most));
+    if (iters > bound / c.walkers) {
+      char msg[320];
+      snprintf(msg, sizeof msg,
+               "overflow: walkers x iterations = %d x %lld would pass the bound %lld (2^62 / (2^24 x max(Rmax, Bmax, "
+               "omega)), Rmax = %g and Bmax = %g chips, omega = %g at epsilon = %g, max|pay| = %g chips)", c.walkers,
+               (long long)iters, (long long)bound, rmax, bmax, omega, c.epsilon, (double)maxpay);
+      return nfsp::fail(NFSP_EINVAL, msg);
+    }
+  }
+  return NFSP_OK;
+}
+
 namespace {
 
-// What both kinds of handle are made of, after their checks: cfgs holds every run's seed and
-// walkers; os is null for external sampling.
-int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os_cfg* os, int n, nfsp_mccfr** out) {
+// What every kind of handle is made of, after its checks: cfgs holds every run's seed and
+// walkers; os is null for external sampling; sampling 2 adds the baseline's tables, all 0.
+int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os_cfg* os, int n, nfsp_mccfr** out,
+                  int sampling = -1) {
   const HostTables* H = nullptr;
   int rc = host_tables(ctx->game, &H);
   if (rc != NFSP_OK) return rc;
@@ -566,7 +894,12 @@ int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os
   rc = device_tables(ctx, &T);
   if (rc != NFSP_OK) return rc;
   const int nterm = (int)(H->pay.size() / 18);
-  if (os) {
+  if (sampling < 0) sampling = os ? 1 : 0;
+  const bool vr = sampling == 2;
+  if (vr) {
+    NFSP_REQUIRE(vr_lds(T->nn, T->ndec) <= 64 * 1024, "MCCFR tables exceed 64 KB of LDS");
+    NFSP_REQUIRE(T->ndec <= VR_FRAME_MAX_ROWS, "a decision row does not fit a frame");
+  } else if (os) {
     NFSP_REQUIRE(os_lds(T->nn, T->ndec) <= 64 * 1024, "MCCFR tables exceed 64 KB of LDS");
     NFSP_REQUIRE(T->ndec <= FRAME_MAX_ROWS, "a decision row does not fit a frame");
   } else {
@@ -581,7 +914,7 @@ int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os
   for (int k = 0; k < n; ++k) h->max_walkers = std::max(h->max_walkers, (int)cfgs[k].walkers);
   std::vector<double>& eps = h->eps;
   if (os) {
-    h->sampling = 1;
+    h->sampling = sampling;
     h->os_cfgs.assign(os, os + n);
     for (int k = 0; k < n; ++k) eps.insert(eps.end(), {os[k].epsilon, os[k].epsilon / 2.0, os[k].epsilon / 3.0});
   }
@@ -592,6 +925,13 @@ int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os
   if (e == hipSuccess) e = hipMalloc(&h->counts, b_counts);
   if (e == hipSuccess) e = hipMalloc(&h->dev_cfg, sizeof(nfsp_mccfr_cfg) * n);
   if (e == hipSuccess && os) e = hipMalloc(&h->dev_eps, sizeof(double) * eps.size());
+  if (vr) {
+    for (float p : H->pay) h->maxpay = std::max(h->maxpay, (double)(p < 0 ? -p : p));
+    if (e == hipSuccess) e = hipMalloc(&h->bstate, b_state);
+    if (e == hipSuccess) e = hipMalloc(&h->btab, sizeof(double) * n9 * n);
+    if (e == hipSuccess) e = hipMemsetAsync(h->bstate, 0, b_state, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->btab, 0, sizeof(double) * n9 * n, ctx->stream);   // B = 0.0
+  }
   if (e == hipSuccess) e = hipMemsetAsync(h->state, 0, b_state, ctx->stream);
   if (e == hipSuccess) e = hipMemsetAsync(h->counts, 0, b_counts, ctx->stream);
   if (e == hipSuccess)
@@ -636,6 +976,23 @@ extern "C" int nfsp_mccfr_os_create(nfsp_ctx* ctx, const nfsp_mccfr_os_cfg* cfgs
   return create_handle(ctx, plain.data(), cfgs, n, out);
 }
 
+extern "C" int nfsp_mccfr_vr_create(nfsp_ctx* ctx, const nfsp_mccfr_vr_cfg* cfgs, int n, nfsp_mccfr** out) {
+  NFSP_REQUIRE(cfgs && out, "null argument");
+  NFSP_REQUIRE(n >= 1 && n <= NFSP_MCCFR_MAX_RUNS, "n must be in 1 .. NFSP_MCCFR_MAX_RUNS");
+  NFSP_REQUIRE(ctx, "null argument");
+  int rc = nfsp_mccfr_vr_cfgs_check(ctx->game, cfgs, n, 0);
+  if (rc != NFSP_OK) return rc;
+  std::vector<nfsp_mccfr_cfg> plain(n);
+  std::vector<nfsp_mccfr_os_cfg> os(n);
+  for (int k = 0; k < n; ++k) {
+    plain[k] = nfsp_mccfr_cfg{cfgs[k].seed, cfgs[k].walkers, 0};
+    os[k] = nfsp_mccfr_os_cfg{cfgs[k].seed, cfgs[k].walkers, 0, cfgs[k].epsilon};
+  }
+  rc = create_handle(ctx, plain.data(), os.data(), n, out, 2);
+  if (rc == NFSP_OK) (*out)->vr_cfgs.assign(cfgs, cfgs + n);
+  return rc;
+}
+
 extern "C" int nfsp_mccfr_sampling(nfsp_mccfr* h, int* out) {
   NFSP_REQUIRE(h && out, "null argument");
   *out = h->sampling;
@@ -646,18 +1003,36 @@ extern "C" int nfsp_mccfr_run(nfsp_mccfr* h, int64_t iters) {
   NFSP_REQUIRE(iters >= 0, "iters must be >= 0");
   NFSP_REQUIRE(h, "null argument");
   NFSP_REQUIRE(iters <= INT64_MAX - h->iterations, "overflow: iters too large");
-  int rc = h->sampling ? nfsp_mccfr_os_cfgs_check(h->ctx->game, h->os_cfgs.data(), h->n, h->iterations + iters)
-                       : nfsp_mccfr_cfgs_check(h->ctx->game, h->cfgs.data(), h->n, h->iterations + iters);
+  int rc = h->sampling == 2   ? nfsp_mccfr_vr_cfgs_check(h->ctx->game, h->vr_cfgs.data(), h->n, h->iterations + iters)
+           : h->sampling == 1 ? nfsp_mccfr_os_cfgs_check(h->ctx->game, h->os_cfgs.data(), h->n, h->iterations + iters)
+                              : nfsp_mccfr_cfgs_check(h->ctx->game, h->cfgs.data(), h->n, h->iterations + iters);
   if (rc != NFSP_OK) return rc;
   const ExTables* T = nullptr;
   rc = device_tables(h->ctx, &T);
   if (rc != NFSP_OK) return rc;
   const dim3 grid(nfsp_blocks(h->max_walkers, NFSP_MCCFR_WG_WALKERS), h->n);
-  const size_t lds = h->sampling ? os_lds(T->nn, T->ndec) : walk_lds(T->nn, T->ndec, h->nterm);
+  const size_t lds = h->sampling == 2   ? vr_lds(T->nn, T->ndec)
+                     : h->sampling == 1 ? os_lds(T->nn, T->ndec)
+                                        : walk_lds(T->nn, T->ndec, h->nterm);
   for (int64_t it = 0; it < iters; ++it) {
     for (int i = 0; i < 2; ++i) {
       const uint64_t hh = 2 * (uint64_t)h->iterations + i;
-      if (h->sampling) {
+      if (h->sampling == 2) {
+        VrArgs A{};
+        A.T = *T;
+        A.cfg = h->dev_cfg;
+        A.eps = h->dev_eps;
+        A.tabs = h->tabs;
+        A.btab = h->btab;
+        A.state = h->state;
+        A.bstate = h->bstate;
+        A.counts = h->counts;
+        A.h_lo = (uint32_t)hh;
+        A.h_hi = (uint32_t)(hh >> 32);
+        A.seat = i;
+        k_mccfr_vr_walk<<<grid, WALK_THREADS, lds, h->ctx->stream>>>(A);
+        NFSP_LAUNCHED("k_mccfr_vr_walk");
+      } else if (h->sampling == 1) {
         OsArgs A{};
         A.T = *T;
         A.cfg = h->dev_cfg;
@@ -685,6 +1060,7 @@ extern "C" int nfsp_mccfr_run(nfsp_mccfr* h, int64_t iters) {
         NFSP_LAUNCHED("k_mccfr_walk");
       }
       rc = launch_apply(h, *T, 1);
+      if (rc == NFSP_OK && h->sampling == 2) rc = launch_vr_apply(h);
       if (rc != NFSP_OK) return rc;
     }
     h->iterations += 1;
@@ -729,6 +1105,42 @@ extern "C" int nfsp_mccfr_state(nfsp_mccfr* h, int run, int64_t* host_R, int64_t
   return NFSP_OK;
 }
 
+extern "C" int nfsp_mccfr_baseline(nfsp_mccfr* h, int run, int64_t* host_Bs, int64_t* host_Bn) {
+  NFSP_REQUIRE(run >= 0, "run out of range");
+  NFSP_REQUIRE(h && host_Bs && host_Bn, "null argument");
+  NFSP_REQUIRE(h->sampling == 2, "not a baseline-corrected handle (nfsp_mccfr_vr_create)");
+  NFSP_REQUIRE(run < h->n, "run out of range");
+  const size_t n9 = 9 * (size_t)h->ndec;
+  const long long* s = h->bstate + (size_t)run * 4 * n9;
+  NFSP_HIP(hipMemcpyAsync(host_Bs, s, sizeof(int64_t) * n9, hipMemcpyDeviceToHost, h->ctx->stream));
+  NFSP_HIP(hipMemcpyAsync(host_Bn, s + n9, sizeof(int64_t) * n9, hipMemcpyDeviceToHost, h->ctx->stream));
+  NFSP_HIP(hipStreamSynchronize(h->ctx->stream));
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_mccfr_set_baseline(nfsp_mccfr* h, int run, const int64_t* host_Bs, const int64_t* host_Bn) {
+  NFSP_REQUIRE(run >= 0, "run out of range");
+  NFSP_REQUIRE(h && host_Bs && host_Bn, "null argument");
+  NFSP_REQUIRE(h->sampling == 2, "not a baseline-corrected handle (nfsp_mccfr_vr_create)");
+  NFSP_REQUIRE(run < h->n, "run out of range");
+  const size_t n9 = 9 * (size_t)h->ndec;
+  const int64_t most = (int64_t)1 << 61;  // half of what the run's budget keeps an entry within
+  for (size_t k = 0; k < n9; ++k) {
+    NFSP_REQUIRE(host_Bn[k] >= 0, "a baseline count is negative");
+    NFSP_REQUIRE(host_Bn[k] != 0 || host_Bs[k] == 0, "a baseline sum is not 0 where its count is 0");
+    NFSP_REQUIRE(host_Bn[k] <= most && host_Bs[k] <= most && host_Bs[k] >= -most,
+                 "a baseline sum or count is beyond 2^61");
+  }
+  // the deltas are 0 between runs: the apply adds nothing, and writes the B of the new tables
+  long long* s = h->bstate + (size_t)run * 4 * n9;
+  NFSP_HIP(hipMemcpyAsync(s, host_Bs, sizeof(int64_t) * n9, hipMemcpyHostToDevice, h->ctx->stream));
+  NFSP_HIP(hipMemcpyAsync(s + n9, host_Bn, sizeof(int64_t) * n9, hipMemcpyHostToDevice, h->ctx->stream));
+  const int rc = launch_vr_apply(h);
+  if (rc != NFSP_OK) return rc;
+  NFSP_HIP(hipStreamSynchronize(h->ctx->stream));
+  return NFSP_OK;
+}
+
 extern "C" int nfsp_mccfr_destroy(nfsp_mccfr* h) {
   NFSP_REQUIRE(h, "null argument");
   if (h->state) (void)hipFree(h->state);
@@ -736,6 +1148,8 @@ extern "C" int nfsp_mccfr_destroy(nfsp_mccfr* h) {
   if (h->counts) (void)hipFree(h->counts);
   if (h->dev_cfg) (void)hipFree(h->dev_cfg);
   if (h->dev_eps) (void)hipFree(h->dev_eps);
+  if (h->bstate) (void)hipFree(h->bstate);
+  if (h->btab) (void)hipFree(h->btab);
   delete h;
   return NFSP_OK;
 }

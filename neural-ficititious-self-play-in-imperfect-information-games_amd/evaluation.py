@@ -26,7 +26,8 @@ approximates, with an exact best response and exact averaging.  ``MccfrSolver`` 
 external-sampling MCCFR on it (``nfsp_mccfr_*``, csrc/mccfr.hip): the sampled tabular yardstick,
 counted in traversals and terminals visited, to set beside the engine's curves in hands;
 ``MccfrOsSolver`` runs outcome sampling on the same handle (``nfsp_mccfr_os_*``), whose traversal
-is one sampled hand, so its cost is in the engine's own unit.
+is one sampled hand, so its cost is in the engine's own unit, and ``MccfrVrSolver`` the same
+paths with baseline-corrected values (``nfsp_mccfr_vr_*``, VR-MCCFR).
 
 ``MemoryTable`` is a memory counted per information set on the device (``nfsp_memory_table``,
 csrc/memtab.hip): M_SL as the tabular average strategy the AR net is a fit of, M_RL as what the
@@ -854,6 +855,47 @@ class MccfrOsSolver(MccfrSolver):
         h = native.P()
         native.check(ctx.L.nfsp_mccfr_os_create(ctx.h, arr, self.n, C.byref(h)), "nfsp_mccfr_os_create")
         self.h = h
+
+
+class MccfrVrSolver(MccfrOsSolver):
+    """Baseline-corrected outcome sampling, VR-MCCFR, on the same handle (``nfsp_mccfr_vr_create``):
+    outcome sampling's paths, hands and ``cfgs``, with the values on the way back up corrected by a
+    learned baseline at every decision.  ``baseline(k)`` is run k's (Bs, Bn), the int64 sums
+    (``native.MCCFR_Q`` per chip) and counts ``[ndec, 3, 3]`` in the acting seat's perspective,
+    ``set_baseline(k, Bs, Bn)`` replaces them, and ``baseline_table(k)`` is the clamped f64 table
+    the next half-iteration uses.  Everything else is ``MccfrOsSolver``'s."""
+
+    def __init__(self, ctx, cfgs=((1, 1024, 0.6),)):
+        _Solver.__init__(self, ctx)
+        self.cfgs = [(int(seed) & (2**64 - 1), int(w), float(eps)) for seed, w, eps in cfgs]
+        self.n = len(self.cfgs)
+        arr = (native.MccfrVrCfg * max(self.n, 1))(*[native.MccfrVrCfg(seed, w, 0, eps) for seed, w, eps in self.cfgs])
+        h = native.P()
+        native.check(ctx.L.nfsp_mccfr_vr_create(ctx.h, arr, self.n, C.byref(h)), "nfsp_mccfr_vr_create")
+        self.h = h
+
+    def baseline(self, run: int = 0) -> tuple:
+        Bs = np.zeros((self.tree.ndec, 3, 3), np.int64)
+        Bn = np.zeros((self.tree.ndec, 3, 3), np.int64)
+        native.check(self.ctx.L.nfsp_mccfr_baseline(self.h, int(run), Bs.ctypes.data_as(native.P),
+                                                    Bn.ctypes.data_as(native.P)), "nfsp_mccfr_baseline")
+        return Bs, Bn
+
+    def set_baseline(self, run: int, Bs, Bn) -> "MccfrVrSolver":
+        shape = (self.tree.ndec, 3, 3)
+        Bs, Bn = (np.ascontiguousarray(x, np.int64) for x in (Bs, Bn))
+        if Bs.shape != shape or Bn.shape != shape:
+            raise ValueError("Bs and Bn must be [ndec, 3, 3]")
+        native.check(self.ctx.L.nfsp_mccfr_set_baseline(self.h, int(run), Bs.ctypes.data_as(native.P),
+                                                        Bn.ctypes.data_as(native.P)), "nfsp_mccfr_set_baseline")
+        return self
+
+    def baseline_table(self, run: int = 0) -> np.ndarray:
+        """B = clamp(Bs / (Bn Q), -P, P), 0 where Bn is 0, P the game's max|pay| (include/nfsp.h)."""
+        Bs, Bn = self.baseline(run)
+        P = float(np.abs(self.tree.pay).max())
+        den = np.where(Bn > 0, Bn, 1).astype(np.float64) * float(native.MCCFR_Q)
+        return np.where(Bn > 0, np.clip(Bs.astype(np.float64) / den, -P, P), 0.0)
 
 
 class CfrSolver(_Solver):

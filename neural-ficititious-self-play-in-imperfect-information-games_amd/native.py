@@ -110,6 +110,12 @@ class MccfrOsCfg(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("walkers", C.c_int32), ("reserved", C.c_int32), ("epsilon", C.c_double)]
 
 
+class MccfrVrCfg(C.Structure):
+    """``nfsp_mccfr_vr_cfg``: one baseline-corrected outcome-sampling run's seed, walkers per
+    half-iteration and exploration rate"""
+    _fields_ = [("seed", C.c_uint64), ("walkers", C.c_int32), ("reserved", C.c_int32), ("epsilon", C.c_double)]
+
+
 class MemSegment(C.Structure):
     """``nfsp_mem_segment``: n packed records (SlRec 16 B / RlRec 32 B) at a device address"""
     _fields_ = [("dev_recs", P), ("n", I64)]
@@ -203,6 +209,10 @@ SIGNATURES = {
     "nfsp_mccfr_os_cfgs_check": (I32, [I32, C.POINTER(MccfrOsCfg), I32, I64]),
     "nfsp_mccfr_os_create": (I32, [P, C.POINTER(MccfrOsCfg), I32, C.POINTER(P)]),
     "nfsp_mccfr_sampling": (I32, [P, C.POINTER(I32)]),
+    "nfsp_mccfr_vr_cfgs_check": (I32, [I32, C.POINTER(MccfrVrCfg), I32, I64]),
+    "nfsp_mccfr_vr_create": (I32, [P, C.POINTER(MccfrVrCfg), I32, C.POINTER(P)]),
+    "nfsp_mccfr_baseline": (I32, [P, I32, P, P]),
+    "nfsp_mccfr_set_baseline": (I32, [P, I32, P, P]),
     "nfsp_engine_set_loss_log": (I32, [P, I32]),
     "nfsp_engine_losses": (I32, [P, P]),
     "nfsp_engine_set_timing": (I32, [P, I32]),

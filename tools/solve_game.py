@@ -11,6 +11,8 @@ csrc/xfp.hip): the algorithm NFSP approximates, with an exact best response and 
     python tools/solve_game.py --solver mccfr --time
     python tools/solve_game.py --game leduc --solver mccfr-os --epsilon 0.6 --walkers 1024 --seeds 4 --iters 32768
     python tools/solve_game.py --solver mccfr-os --time
+    python tools/solve_game.py --game leduc --solver mccfr-vr --epsilon 0.6 --walkers 1024 --seeds 4 --iters 16384
+    python tools/solve_game.py --solver mccfr-vr --time
 
 eq.npz holds ``table`` [ndec, 3 ranks, 3 actions] (rows as evaluation.GameTree's; usable as
 evaluation.Policy.table), ``game``, and per checkpoint (--every, doubling by default)
@@ -37,6 +39,12 @@ handle, --epsilon the exploration rate of the updating seat's own actions.  A tr
 sampled hand and one terminal, so its lines carry ``hands`` (= traversals) and ``epsilon`` beside
 what mccfr's carry, and --time adds ``hands_per_s``.  W x iterations is bounded by the int64
 fixed point (include/nfsp.h): 197,912,092 on Leduc at --epsilon 0.6.
+
+--solver mccfr-vr: baseline-corrected outcome sampling, VR-MCCFR (evaluation.MccfrVrSolver,
+k_mccfr_vr_walk), with mccfr-os's options and output columns, --time included: the same sampled
+hands, the values on the way back up corrected by a learned baseline at every decision.  Its
+corrected values are larger than one pay, so its budget is smaller: W x iterations up to
+29,142,433 on Leduc at --epsilon 0.6.
 """
 import argparse
 import json
@@ -50,13 +58,15 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 
-def time_mccfr(ev, nat, epsilon=None, walkers=1 << 20, repeats=5):
+def time_mccfr(ev, nat, epsilon=None, walkers=1 << 20, repeats=5, baselines=False):
     """Best of ``repeats`` single iterations (2 W traversals each) after a warm-up; outcome
-    sampling where ``epsilon`` is given."""
+    sampling where ``epsilon`` is given, baseline-corrected with ``baselines``."""
     import torch
     ctx = nat.Context(1, game=nat.GAME_LEDUC)
     if epsilon is None:
         solver = ev.MccfrSolver(ctx, [(1, walkers)]).run(1)
+    elif baselines:
+        solver = ev.MccfrVrSolver(ctx, [(1, walkers, epsilon)]).run(1)
     else:
         solver = ev.MccfrOsSolver(ctx, [(1, walkers, epsilon)]).run(1)
     best = None
@@ -72,7 +82,8 @@ def time_mccfr(ev, nat, epsilon=None, walkers=1 << 20, repeats=5):
         rec = {"ms": ms, "traversals": after[0] - before[0], "terminals": after[1] - before[1]}
         if best is None or ms < best["ms"]:
             best = rec
-    best.update(game="leduc", solver="mccfr" if epsilon is None else "mccfr-os", walkers=walkers, repeats=repeats,
+    name = "mccfr" if epsilon is None else "mccfr-vr" if baselines else "mccfr-os"
+    best.update(game="leduc", solver=name, walkers=walkers, repeats=repeats,
                 traversals_per_s=best["traversals"] / (best["ms"] * 1e-3),
                 terminals_per_s=best["terminals"] / (best["ms"] * 1e-3))
     if epsilon is not None:
@@ -84,7 +95,7 @@ def time_mccfr(ev, nat, epsilon=None, walkers=1 << 20, repeats=5):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--game", default="leduc", choices=["leduc", "kuhn"])
-    ap.add_argument("--solver", default="cfr", choices=["cfr", "xfp", "mccfr", "mccfr-os"])
+    ap.add_argument("--solver", default="cfr", choices=["cfr", "xfp", "mccfr", "mccfr-os", "mccfr-vr"])
     ap.add_argument("--iters", type=int, default=1024)
     ap.add_argument("--every", type=int, default=0, help="checkpoint every K iterations (default: 1, 2, 4, ...)")
     ap.add_argument("--eta", type=float, default=0.0, help="xfp: anticipatory parameter, in [0, 1)")
@@ -92,9 +103,9 @@ def main():
     ap.add_argument("--runs", type=int, default=1, help="xfp: runs in one launch, eta spaced over [0, --eta]")
     ap.add_argument("--walkers", type=int, default=1024, help="mccfr: traversals per seat and iteration (even)")
     ap.add_argument("--seeds", type=int, default=1, help="mccfr: independent runs, seeds 1 .. K")
-    ap.add_argument("--epsilon", type=float, default=0.6, help="mccfr-os: exploration rate, in [0.0625, 1]")
+    ap.add_argument("--epsilon", type=float, default=0.6, help="mccfr-os, mccfr-vr: exploration rate, in [0.0625, 1]")
     ap.add_argument("--time", action="store_true",
-                    help="mccfr, mccfr-os: traversals/s and terminals/s, Leduc at W = 2^20")
+                    help="mccfr, mccfr-os, mccfr-vr: traversals/s and terminals/s, Leduc at W = 2^20")
     ap.add_argument("--out", default=None, metavar="PATH")
     args = ap.parse_args()
     import __graft_entry__
@@ -102,15 +113,16 @@ def main():
     ev, nat = pkg.evaluation, pkg.native
     game = nat.GAME_KUHN if args.game == "kuhn" else nat.GAME_LEDUC
     if args.time:
-        if args.solver not in ("mccfr", "mccfr-os"):
-            ap.error("--time is for --solver mccfr and mccfr-os")
-        return time_mccfr(ev, nat, args.epsilon if args.solver == "mccfr-os" else None)
+        if args.solver not in ("mccfr", "mccfr-os", "mccfr-vr"):
+            ap.error("--time is for --solver mccfr, mccfr-os and mccfr-vr")
+        return time_mccfr(ev, nat, None if args.solver == "mccfr" else args.epsilon, baselines=args.solver == "mccfr-vr")
     ctx = nat.Context(1, game=game)
     xfp = args.solver == "xfp"
-    outcome = args.solver == "mccfr-os"
+    outcome = args.solver in ("mccfr-os", "mccfr-vr")
     mccfr = args.solver == "mccfr" or outcome
     if outcome:
-        solver = ev.MccfrOsSolver(ctx, [(seed, args.walkers, args.epsilon) for seed in range(1, args.seeds + 1)])
+        solver = (ev.MccfrVrSolver if args.solver == "mccfr-vr" else ev.MccfrOsSolver)(
+            ctx, [(seed, args.walkers, args.epsilon) for seed in range(1, args.seeds + 1)])
     elif mccfr:
         solver = ev.MccfrSolver(ctx, [(seed, args.walkers) for seed in range(1, args.seeds + 1)])
     elif xfp:
