@@ -486,7 +486,15 @@ int nfsp_group_average_ar(nfsp_group* g);
  * replica order from +0, and W0 <- that.  every = 0: off.  NFSP_GROUP_AVG_AR at creation is
  * nets = AR, every = cfg.slices (once per step, after its last slice), scale = 1 / R.  The first
  * exchange of a net (or nfsp_group_average_ar) copies replica 0's net (with BR also its target
- * net) to every replica instead -- also the first after a call that turns the net on again. */
+ * net) to every replica instead -- also the first after a call that turns the net on again.
+ *   Resume: a group's blob holds W0 and which nets have one, not the cadence.  The first
+ * nfsp_group_set_exchange after nfsp_group_load_state (no step or exchange in between) continues
+ * the nets whose W0 the blob restored instead of starting them over: re-issuing the saved run's
+ * exchange goes on bit-identical to the uninterrupted run, AR and BR alike.  (A broadcast there
+ * would replace every replica's own target net by replica 0's: the BR nets are equal at a step
+ * boundary, the target nets are not -- each replica syncs its own at its own update count.)
+ * Any later call that turns a net on again broadcasts as above.
+ *   tests/exchange_ref.py restates this rule and the group's bookkeeping around it in numpy. */
 #define NFSP_XCHG_AR 1u
 #define NFSP_XCHG_BR 2u
 int nfsp_group_set_exchange(nfsp_group* g, unsigned nets, int every, float scale);

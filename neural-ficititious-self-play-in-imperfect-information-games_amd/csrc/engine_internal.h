@@ -353,6 +353,7 @@ struct GroupState {
   nfsp_engine* const* eng;     // [R]
   float* w0;                   // [3 nets][2 agents][NP], device
   unsigned* w0_valid;
+  unsigned* w0_loaded;         // the nets whose W0 a load just restored (nfsp_group_set_exchange)
   int64_t* calls;
   int xchg_every;
 };

@@ -48,6 +48,8 @@ struct nfsp_group {
   float** d_war = nullptr;       // [3 nets][R][2] weight pointers (k_group_xchg)
   float* w0 = nullptr;           // [3][2][NP] the exchanged nets after the last exchange
   unsigned w0_valid = 0;         // nets (NFSP_XCHG_*) broadcast from replica 0 already
+  unsigned w0_loaded = 0;        // nets whose W0 nfsp_group_load_state restored, until the next
+                                 // nfsp_group_set_exchange, exchange or step
   unsigned xchg_nets = 0;        // nfsp_group_set_exchange
   int xchg_every = 0;
   float xchg_scale = 1.f;
@@ -235,7 +237,7 @@ namespace nfsp {
 namespace eng {
 int group_state(nfsp_group* g, GroupState* out) {
   NFSP_REQUIRE(g && out, "null argument");
-  *out = GroupState{g->ctx, g->R, g->flags, g->eng.data(), g->w0, &g->w0_valid, &g->calls, g->xchg_every};
+  *out = GroupState{g->ctx, g->R, g->flags, g->eng.data(), g->w0, &g->w0_valid, &g->w0_loaded, &g->calls, g->xchg_every};
   return NFSP_OK;
 }
 
@@ -282,6 +284,7 @@ extern "C" int nfsp_group_set_act_table(nfsp_group* g, int replica, int agent, i
 // the group's exchange (k_group_xchg) on stream `s`
 static int group_xchg_launch(nfsp_group* g, hipStream_t s) {
   const unsigned nets = g->xchg_nets ? g->xchg_nets : NFSP_XCHG_AR;
+  g->w0_loaded = 0;
   // nets not broadcast yet take replica 0's (a BR net with its target net)
   unsigned bc = nets & ~g->w0_valid;
   if (bc & NFSP_XCHG_BR) bc |= 4u;
@@ -307,9 +310,13 @@ extern "C" int nfsp_group_set_exchange(nfsp_group* g, unsigned nets, int every, 
                "nfsp_group_set_exchange: the replicas' cfgs differ (a heterogeneous group has no exchange)");
   // a net this call turns on starts like the rank path's (AvgPolicyExchange broadcasts rank 0's
   // nets, then nfsp_engine_set_exchange takes them as W0): its next exchange copies replica 0's
-  // net everywhere instead of applying deltas against a W0 from before the exchange was off
+  // net everywhere instead of applying deltas against a W0 from before the exchange was off.
+  // Not the first call after nfsp_group_load_state: the cadence is a session setting, so a
+  // resumed run re-issues it, and the nets whose W0 the blob restored go on from that W0 -- a
+  // broadcast would replace the replicas' own target nets by replica 0's.
   const unsigned on = every ? nets : 0;
-  g->w0_valid &= ~(on & ~g->xchg_nets);
+  g->w0_valid &= ~(on & ~g->xchg_nets & ~g->w0_loaded);
+  g->w0_loaded = 0;
   g->xchg_nets = on;
   g->xchg_every = every;
   g->xchg_scale = scale;
@@ -674,6 +681,7 @@ extern "C" int nfsp_group_get_timings(nfsp_group* g, double* ms, int64_t* launch
 extern "C" int nfsp_group_step(nfsp_group* g) {
   NFSP_REQUIRE(g, "null argument");
   int rc;
+  g->w0_loaded = 0;                     // the nets move on: a later set_exchange starts over
   if (g->xchg_nets & ~g->w0_valid)      // common nets before the first exchange
     if ((rc = nfsp_group_average_ar(g)) != NFSP_OK) return rc;
   const int K = g->eng[0]->slices;

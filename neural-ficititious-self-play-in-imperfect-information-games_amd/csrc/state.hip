@@ -669,6 +669,7 @@ extern "C" int nfsp_group_load_state(nfsp_group* g, const void* host_buf, int64_
   for (int r = 0; r < G.R; ++r)
     if ((rc = engine_restore(G.eng[r], v, v.engine_sec(r))) != NFSP_OK) return rc;
   *G.w0_valid = gr.w0_valid;
+  *G.w0_loaded = gr.w0_valid;
   // calls matters modulo the exchange cadence only, and a boundary is a multiple of it
   *G.calls = (G.xchg_every > 0 && gr.calls % G.xchg_every != 0) ? 0 : gr.calls;
   // prove the device state: the group record on the host, w0 and every replica in place

@@ -210,6 +210,77 @@ def test_group_resume_restores_the_exchange_base(pkg, tmp_path):
     assert len(set(c.state_digest())) == 3
 
 
+def test_group_resume_with_a_br_exchange(pkg, tmp_path):
+    """A group exchanging AR and BR nets after every slice, saved, loaded and its exchange
+    re-issued (the cadence is a session setting), continues as the uninterrupted run.  The
+    re-issued nfsp_group_set_exchange must not start the BR exchange over: a broadcast of replica
+    0's BR net takes its target net along, and the target nets are each replica's own (their
+    syncs fall mid-call at each replica's own update count) -- asserted at the save, without
+    which the case could not fail."""
+    XB = pkg.native.XCHG_AR | pkg.native.XCHG_BR
+
+    def group():
+        g = pkg.engine.EngineGroup(3, slices=2, seed=909, init_seed=7, **BASE)
+        g.set_exchange(XB, every=1)
+        return g
+    b = group()
+    n1 = step_until_meaningful(b, probe=b.replicas[0])
+    torch.cuda.synchronize()
+    at_save = [nets(e) for e in b.replicas]              # [a * 3 + net]
+    for r in (1, 2):
+        for a in (0, 1):
+            assert np.array_equal(bits(at_save[r][3 * a]), bits(at_save[0][3 * a]))            # one AR net
+            assert np.array_equal(bits(at_save[r][3 * a + 1]), bits(at_save[0][3 * a + 1]))    # one BR net
+            assert not np.array_equal(bits(at_save[r][3 * a + 2]), bits(at_save[0][3 * a + 2]))   # own targets
+    b.save(tmp_path / "g.nfsp")
+    b.close()
+    ck = pkg.checkpoint.read(tmp_path / "g.nfsp")
+    assert ck["group"]["R"] == 3 and ck["group"]["w0_valid"] == XB and ck["group"]["calls"] == 2 * n1
+    c = pkg.engine.EngineGroup.from_checkpoint(tmp_path / "g.nfsp", init_seed=50)
+    c.set_exchange(XB, every=1)
+    a = group()
+    for _ in range(n1):
+        a.step()
+    assert a.state_digest() == c.state_digest()
+    for step in range(2):
+        a.step()
+        c.step()
+        torch.cuda.synchronize()
+        for r in range(3):
+            na, nc = nets(a.replicas[r]), nets(c.replicas[r])
+            for k in range(6):
+                d = np.flatnonzero(na[k].view(np.uint32) != nc[k].view(np.uint32))
+                assert not len(d), (f"step {step} replica {r} agent {k // 3} net {('AR', 'BR', 'target')[k % 3]} "
+                                    f"index {d[0]}: {na[k][d[0]]!r} uninterrupted, {nc[k][d[0]]!r} resumed")
+    assert a.state_digest() == c.state_digest()
+    assert len(set(c.state_digest())) == 3
+    # on, off, on after a load still starts over: replica 0's BR and target nets everywhere
+    c.set_exchange(XB, every=0)
+    c.step()
+    c.set_exchange(XB, every=1)
+    torch.cuda.synchronize()
+    w_r0 = nets(c.replicas[0])
+    c.average_ar()
+    torch.cuda.synchronize()
+    for r in (1, 2):
+        assert np.array_equal(bits(nets(c.replicas[r])), bits(w_r0))
+    a.close()
+    c.close()
+    # a load honours the blob's W0 only while the nets are the blob's: after a step without the
+    # exchange (the replicas' nets apart) a set_exchange starts over
+    d = pkg.engine.EngineGroup.from_checkpoint(tmp_path / "g.nfsp", init_seed=51)
+    d.step()
+    d.set_exchange(XB, every=1)
+    torch.cuda.synchronize()
+    w_r0 = nets(d.replicas[0])
+    assert not np.array_equal(bits(nets(d.replicas[1])[1]), bits(w_r0[1]))
+    d.average_ar()
+    torch.cuda.synchronize()
+    for r in (1, 2):
+        assert np.array_equal(bits(nets(d.replicas[r])), bits(w_r0))
+    d.close()
+
+
 def test_exchange_continues_after_a_load(pkg, tmp_path):
     """A host-callback exchange that is not the identity (S = 2 D, scale 0.75, every slice):
     re-issued after the load, the continuation is the uninterrupted run's."""

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from engine_ref import STAT_KEYS, mem, nets
+from exchange_ref import group_exchange
 
 pytestmark = pytest.mark.gpu
 
@@ -82,11 +83,7 @@ def test_group_ar_exchange(pkg):
             e.step()
         torch.cuda.synchronize()
         for a in (0, 1):
-            base = w0[a].astype(np.float32)
-            s = np.zeros_like(base)
-            for e in solo:
-                s = (s + (e.get_weights(a, 0) - base)).astype(np.float32)
-            exp = (base + s * np.float32(1.0 / R)).astype(np.float32)
+            exp = group_exchange(np.stack([e.get_weights(a, 0) for e in solo]), w0[a], np.float32(1.0 / R))
             for r in range(R):
                 assert np.array_equal(g.replicas[r].get_weights(a, 0), exp), (step, a, r)
             w0[a] = exp
