@@ -946,6 +946,69 @@ int nfsp_mccfr_baseline(nfsp_mccfr* h, int run, int64_t* host_Bs /*[ndec][3][3]*
 int nfsp_mccfr_set_baseline(nfsp_mccfr* h, int run, const int64_t* host_Bs /*[ndec][3][3]*/,
                             const int64_t* host_Bn /*[ndec][3][3]*/);
 
+/* ---- regret matching+ and linear averaging on the same handle (csrc/mccfr.hip k_mccfr_x_apply) ----
+ * Two of CFR+'s three ingredients (Tammelin 2014; the third, alternating updates, every kind here
+ * has) on any of the three sampling kinds; with sampling 2 this is VR-MCCFR+ (Schmid et al. 2019).
+ * A fourth way to create an nfsp_mccfr.  `sampling` is the handle's: one walk kernel serves a
+ * launch, so every run of a handle names the same one.  `regret` and `average` are per run.
+ * Steps 1 and 2 are exactly the sampling kind's, above: the draws, the choices, the dealer, the
+ * deal, dR, dS, dBs, dBn and the counts, bit for bit.  Step 3 of a half-iteration changes.  t is
+ * the number of iterations completed before the one in progress, the same for both of its
+ * half-iterations.  Per entry, by the one thread that owns it, in this order:
+ *   R = R + dR                                int64; under NFSP_MCCFR_REGRET_PLUS then
+ *   R = max(R, 0)                             int64.  The floor is applied once per half-iteration,
+ *                                             to the sum over the W walkers: the declared
+ *                                             mini-batch form, sigma was frozen for them all.
+ *   S = S + dS                                int64, as before.
+ *   Sw = Sw + (double)(t + 1) * (double)dS    f64, one multiplication and one addition, no FMA
+ *                                             contraction.  Sw [ndec][3][3] is 0.0 at creation.
+ *   for sampling 2: Bs += dBs, Bn += dBn, the next B, as k_mccfr_vr_apply does.
+ * The next sigma comes from the new R by the unchanged step 1.  Two averages, both by the rule of
+ * nfsp_mccfr_average (normalised per row, uniform where the row's sum is 0): the uniform one from
+ * (double)S, the linear one from Sw.  nfsp_mccfr_average returns the one cfg.average names,
+ * nfsp_mccfr_average_of either, so one run scores both on identical sample paths.  Sw and both
+ * averages are kept whatever `average` is.
+ * Why Sw is f64: a linearly weighted int64 sum would carry the worst-case bound W omega Q T^2 / 2,
+ * which on Leduc at eps = 0.6 allows about 1,390 iterations at W = 2^10.  dS is an integer sum and
+ * does not depend on the grid, and the f64 accumulation over half-iterations is done by a single
+ * owner in stream order: Sw is bit-reproducible whatever the grid.  It is deterministic, not
+ * exact: its relative error is of order T 2^-53 after T iterations, and it needs no refusal.
+ * Overflow is the sampling kind's own bound, unchanged, and nfsp_mccfr_run re-checks it:
+ * |max(R + dR, 0)| <= |R + dR| <= |R| + |dR|, so by induction |R| stays within the sum of |dR|
+ * over the half-iterations so far, which is what that bound bounds.
+ * k_mccfr_x_apply is the one apply launch of a half-iteration of this kind, the baseline's part
+ * included: an iteration is 4 launches where nfsp_mccfr_vr_create's is 6.  One thread per
+ * (row, rank); no workgroup waits for another.  tests/mccfr_x_ref.py restates the rule in numpy;
+ * R, S, Bs, Bn, the counts and Sw (as its 64 bits) agree to the bit. */
+#define NFSP_MCCFR_REGRET_PLAIN 0
+#define NFSP_MCCFR_REGRET_PLUS 1
+#define NFSP_MCCFR_AVG_UNIFORM 0
+#define NFSP_MCCFR_AVG_LINEAR 1
+typedef struct {
+  uint64_t seed;
+  int32_t walkers;                      /* W: even, 2 .. NFSP_MCCFR_MAX_WALKERS */
+  int32_t sampling;                     /* 0 external, 1 outcome, 2 outcome with baselines: nfsp_mccfr_sampling's numbers */
+  double epsilon;                       /* sampling 1, 2: in [NFSP_MCCFR_OS_EPS_MIN, 1]; sampling 0: must be 0.0 */
+  int32_t regret;                       /* NFSP_MCCFR_REGRET_* */
+  int32_t average;                      /* NFSP_MCCFR_AVG_*: the table nfsp_mccfr_average returns */
+} nfsp_mccfr_x_cfg;                     /* 32 bytes */
+/* Host only, as nfsp_mccfr_cfgs_check: every field of every cfg (a message names
+ * nfsp_mccfr_x_cfg.<field>; a run whose sampling differs from run 0's is named with its run), then
+ * the sampling kind's own overflow bound. */
+int nfsp_mccfr_x_cfgs_check(int game, const nfsp_mccfr_x_cfg* cfgs /*[n]*/, int n, int64_t iters);
+/* The handle is an nfsp_mccfr: nfsp_mccfr_run / _iterations / _counts / _average / _state /
+ * _sampling / _destroy serve it unchanged, and _baseline / _set_baseline where sampling is 2. */
+int nfsp_mccfr_x_create(nfsp_ctx* ctx, const nfsp_mccfr_x_cfg* cfgs /*[n]*/, int n, nfsp_mccfr** out);
+/* out[0] regret, out[1] average of a run; (0, 0) for a handle of nfsp_mccfr_create / _os_create /
+ * _vr_create, whose rule that is. */
+int nfsp_mccfr_rule(nfsp_mccfr* h, int run, int32_t out[2]);
+/* The uniform (NFSP_MCCFR_AVG_UNIFORM) or the linear (NFSP_MCCFR_AVG_LINEAR) average of a run, a
+ * device table as nfsp_mccfr_average's.  Refused for a handle not made by nfsp_mccfr_x_create:
+ * the other kinds keep no Sw. */
+int nfsp_mccfr_average_of(nfsp_mccfr* h, int run, int average, const double** dev_table);
+/* Sw of a run.  Synchronises the ctx stream.  Refused as nfsp_mccfr_average_of. */
+int nfsp_mccfr_weighted(nfsp_mccfr* h, int run, double* host_Sw /*[ndec][3][3]*/);
+
 /* ---- the memories as tables (csrc/memtab.hip k_memtab, k_memtab_sum) ----
  * M_SL (utils/ReservoirBuffer.py:18-28) and M_RL (utils/replay_buffer.py:30-41) counted per
  * information set where they lie, from the packed device records (SlRec 16 B {obs bits, a[3]},

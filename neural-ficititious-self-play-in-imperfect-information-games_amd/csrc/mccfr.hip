@@ -36,6 +36,11 @@
 //                  every frame adds its sample to dBs / dBn beside dR / dS (Leduc: 64,904 B of LDS,
 //                  two workgroups to a CU).
 //   k_mccfr_vr_apply  after k_mccfr_apply: Bs += dBs, Bn += dBn, the deltas zeroed, the next B.
+// Regret matching+ and linear averaging (nfsp_mccfr_x_*, the same handle, any of the three walks)
+// swap both applies for
+//   k_mccfr_x_apply  one launch: R += dR and, per run, its floor at 0; S += dS; the f64 linear sum
+//                  Sw += (t + 1) dS; the next sigma, both averages, the counts, and with baselines
+//                  k_mccfr_vr_apply's part for the thread's three entries.
 // No workgroup waits for another -- no flags, no tickets, no spinning: the stream orders the
 // launches, and nfsp_mccfr_run synchronises once at its end.
 // All f64 arithmetic is in tree_walk.h's style (no FMA contraction, the sums ascending).
@@ -62,6 +67,10 @@ struct nfsp_mccfr {
   long long* bstate = nullptr;            // with baselines: per run Bs | Bn | dBs | dBn, [ndec][3][3] each
   double* btab = nullptr;                 // with baselines: per run B, [ndec][3][3]
   double maxpay = 0.0;                    // with baselines: P, the game's max|pay|
+  std::vector<nfsp_mccfr_x_cfg> x_cfgs;   // nfsp_mccfr_x_create: the cfgs as given (empty for the other kinds)
+  int32_t* dev_rule = nullptr;            // that kind: per run regret, average
+  double* sw = nullptr;                   // that kind: per run Sw, [ndec][3][3]
+  double* avg2 = nullptr;                 // that kind: per run the average cfg.average does not name
 };
 
 namespace {
@@ -701,6 +710,88 @@ __global__ void __launch_bounds__(256) k_mccfr_apply(ApplyArgs A) {
   average_row(s, legal_raise, sg + n9);
 }
 
+struct XApplyArgs {
+  const uint8_t* legal;
+  const nfsp_mccfr_cfg* cfg;
+  const int32_t* rule;                    // [n][2]: regret, average
+  long long* state;
+  double* tabs;                           // slot 1: the average the run's cfg names
+  double* sw;                             // [n][ndec][3][3]
+  double* avg2;                           // [n][ndec][3][3]: the other average
+  unsigned long long* counts;
+  long long* bstate;                      // null without baselines
+  double* btab;
+  double maxpay;                          // P
+  double tw;                              // (double)(t + 1), t the iterations completed before this one
+  int ndec;
+  int walked;
+};
+
+// Step 3 of the kind nfsp_mccfr_x_create makes, one thread per (row, rank) of a run: what
+// k_mccfr_apply does, with the run's floor on R, the linear sum Sw beside S and both averages;
+// then, with baselines, what k_mccfr_vr_apply does for this thread's three entries.
+__global__ void __launch_bounds__(256) k_mccfr_x_apply(XApplyArgs A) {
+#pragma clang fp contract(off)
+  const int run = blockIdx.y;
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t n9 = (size_t)A.ndec * 9;
+  if (k == 0 && A.walked) {
+    unsigned long long* c = A.counts + (size_t)run * 3;
+    c[0] += (unsigned long long)A.cfg[run].walkers;
+    c[1] += c[2];
+    c[2] = 0;
+  }
+  if (k >= A.ndec * 3) return;
+  const bool plus = A.rule[2 * run] == NFSP_MCCFR_REGRET_PLUS;
+  const bool linear = A.rule[2 * run + 1] == NFSP_MCCFR_AVG_LINEAR;
+  long long* R = A.state + (size_t)run * 4 * n9 + 3 * (size_t)k;
+  long long* S = R + n9;
+  long long* dR = S + n9;
+  long long* dS = dR + n9;
+  double* Sw = A.sw + (size_t)run * n9 + 3 * (size_t)k;
+  const bool legal_raise = A.legal[k / 3] & 1;
+  double rp[3], s[3], sl[3];
+  for (int a = 0; a < 3; ++a) {
+    long long r = R[a] + dR[a];
+    if (plus && r < 0) r = 0;
+    const long long t = S[a] + dS[a];
+    const double w = Sw[a] + A.tw * (double)dS[a];
+    R[a] = r;
+    S[a] = t;
+    Sw[a] = w;
+    dR[a] = 0;
+    dS[a] = 0;
+    rp[a] = (double)(r > 0 ? r : 0);
+    s[a] = (double)t;
+    sl[a] = w;
+  }
+  if (!legal_raise) rp[2] = 0.0;
+  double* sg = A.tabs + (size_t)run * 2 * n9 + 3 * (size_t)k;
+  double* other = A.avg2 + (size_t)run * n9 + 3 * (size_t)k;
+  average_row(rp, legal_raise, sg);
+  average_row(s, legal_raise, linear ? other : sg + n9);
+  average_row(sl, legal_raise, linear ? sg + n9 : other);
+  if (!A.bstate) return;
+  long long* Bs = A.bstate + (size_t)run * 4 * n9 + 3 * (size_t)k;
+  long long* Bn = Bs + n9;
+  long long* dBs = Bn + n9;
+  long long* dBn = dBs + n9;
+  double* B = A.btab + (size_t)run * n9 + 3 * (size_t)k;
+  for (int a = 0; a < 3; ++a) {
+    const long long bs = Bs[a] + dBs[a], c = Bn[a] + dBn[a];
+    Bs[a] = bs;
+    Bn[a] = c;
+    dBs[a] = 0;
+    dBn[a] = 0;
+    double b = 0.0;
+    if (c > 0) {
+      b = (double)bs / ((double)c * Q);
+      b = b < -A.maxpay ? -A.maxpay : b > A.maxpay ? A.maxpay : b;
+    }
+    B[a] = b;
+  }
+}
+
 // seat i's decisions on the longest path below n
 int frames_below(const HostTables& H, int n, int i) {
   if (n < 0) return 0;
@@ -761,6 +852,28 @@ int launch_vr_apply(nfsp_mccfr* h) {
   A.maxpay = h->maxpay;
   k_mccfr_vr_apply<<<dim3(nfsp_blocks(9 * (int64_t)h->ndec, 256), h->n), 256, 0, h->ctx->stream>>>(A);
   NFSP_LAUNCHED("k_mccfr_vr_apply");
+  return NFSP_OK;
+}
+
+// t: the iterations completed before the one in progress
+int launch_x_apply(nfsp_mccfr* h, const ExTables& T, int walked, int64_t t) {
+  XApplyArgs A{};
+  A.legal = T.legal;
+  A.cfg = h->dev_cfg;
+  A.rule = h->dev_rule;
+  A.state = h->state;
+  A.tabs = h->tabs;
+  A.sw = h->sw;
+  A.avg2 = h->avg2;
+  A.counts = h->counts;
+  A.bstate = h->bstate;
+  A.btab = h->btab;
+  A.maxpay = h->maxpay;
+  A.tw = (double)(t + 1);
+  A.ndec = h->ndec;
+  A.walked = walked;
+  k_mccfr_x_apply<<<dim3(nfsp_blocks(3 * (int64_t)h->ndec, 256), h->n), 256, 0, h->ctx->stream>>>(A);
+  NFSP_LAUNCHED("k_mccfr_x_apply");
   return NFSP_OK;
 }
 
@@ -878,12 +991,59 @@ extern "C" int nfsp_mccfr_vr_cfgs_check(int game, const nfsp_mccfr_vr_cfg* cfgs,
   return NFSP_OK;
 }
 
+extern "C" int nfsp_mccfr_x_cfgs_check(int game, const nfsp_mccfr_x_cfg* cfgs, int n, int64_t iters) {
+  NFSP_REQUIRE(cfgs, "null argument");
+  NFSP_REQUIRE(n >= 1 && n <= NFSP_MCCFR_MAX_RUNS, "n must be in 1 .. NFSP_MCCFR_MAX_RUNS");
+  NFSP_REQUIRE(iters >= 0, "iters must be >= 0");
+  NFSP_REQUIRE(game == NFSP_GAME_LEDUC || game == NFSP_GAME_KUHN, "unknown game");
+  for (int k = 0; k < n; ++k) {
+    const nfsp_mccfr_x_cfg& c = cfgs[k];
+    NFSP_REQUIRE(c.walkers >= 2 && c.walkers <= NFSP_MCCFR_MAX_WALKERS,
+                 "nfsp_mccfr_x_cfg.walkers must be in 2 .. NFSP_MCCFR_MAX_WALKERS");
+    NFSP_REQUIRE(c.walkers % 2 == 0, "nfsp_mccfr_x_cfg.walkers must be even (one dealer each in turn)");
+    NFSP_REQUIRE(c.sampling >= 0 && c.sampling <= 2,
+                 "nfsp_mccfr_x_cfg.sampling must be 0 (external), 1 (outcome) or 2 (outcome with baselines)");
+    if (c.sampling != cfgs[0].sampling) {
+      char msg[200];
+      snprintf(msg, sizeof msg,
+               "nfsp_mccfr_x_cfg.sampling of run %d is %d, run 0's is %d: one walk kernel serves a launch, so a handle "
+               "has one sampling kind", k, c.sampling, cfgs[0].sampling);
+      return nfsp::fail(NFSP_EINVAL, msg);
+    }
+    if (c.sampling == 0)
+      NFSP_REQUIRE(c.epsilon == 0.0, "nfsp_mccfr_x_cfg.epsilon must be 0.0 under sampling 0 (external sampling has none)");
+    else
+      NFSP_REQUIRE(c.epsilon >= NFSP_MCCFR_OS_EPS_MIN && c.epsilon <= 1.0,       // false for a NaN
+                   "nfsp_mccfr_x_cfg.epsilon must be in NFSP_MCCFR_OS_EPS_MIN .. 1");
+    NFSP_REQUIRE(c.regret == NFSP_MCCFR_REGRET_PLAIN || c.regret == NFSP_MCCFR_REGRET_PLUS,
+                 "nfsp_mccfr_x_cfg.regret must be NFSP_MCCFR_REGRET_PLAIN or NFSP_MCCFR_REGRET_PLUS");
+    NFSP_REQUIRE(c.average == NFSP_MCCFR_AVG_UNIFORM || c.average == NFSP_MCCFR_AVG_LINEAR,
+                 "nfsp_mccfr_x_cfg.average must be NFSP_MCCFR_AVG_UNIFORM or NFSP_MCCFR_AVG_LINEAR");
+  }
+  // the fields hold: what is left of the sampling kind's own check is its overflow bound (the floor
+  // only shrinks |R + dR|, so the bound on the sum of |dR| still bounds R; Sw is f64)
+  if (cfgs[0].sampling == 0) {
+    std::vector<nfsp_mccfr_cfg> es(n);
+    for (int k = 0; k < n; ++k) es[k] = nfsp_mccfr_cfg{cfgs[k].seed, cfgs[k].walkers, 0};
+    return nfsp_mccfr_cfgs_check(game, es.data(), n, iters);
+  }
+  if (cfgs[0].sampling == 1) {
+    std::vector<nfsp_mccfr_os_cfg> os(n);
+    for (int k = 0; k < n; ++k) os[k] = nfsp_mccfr_os_cfg{cfgs[k].seed, cfgs[k].walkers, 0, cfgs[k].epsilon};
+    return nfsp_mccfr_os_cfgs_check(game, os.data(), n, iters);
+  }
+  std::vector<nfsp_mccfr_vr_cfg> vr(n);
+  for (int k = 0; k < n; ++k) vr[k] = nfsp_mccfr_vr_cfg{cfgs[k].seed, cfgs[k].walkers, 0, cfgs[k].epsilon};
+  return nfsp_mccfr_vr_cfgs_check(game, vr.data(), n, iters);
+}
+
 namespace {
 
 // What every kind of handle is made of, after its checks: cfgs holds every run's seed and
-// walkers; os is null for external sampling; sampling 2 adds the baseline's tables, all 0.
+// walkers; os is null for external sampling; sampling 2 adds the baseline's tables, all 0; x (the
+// cfgs of nfsp_mccfr_x_create) adds the per-run rule, Sw and the second average, and its own apply.
 int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os_cfg* os, int n, nfsp_mccfr** out,
-                  int sampling = -1) {
+                  int sampling = -1, const nfsp_mccfr_x_cfg* x = nullptr) {
   const HostTables* H = nullptr;
   int rc = host_tables(ctx->game, &H);
   if (rc != NFSP_OK) return rc;
@@ -932,6 +1092,17 @@ int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os
     if (e == hipSuccess) e = hipMemsetAsync(h->bstate, 0, b_state, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(h->btab, 0, sizeof(double) * n9 * n, ctx->stream);   // B = 0.0
   }
+  std::vector<int32_t> rule;
+  if (x) {
+    h->x_cfgs.assign(x, x + n);
+    for (int k = 0; k < n; ++k) rule.insert(rule.end(), {x[k].regret, x[k].average});
+    if (e == hipSuccess) e = hipMalloc(&h->dev_rule, sizeof(int32_t) * rule.size());
+    if (e == hipSuccess) e = hipMalloc(&h->sw, sizeof(double) * n9 * n);
+    if (e == hipSuccess) e = hipMalloc(&h->avg2, sizeof(double) * n9 * n);
+    if (e == hipSuccess) e = hipMemsetAsync(h->sw, 0, sizeof(double) * n9 * n, ctx->stream);   // Sw = 0.0
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(h->dev_rule, rule.data(), sizeof(int32_t) * rule.size(), hipMemcpyHostToDevice, ctx->stream);
+  }
   if (e == hipSuccess) e = hipMemsetAsync(h->state, 0, b_state, ctx->stream);
   if (e == hipSuccess) e = hipMemsetAsync(h->counts, 0, b_counts, ctx->stream);
   if (e == hipSuccess)
@@ -942,7 +1113,8 @@ int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os
     (void)nfsp_mccfr_destroy(h);
     return nfsp::hip_fail(e, "nfsp_mccfr_create");
   }
-  rc = launch_apply(h, *T, 0);            // sigma and the average before any iteration: uniform
+  // sigma and the average before any iteration: uniform
+  rc = x ? launch_x_apply(h, *T, 0, 0) : launch_apply(h, *T, 0);
   if (rc == NFSP_OK && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess)
     rc = nfsp::hip_fail(e, "nfsp_mccfr_create");
   if (rc != NFSP_OK) {
@@ -991,6 +1163,60 @@ extern "C" int nfsp_mccfr_vr_create(nfsp_ctx* ctx, const nfsp_mccfr_vr_cfg* cfgs
   rc = create_handle(ctx, plain.data(), os.data(), n, out, 2);
   if (rc == NFSP_OK) (*out)->vr_cfgs.assign(cfgs, cfgs + n);
   return rc;
+}
+
+extern "C" int nfsp_mccfr_x_create(nfsp_ctx* ctx, const nfsp_mccfr_x_cfg* cfgs, int n, nfsp_mccfr** out) {
+  NFSP_REQUIRE(cfgs && out, "null argument");
+  NFSP_REQUIRE(n >= 1 && n <= NFSP_MCCFR_MAX_RUNS, "n must be in 1 .. NFSP_MCCFR_MAX_RUNS");
+  NFSP_REQUIRE(ctx, "null argument");
+  int rc = nfsp_mccfr_x_cfgs_check(ctx->game, cfgs, n, 0);
+  if (rc != NFSP_OK) return rc;
+  const int sampling = cfgs[0].sampling;
+  std::vector<nfsp_mccfr_cfg> plain(n);
+  std::vector<nfsp_mccfr_os_cfg> os(n);
+  std::vector<nfsp_mccfr_vr_cfg> vr(n);
+  for (int k = 0; k < n; ++k) {
+    plain[k] = nfsp_mccfr_cfg{cfgs[k].seed, cfgs[k].walkers, 0};
+    os[k] = nfsp_mccfr_os_cfg{cfgs[k].seed, cfgs[k].walkers, 0, cfgs[k].epsilon};
+    vr[k] = nfsp_mccfr_vr_cfg{cfgs[k].seed, cfgs[k].walkers, 0, cfgs[k].epsilon};
+  }
+  rc = create_handle(ctx, plain.data(), sampling ? os.data() : nullptr, n, out, sampling, cfgs);
+  if (rc == NFSP_OK && sampling == 2) (*out)->vr_cfgs = vr;
+  return rc;
+}
+
+extern "C" int nfsp_mccfr_rule(nfsp_mccfr* h, int run, int32_t out[2]) {
+  NFSP_REQUIRE(run >= 0, "run out of range");
+  NFSP_REQUIRE(h && out, "null argument");
+  NFSP_REQUIRE(run < h->n, "run out of range");
+  const bool x = !h->x_cfgs.empty();
+  out[0] = x ? h->x_cfgs[run].regret : NFSP_MCCFR_REGRET_PLAIN;
+  out[1] = x ? h->x_cfgs[run].average : NFSP_MCCFR_AVG_UNIFORM;
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_mccfr_average_of(nfsp_mccfr* h, int run, int average, const double** dev_table) {
+  NFSP_REQUIRE(run >= 0, "run out of range");
+  NFSP_REQUIRE(h && dev_table, "null argument");
+  NFSP_REQUIRE(!h->x_cfgs.empty(), "not a handle of nfsp_mccfr_x_create: the other kinds keep no linear sum Sw");
+  NFSP_REQUIRE(run < h->n, "run out of range");
+  NFSP_REQUIRE(average == NFSP_MCCFR_AVG_UNIFORM || average == NFSP_MCCFR_AVG_LINEAR,
+               "average must be NFSP_MCCFR_AVG_UNIFORM or NFSP_MCCFR_AVG_LINEAR");
+  const size_t n9 = 9 * (size_t)h->ndec;
+  *dev_table = average == h->x_cfgs[run].average ? h->tabs + ((size_t)run * 2 + 1) * n9 : h->avg2 + (size_t)run * n9;
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_mccfr_weighted(nfsp_mccfr* h, int run, double* host_Sw) {
+  NFSP_REQUIRE(run >= 0, "run out of range");
+  NFSP_REQUIRE(h && host_Sw, "null argument");
+  NFSP_REQUIRE(!h->x_cfgs.empty(), "not a handle of nfsp_mccfr_x_create: the other kinds keep no linear sum Sw");
+  NFSP_REQUIRE(run < h->n, "run out of range");
+  const size_t n9 = 9 * (size_t)h->ndec;
+  NFSP_HIP(hipMemcpyAsync(host_Sw, h->sw + (size_t)run * n9, sizeof(double) * n9, hipMemcpyDeviceToHost,
+                          h->ctx->stream));
+  NFSP_HIP(hipStreamSynchronize(h->ctx->stream));
+  return NFSP_OK;
 }
 
 extern "C" int nfsp_mccfr_sampling(nfsp_mccfr* h, int* out) {
@@ -1059,8 +1285,12 @@ extern "C" int nfsp_mccfr_run(nfsp_mccfr* h, int64_t iters) {
         k_mccfr_walk<<<grid, WALK_THREADS, lds, h->ctx->stream>>>(A);
         NFSP_LAUNCHED("k_mccfr_walk");
       }
-      rc = launch_apply(h, *T, 1);
-      if (rc == NFSP_OK && h->sampling == 2) rc = launch_vr_apply(h);
+      if (!h->x_cfgs.empty()) {
+        rc = launch_x_apply(h, *T, 1, h->iterations);
+      } else {
+        rc = launch_apply(h, *T, 1);
+        if (rc == NFSP_OK && h->sampling == 2) rc = launch_vr_apply(h);
+      }
       if (rc != NFSP_OK) return rc;
     }
     h->iterations += 1;
@@ -1150,6 +1380,9 @@ extern "C" int nfsp_mccfr_destroy(nfsp_mccfr* h) {
   if (h->dev_eps) (void)hipFree(h->dev_eps);
   if (h->bstate) (void)hipFree(h->bstate);
   if (h->btab) (void)hipFree(h->btab);
+  if (h->dev_rule) (void)hipFree(h->dev_rule);
+  if (h->sw) (void)hipFree(h->sw);
+  if (h->avg2) (void)hipFree(h->avg2);
   delete h;
   return NFSP_OK;
 }

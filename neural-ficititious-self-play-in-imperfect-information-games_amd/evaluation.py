@@ -27,7 +27,8 @@ external-sampling MCCFR on it (``nfsp_mccfr_*``, csrc/mccfr.hip): the sampled ta
 counted in traversals and terminals visited, to set beside the engine's curves in hands;
 ``MccfrOsSolver`` runs outcome sampling on the same handle (``nfsp_mccfr_os_*``), whose traversal
 is one sampled hand, so its cost is in the engine's own unit, and ``MccfrVrSolver`` the same
-paths with baseline-corrected values (``nfsp_mccfr_vr_*``, VR-MCCFR).
+paths with baseline-corrected values (``nfsp_mccfr_vr_*``, VR-MCCFR).  ``MccfrXSolver`` puts
+regret matching+ and linear averaging on any of the three (``nfsp_mccfr_x_*``).
 
 ``MemoryTable`` is a memory counted per information set on the device (``nfsp_memory_table``,
 csrc/memtab.hip): M_SL as the tabular average strategy the AR net is a fit of, M_RL as what the
@@ -896,6 +897,58 @@ class MccfrVrSolver(MccfrOsSolver):
         P = float(np.abs(self.tree.pay).max())
         den = np.where(Bn > 0, Bn, 1).astype(np.float64) * float(native.MCCFR_Q)
         return np.where(Bn > 0, np.clip(Bs.astype(np.float64) / den, -P, P), 0.0)
+
+
+class MccfrXSolver(MccfrVrSolver):
+    """Regret matching+ and linear averaging on any of the three sampling kinds
+    (``nfsp_mccfr_x_create``).  ``sampling`` (0 external, 1 outcome, 2 outcome with baselines, or
+    "es" / "os" / "vr") is the handle's; ``cfgs`` is one ``(seed, walkers, epsilon, regret,
+    average)`` per run, epsilon 0.0 under external sampling, regret ``native.MCCFR_REGRET_*`` or
+    "plain" / "plus", average ``native.MCCFR_AVG_*`` or "uniform" / "linear".  ``rule(k)`` is run
+    k's (regret, average); ``average(k)`` the average its cfg names and ``average(k, which)``
+    either, both kept on the same sample paths; ``weighted(k)`` the f64 linear sum Sw.  The
+    baseline methods serve sampling 2 and are refused otherwise.  Everything else is
+    ``MccfrSolver``'s."""
+
+    SAMPLINGS = {"es": 0, "os": 1, "vr": 2}
+    REGRETS = {"plain": native.MCCFR_REGRET_PLAIN, "plus": native.MCCFR_REGRET_PLUS}
+    AVERAGES = {"uniform": native.MCCFR_AVG_UNIFORM, "linear": native.MCCFR_AVG_LINEAR}
+
+    def __init__(self, ctx, cfgs=((1, 1024, 0.6, "plus", "linear"),), sampling=2):
+        _Solver.__init__(self, ctx)
+        samp = int(self.SAMPLINGS.get(sampling, sampling))
+        self.cfgs = [(int(seed) & (2**64 - 1), int(w), float(eps), int(self.REGRETS.get(reg, reg)),
+                      int(self.AVERAGES.get(avg, avg))) for seed, w, eps, reg, avg in cfgs]
+        self.n = len(self.cfgs)
+        arr = (native.MccfrXCfg * max(self.n, 1))(*[native.MccfrXCfg(seed, w, samp, eps, reg, avg)
+                                                    for seed, w, eps, reg, avg in self.cfgs])
+        h = native.P()
+        native.check(ctx.L.nfsp_mccfr_x_create(ctx.h, arr, self.n, C.byref(h)), "nfsp_mccfr_x_create")
+        self.h = h
+
+    def rule(self, run: int = 0) -> tuple:
+        """(regret, average) of a run."""
+        out = (native.I32 * 2)()
+        native.check(self.ctx.L.nfsp_mccfr_rule(self.h, int(run), out), "nfsp_mccfr_rule")
+        return int(out[0]), int(out[1])
+
+    def average(self, run: int = 0, which=None) -> Policy:
+        if which is None:
+            return MccfrSolver.average(self, run)
+        p = native.P()
+        native.check(self.ctx.L.nfsp_mccfr_average_of(self.h, int(run), int(self.AVERAGES.get(which, which)),
+                                                      C.byref(p)), "nfsp_mccfr_average_of")
+        return Policy(native.POL_TABLE, None, p.value, self)
+
+    def average_table(self, run: int = 0, which=None) -> np.ndarray:
+        return self._host_table(self.average(run, which))
+
+    def weighted(self, run: int = 0) -> np.ndarray:
+        """Sw of a run: the linearly weighted strategy sum, f64 ``[ndec, 3, 3]``."""
+        Sw = np.zeros((self.tree.ndec, 3, 3))
+        native.check(self.ctx.L.nfsp_mccfr_weighted(self.h, int(run), Sw.ctypes.data_as(native.P)),
+                     "nfsp_mccfr_weighted")
+        return Sw
 
 
 class CfrSolver(_Solver):

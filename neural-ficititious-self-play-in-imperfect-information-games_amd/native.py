@@ -116,6 +116,13 @@ class MccfrVrCfg(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("walkers", C.c_int32), ("reserved", C.c_int32), ("epsilon", C.c_double)]
 
 
+class MccfrXCfg(C.Structure):
+    """``nfsp_mccfr_x_cfg``: one run of any sampling kind (the handle's) with its regret rule
+    (``MCCFR_REGRET_*``) and the average ``nfsp_mccfr_average`` returns (``MCCFR_AVG_*``)"""
+    _fields_ = [("seed", C.c_uint64), ("walkers", C.c_int32), ("sampling", C.c_int32), ("epsilon", C.c_double),
+                ("regret", C.c_int32), ("average", C.c_int32)]
+
+
 class MemSegment(C.Structure):
     """``nfsp_mem_segment``: n packed records (SlRec 16 B / RlRec 32 B) at a device address"""
     _fields_ = [("dev_recs", P), ("n", I64)]
@@ -213,6 +220,11 @@ SIGNATURES = {
     "nfsp_mccfr_vr_create": (I32, [P, C.POINTER(MccfrVrCfg), I32, C.POINTER(P)]),
     "nfsp_mccfr_baseline": (I32, [P, I32, P, P]),
     "nfsp_mccfr_set_baseline": (I32, [P, I32, P, P]),
+    "nfsp_mccfr_x_cfgs_check": (I32, [I32, C.POINTER(MccfrXCfg), I32, I64]),
+    "nfsp_mccfr_x_create": (I32, [P, C.POINTER(MccfrXCfg), I32, C.POINTER(P)]),
+    "nfsp_mccfr_rule": (I32, [P, I32, C.POINTER(I32)]),
+    "nfsp_mccfr_average_of": (I32, [P, I32, I32, C.POINTER(P)]),
+    "nfsp_mccfr_weighted": (I32, [P, I32, P]),
     "nfsp_engine_set_loss_log": (I32, [P, I32]),
     "nfsp_engine_losses": (I32, [P, P]),
     "nfsp_engine_set_timing": (I32, [P, I32]),
@@ -297,6 +309,9 @@ MCCFR_MAX_RUNS = 64
 MCCFR_MAX_WALKERS = 1 << 22
 MCCFR_WG_WALKERS = 1024
 MCCFR_OS_EPS_MIN = 0.0625       # outcome sampling's least exploration rate (NFSP_MCCFR_OS_EPS_MIN)
+# nfsp_mccfr_x_cfg.regret / .average (NFSP_MCCFR_REGRET_*, NFSP_MCCFR_AVG_*)
+MCCFR_REGRET_PLAIN, MCCFR_REGRET_PLUS = 0, 1
+MCCFR_AVG_UNIFORM, MCCFR_AVG_LINEAR = 0, 1
 # the memories as tables (NFSP_MEM_*, NFSP_MEMTAB_*)
 MEM_SL, MEM_RL, MEM_TD, MEM_TDQ = 0, 1, 2, 3
 # what nfsp_table_rows makes of a table (NFSP_ROWS_*), and the most sweeps and tables of a call

@@ -13,6 +13,8 @@ csrc/xfp.hip): the algorithm NFSP approximates, with an exact best response and 
     python tools/solve_game.py --solver mccfr-os --time
     python tools/solve_game.py --game leduc --solver mccfr-vr --epsilon 0.6 --walkers 1024 --seeds 4 --iters 16384
     python tools/solve_game.py --solver mccfr-vr --time
+    python tools/solve_game.py --game leduc --solver mccfr-vr --regret plus --average both --walkers 1024 --seeds 4
+    python tools/solve_game.py --solver mccfr-vr --regret plus --average linear --time --time-walkers 1024 --time-runs 4
 
 eq.npz holds ``table`` [ndec, 3 ranks, 3 actions] (rows as evaluation.GameTree's; usable as
 evaluation.Policy.table), ``game``, and per checkpoint (--every, doubling by default)
@@ -45,6 +47,15 @@ k_mccfr_vr_walk), with mccfr-os's options and output columns, --time included: t
 hands, the values on the way back up corrected by a learned baseline at every decision.  Its
 corrected values are larger than one pay, so its budget is smaller: W x iterations up to
 29,142,433 on Leduc at --epsilon 0.6.
+
+--regret plain|plus and --average uniform|linear|both, for the three mccfr solvers: regret matching+
+and the linearly weighted average on the same walks (evaluation.MccfrXSolver, k_mccfr_x_apply; a flag
+left out is plain / uniform).  Given either, the handle is nfsp_mccfr_x_create's and the lines carry
+``regret`` and ``average``; without both flags the handles are the old ones and the output is as it
+was.  ``both`` keeps the linear average as the handle's own and scores the two averages of every run
+at every checkpoint, on identical sample paths: ``exploitability_runs_uniform`` and
+``exploitability_runs_linear``; the other fields are then the linear average's.  --time takes the
+flags too, and --time-walkers W / --time-runs K time K runs of W walkers in the one handle.
 """
 import argparse
 import json
@@ -58,17 +69,23 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 
-def time_mccfr(ev, nat, epsilon=None, walkers=1 << 20, repeats=5, baselines=False):
+def time_mccfr(ev, nat, epsilon=None, walkers=1 << 20, repeats=5, baselines=False, rule=None, runs=1):
     """Best of ``repeats`` single iterations (2 W traversals each) after a warm-up; outcome
-    sampling where ``epsilon`` is given, baseline-corrected with ``baselines``."""
+    sampling where ``epsilon`` is given, baseline-corrected with ``baselines``; ``rule`` =
+    (regret, average) times the handle of nfsp_mccfr_x_create; ``runs`` seeds 1 .. runs in the one
+    handle (the counts are the first's)."""
     import torch
     ctx = nat.Context(1, game=nat.GAME_LEDUC)
-    if epsilon is None:
-        solver = ev.MccfrSolver(ctx, [(1, walkers)]).run(1)
+    seeds = range(1, runs + 1)
+    if rule is not None:
+        sampling = 0 if epsilon is None else 2 if baselines else 1
+        solver = ev.MccfrXSolver(ctx, [(seed, walkers, epsilon or 0.0) + tuple(rule) for seed in seeds], sampling).run(1)
+    elif epsilon is None:
+        solver = ev.MccfrSolver(ctx, [(seed, walkers) for seed in seeds]).run(1)
     elif baselines:
-        solver = ev.MccfrVrSolver(ctx, [(1, walkers, epsilon)]).run(1)
+        solver = ev.MccfrVrSolver(ctx, [(seed, walkers, epsilon) for seed in seeds]).run(1)
     else:
-        solver = ev.MccfrOsSolver(ctx, [(1, walkers, epsilon)]).run(1)
+        solver = ev.MccfrOsSolver(ctx, [(seed, walkers, epsilon) for seed in seeds]).run(1)
     best = None
     for _ in range(repeats):
         before = solver.counts(0)
@@ -88,6 +105,10 @@ def time_mccfr(ev, nat, epsilon=None, walkers=1 << 20, repeats=5, baselines=Fals
                 terminals_per_s=best["terminals"] / (best["ms"] * 1e-3))
     if epsilon is not None:
         best.update(epsilon=epsilon, hands=best["traversals"], hands_per_s=best["traversals_per_s"])
+    if rule is not None:
+        best.update(regret=rule[0], average=rule[1])
+    if runs != 1:
+        best.update(runs=runs)
     print(json.dumps(best), flush=True)
     solver.close()
 
@@ -106,21 +127,38 @@ def main():
     ap.add_argument("--epsilon", type=float, default=0.6, help="mccfr-os, mccfr-vr: exploration rate, in [0.0625, 1]")
     ap.add_argument("--time", action="store_true",
                     help="mccfr, mccfr-os, mccfr-vr: traversals/s and terminals/s, Leduc at W = 2^20")
+    ap.add_argument("--regret", default=None, choices=["plain", "plus"],
+                    help="mccfr, mccfr-os, mccfr-vr: regret matching (plain) or regret matching+ (plus)")
+    ap.add_argument("--average", default=None, choices=["uniform", "linear", "both"],
+                    help="mccfr, mccfr-os, mccfr-vr: the average scored; both scores the two of every run")
+    ap.add_argument("--time-walkers", type=int, default=1 << 20, help="--time: walkers of a run")
+    ap.add_argument("--time-runs", type=int, default=1, help="--time: runs in the one handle")
     ap.add_argument("--out", default=None, metavar="PATH")
     args = ap.parse_args()
     import __graft_entry__
     pkg = __graft_entry__.load_package()
     ev, nat = pkg.evaluation, pkg.native
     game = nat.GAME_KUHN if args.game == "kuhn" else nat.GAME_LEDUC
+    rule = None                                         # (regret, average of the handle): nfsp_mccfr_x_create
+    if args.regret is not None or args.average is not None:
+        if args.solver not in ("mccfr", "mccfr-os", "mccfr-vr"):
+            ap.error("--regret and --average are for --solver mccfr, mccfr-os and mccfr-vr")
+        rule = (args.regret or "plain", "linear" if args.average == "both" else args.average or "uniform")
+    both = args.average == "both"
     if args.time:
         if args.solver not in ("mccfr", "mccfr-os", "mccfr-vr"):
             ap.error("--time is for --solver mccfr, mccfr-os and mccfr-vr")
-        return time_mccfr(ev, nat, None if args.solver == "mccfr" else args.epsilon, baselines=args.solver == "mccfr-vr")
+        return time_mccfr(ev, nat, None if args.solver == "mccfr" else args.epsilon, baselines=args.solver == "mccfr-vr",
+                          rule=rule, walkers=args.time_walkers, runs=args.time_runs)
     ctx = nat.Context(1, game=game)
     xfp = args.solver == "xfp"
     outcome = args.solver in ("mccfr-os", "mccfr-vr")
     mccfr = args.solver == "mccfr" or outcome
-    if outcome:
+    if rule is not None:
+        solver = ev.MccfrXSolver(ctx, [(seed, args.walkers, args.epsilon if outcome else 0.0) + rule
+                                       for seed in range(1, args.seeds + 1)],
+                                 {"mccfr": "es", "mccfr-os": "os", "mccfr-vr": "vr"}[args.solver])
+    elif outcome:
         solver = (ev.MccfrVrSolver if args.solver == "mccfr-vr" else ev.MccfrOsSolver)(
             ctx, [(seed, args.walkers, args.epsilon) for seed in range(1, args.seeds + 1)])
     elif mccfr:
@@ -158,6 +196,12 @@ def main():
                        terminals=[c[1] for c in counts], exploitability_runs=[x["exploitability"] for x in res])
         if outcome:
             rec.update(hands=counts[0][0], epsilon=args.epsilon)
+        if rule is not None:
+            rec.update(regret=rule[0], average=args.average or "uniform")
+        if both:
+            uni = ev.evaluate_batch(ctx, [(a, a) for a in (solver.average(k, "uniform") for k in range(solver.n))])
+            rec.update(exploitability_runs_uniform=[x["exploitability"] for x in uni],
+                       exploitability_runs_linear=rec["exploitability_runs"])
         if xfp:
             rec.update(solver="xfp", weight=args.weight, eta=etas[-1])
             if len(etas) > 1:
