@@ -1009,6 +1009,97 @@ int nfsp_mccfr_average_of(nfsp_mccfr* h, int run, int average, const double** de
 /* Sw of a run.  Synchronises the ctx stream.  Refused as nfsp_mccfr_average_of. */
 int nfsp_mccfr_weighted(nfsp_mccfr* h, int run, double* host_Sw /*[ndec][3][3]*/);
 
+/* ---- regret nets on the same handle (csrc/mccfr.hip k_mccfr_net_apply, after k_mccfr_x_apply) ----
+ * Regression CFR (Waugh, Morrill, Bagnell and Bowling 2015) with sampled regrets: the learner
+ * holds its regrets in two packed 30-64-3 nets, the engine's own shape, and the walkers' sigma is
+ * the nets', not the table's.  With sampled regrets it is Deep CFR (Brown, Lerer, Gross and
+ * Sandholm 2019) in the limit of an unbounded memory and a full-batch fit.  A fifth way to create
+ * an nfsp_mccfr.  The cfg holds nfsp_mccfr_x_cfg's fields with the same meaning and the same
+ * checks, and adds `target`, `fit_steps` (K), `loss`, `lr` and `momentum`, all per run.
+ * Each run has two nets w[seat] (NP f32, linear heads: NFSP_ACT_LINEAR) and their momentum states
+ * v[seat], 0.0 at creation; the caller gives the initial nets, which are copied.
+ * Steps 1 to 3 of the sampling kind and of nfsp_mccfr_x_create are unchanged, bit for bit: the
+ * draws, the choices, dR, dS, dBs, dBn, the counts, R, its floor, S, Sw, both averages and B.  One
+ * thing changes: the sigma a half-iteration's walkers read is not regret matching on R.  After the
+ * tables of a half-iteration of seat i are applied, for seat i, with tw = (double)(t + 1) as above:
+ *   targets   f64, per (d, r) of the seat's rows and action a:
+ *             NFSP_MCCFR_NET_TARGET_AVG     y_a = (double)R_a / (((double)W * Q) * tw)
+ *             NFSP_MCCFR_NET_TARGET_ROWMAX  m = the largest |R_b| over the legal b, as int64;
+ *                                           y_a = (double)R_a / (double)m, and 0.0 where m = 0
+ *             An illegal raise has y = 0.0, and the default mask of nfsp_fit_tables removes it.
+ *   fit       K steps of nfsp_fit_tables' step exactly as stated below: f32, contraction off, the
+ *             same orders, t = (float)y, uniform weights what = (float)(1.0 / N) with N the seat's
+ *             (d, r) rows, the legal actions' mask, the linear head and the cfg's loss.  It starts
+ *             from w[i] and v[i], and both carry over to the seat's next fit.  The loss before the
+ *             first step and at the final weights (one more forward; the same number where K = 0)
+ *             is kept per (run, seat), summed as nfsp_fit_tables' host_loss is.
+ *   head      z[d][r][.] (f32): the net's three head sums at the seat's rows, by the step's forward
+ *   sigma     rp_a = max((double)z_a, 0.0), 0.0 at an illegal raise; sigma[d][r] is rp normalised by
+ *             the rule of step 1 (s = (rp_0 + rp_1) + rp_2, rp_a / s, uniform over the legal
+ *             actions where s = 0): the function that turns R into sigma for the other kinds.
+ * The other seat's rows of z and sigma keep their bits: its net did not change, and its head is
+ * formed again from it by the same operations.  A net written through nfsp_mccfr_net_weights
+ * between runs therefore reaches z and sigma at the first apply after it, the fitted seat's after
+ * its fit.
+ * At creation both seats take this step once with R = 0 and tw = 1: K steps toward zero regrets.
+ * Declared property: the first sigma is the nets', not uniform.
+ * The regret-matching table on R is still computed and kept beside: sigma_tab.  The distance of
+ * the two tables is the epsilon of regression CFR's bound.  Overflow is the sampling kind's own
+ * bound, re-checked by nfsp_mccfr_run: the bound on the sum of |dR| does not depend on sigma.
+ * k_mccfr_net_apply follows k_mccfr_x_apply in every half-iteration on the ctx stream: an
+ * iteration is 6 launches.  Grid (2 seats, n runs), 512 threads, the net, v, the seat's rows and
+ * the workspace in LDS as k_fit_tables holds them, all K steps inside the launch; no atomics, no
+ * workgroup waits for another.  Determinism: a run's nets, z and sigma are functions of the run
+ * alone, not of its place in the handle or of n.  tests/mccfr_net_ref.py restates the rule in
+ * numpy; the integer tables agree to the bit when the restatement reads the device's sigma, the
+ * nets within nfsp_fit_tables' own bar. */
+#define NFSP_MCCFR_NET_TARGET_AVG 0
+#define NFSP_MCCFR_NET_TARGET_ROWMAX 1
+#define NFSP_MCCFR_NET_MAX_STEPS 4096
+typedef struct {
+  uint64_t seed;
+  int32_t walkers;                      /* W: even, 2 .. NFSP_MCCFR_MAX_WALKERS */
+  int32_t sampling;                     /* the handle's, as nfsp_mccfr_x_cfg.sampling */
+  double epsilon;                       /* as nfsp_mccfr_x_cfg.epsilon */
+  int32_t regret;                       /* NFSP_MCCFR_REGRET_* */
+  int32_t average;                      /* NFSP_MCCFR_AVG_* */
+  int32_t target;                       /* NFSP_MCCFR_NET_TARGET_* */
+  int32_t fit_steps;                    /* K: 0 .. NFSP_MCCFR_NET_MAX_STEPS */
+  int32_t loss;                         /* NFSP_FIT_MSE or NFSP_FIT_HUBER */
+  float lr;                             /* finite, >= 0 */
+  float momentum;                       /* in [0, 1) */
+  int32_t reserved;                     /* must be 0 */
+} nfsp_mccfr_net_cfg;                   /* 56 bytes */
+/* Host only, as nfsp_mccfr_x_cfgs_check: every field of every cfg (a message names
+ * nfsp_mccfr_net_cfg.<field> and the run), then the sampling kind's own overflow bound. */
+int nfsp_mccfr_net_cfgs_check(int game, const nfsp_mccfr_net_cfg* cfgs /*[n]*/, int n, int64_t iters);
+/* dev_w0[2 k + seat]: run k's initial net of that seat, NP f32 on the device; copied, and refused
+ * unless every value is finite.  The handle is an nfsp_mccfr: nfsp_mccfr_run / _iterations /
+ * _counts / _average / _average_of / _weighted / _state / _rule / _sampling / _destroy serve it
+ * unchanged, and _baseline / _set_baseline where sampling is 2. */
+int nfsp_mccfr_net_create(nfsp_ctx* ctx, const nfsp_mccfr_net_cfg* cfgs /*[n]*/, int n,
+                          const float* const* dev_w0 /*[n][2]*/, nfsp_mccfr** out);
+/* The three tables of a run on the device: the sigma the walkers read, regret matching on R
+ * (f64 [ndec][3][3] each) and the heads z (f32 [ndec][3][3]).  Any of the three may be NULL.
+ * This and the two calls below are refused for a handle not made by nfsp_mccfr_net_create. */
+int nfsp_mccfr_net_tables(nfsp_mccfr* h, int run, const double** dev_sigma, const double** dev_sigma_tab,
+                          const float** dev_z);
+/* A seat's net and momentum state, NP f32 each on the device: may be read, and written between
+ * runs (on the ctx stream, or synchronised with it).  Either of the two may be NULL. */
+int nfsp_mccfr_net_weights(nfsp_mccfr* h, int run, int seat, float** dev_w, float** dev_v);
+/* out[seat][0] / [1]: the loss of the seat's last fit before its first step / at its final
+ * weights.  Synchronises the ctx stream. */
+int nfsp_mccfr_net_loss(nfsp_mccfr* h, int run, double out[2][2]);
+/* Timing of a handle of any kind, off at creation.  While it is on, nfsp_mccfr_run records three
+ * HIP events per half-iteration on the ctx stream (before the walk, after it, after the applies;
+ * at most NFSP_MCCFR_TIMED_ITERS iterations per call) and adds the elapsed times up after its
+ * synchronisation.  nfsp_mccfr_set_timing sets the sums to 0; nfsp_mccfr_get_timings gives
+ * out_ms[0] the walks', out_ms[1] the applies', and the iterations they cover.  The tables do
+ * not depend on it. */
+#define NFSP_MCCFR_TIMED_ITERS 4096
+int nfsp_mccfr_set_timing(nfsp_mccfr* h, int enable);
+int nfsp_mccfr_get_timings(nfsp_mccfr* h, double out_ms[2], int64_t* iterations);
+
 /* ---- the memories as tables (csrc/memtab.hip k_memtab, k_memtab_sum) ----
  * M_SL (utils/ReservoirBuffer.py:18-28) and M_RL (utils/replay_buffer.py:30-41) counted per
  * information set where they lie, from the packed device records (SlRec 16 B {obs bits, a[3]},

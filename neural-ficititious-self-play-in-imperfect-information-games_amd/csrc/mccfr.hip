@@ -41,6 +41,14 @@
 //   k_mccfr_x_apply  one launch: R += dR and, per run, its floor at 0; S += dS; the f64 linear sum
 //                  Sw += (t + 1) dS; the next sigma, both averages, the counts, and with baselines
 //                  k_mccfr_vr_apply's part for the thread's three entries.
+// Regret nets (nfsp_mccfr_net_*, the same handle, any of the three walks) add after it
+//   k_mccfr_net_apply  grid (2 seats, n runs), 512 lanes, one workgroup per (run, seat) with the
+//                  seat's 30-64-3 net, its momentum state and the seat's rows in LDS as
+//                  k_fit_tables holds them (fit_step.h).  The workgroup of the seat that walked
+//                  turns R into targets and runs the run's K full-batch steps; every workgroup
+//                  then takes one forward and writes the heads z and the sigma the next walk
+//                  reads for its seat's rows.  k_mccfr_x_apply's regret matching on R goes to a
+//                  table beside (sigma_tab).
 // No workgroup waits for another -- no flags, no tickets, no spinning: the stream orders the
 // launches, and nfsp_mccfr_run synchronises once at its end.
 // All f64 arithmetic is in tree_walk.h's style (no FMA contraction, the sums ascending).
@@ -48,6 +56,7 @@
 
 #include <vector>
 
+#include "fit_step.h"
 #include "tree_walk.h"
 
 struct nfsp_mccfr {
@@ -71,6 +80,18 @@ struct nfsp_mccfr {
   int32_t* dev_rule = nullptr;            // that kind: per run regret, average
   double* sw = nullptr;                   // that kind: per run Sw, [ndec][3][3]
   double* avg2 = nullptr;                 // that kind: per run the average cfg.average does not name
+  std::vector<nfsp_mccfr_net_cfg> net_cfgs;   // nfsp_mccfr_net_create: the cfgs as given (x_cfgs holds their rule)
+  void* dev_net = nullptr;                // that kind: per run target, K, loss, lr, momentum (NetDevCfg)
+  int32_t* net_rows = nullptr;            // that kind: [2][FIT_SEAT_ROWS], a seat's decision rows, ascending
+  int net_nrows[2] = {0, 0};
+  float* net_w = nullptr;                 // that kind: per run and seat the net, NP f32
+  float* net_v = nullptr;                 // that kind: per run and seat its momentum state
+  float* net_z = nullptr;                 // that kind: per run the heads, [ndec][3][3]
+  double* sigma_tab = nullptr;            // that kind: per run regret matching on R (tabs holds the nets' sigma)
+  double* net_loss = nullptr;             // that kind: per run and seat the loss before and after the last fit
+  bool timing = false;                    // nfsp_mccfr_set_timing: events around the walks and the applies
+  double ms_walk = 0.0, ms_apply = 0.0;   // summed over the half-iterations timed
+  int64_t timed = 0;                      // iterations timed
 };
 
 namespace {
@@ -718,6 +739,8 @@ struct XApplyArgs {
   double* tabs;                           // slot 1: the average the run's cfg names
   double* sw;                             // [n][ndec][3][3]
   double* avg2;                           // [n][ndec][3][3]: the other average
+  double* sigma_tab;                      // [n][ndec][3][3]: where regret matching on R goes instead of tabs'
+                                          // slot 0, which then holds the nets' sigma; null without nets
   unsigned long long* counts;
   long long* bstate;                      // null without baselines
   double* btab;
@@ -768,7 +791,7 @@ __global__ void __launch_bounds__(256) k_mccfr_x_apply(XApplyArgs A) {
   if (!legal_raise) rp[2] = 0.0;
   double* sg = A.tabs + (size_t)run * 2 * n9 + 3 * (size_t)k;
   double* other = A.avg2 + (size_t)run * n9 + 3 * (size_t)k;
-  average_row(rp, legal_raise, sg);
+  average_row(rp, legal_raise, A.sigma_tab ? A.sigma_tab + (size_t)run * n9 + 3 * (size_t)k : sg);
   average_row(s, legal_raise, linear ? other : sg + n9);
   average_row(sl, legal_raise, linear ? sg + n9 : other);
   if (!A.bstate) return;
@@ -789,6 +812,128 @@ __global__ void __launch_bounds__(256) k_mccfr_x_apply(XApplyArgs A) {
       b = b < -A.maxpay ? -A.maxpay : b > A.maxpay ? A.maxpay : b;
     }
     B[a] = b;
+  }
+}
+
+struct NetDevCfg {
+  int32_t target, steps, loss;
+  float lr, mu;
+};
+
+struct NetApplyArgs {
+  const NetDevCfg* net;                   // [n]
+  const nfsp_mccfr_cfg* cfg;              // [n]: W
+  const int32_t* rows;                    // [2][FIT_SEAT_ROWS]
+  const uint32_t* obs;                    // [ndec][3]
+  const uint8_t* legal;                   // [ndec]
+  const long long* state;                 // R is the first of a run's four tables
+  double* tabs;                           // slot 0: the nets' sigma
+  float* z;                               // [n][ndec][3][3]
+  float* w;                               // [n][2][NP]
+  float* v;                               // [n][2][NP]
+  double* loss;                           // [n][2][2]
+  double tw;                              // (double)(t + 1); 1.0 at creation
+  int32_t nrows[2];
+  int ndec;
+  int fitseat;                            // the seat that walked; 2: both (creation)
+};
+
+// The nets' step of a half-iteration, one workgroup per (seat, run): k_fit_tables with the targets
+// made here from R and the head turned into sigma.  `fits`, the step count and every row count are
+// uniform over the workgroup; the two single-thread regions (the loss sums) lie outside the step
+// loop.
+__global__ void __launch_bounds__(nfsp::fit::FIT_WG) k_mccfr_net_apply(NetApplyArgs A) {
+#pragma clang fp contract(off)
+  using namespace nfsp::fit;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int seat = blockIdx.x, run = blockIdx.y;
+  const int tid = threadIdx.x;
+  const bool fits = A.fitseat == 2 || A.fitseat == seat;
+  const NetDevCfg C = A.net[run];
+  const int N = A.nrows[seat] * 3;
+  const int nmax = (A.nrows[0] > A.nrows[1] ? A.nrows[0] : A.nrows[1]) * 3;
+  const FitLds S = fit_carve(smem_raw, (nmax + 3) & ~3);
+  const float lr = C.lr, mu = C.mu;
+  const int head = NFSP_ACT_LINEAR, loss = C.loss;
+  const size_t n9 = (size_t)A.ndec * 9;
+  float* gw = A.w + ((size_t)run * 2 + seat) * NP;
+  float* gv = A.v + ((size_t)run * 2 + seat) * NP;
+  const long long* R = A.state + (size_t)run * 4 * n9;
+  const double den = ((double)A.cfg[run].walkers * Q) * A.tw;
+  const float what = (float)(1.0 / (double)N);
+
+  for (int e = tid; e < NP; e += FIT_WG) {
+    S.w[e] = gw[e];
+    S.v[e] = gv[e];
+  }
+  for (int b = tid; b < N; b += FIT_WG) {
+    const int c = b / 3, r = b - c * 3;
+    const int d = A.rows[seat * FIT_SEAT_ROWS + c];
+    const int sid = d * 3 + r;
+    const bool raise = A.legal[d] & 1;
+    S.x[b] = A.obs[sid];
+    S.wh[b] = what;
+    const long long r0 = R[sid * 3], r1 = R[sid * 3 + 1], r2 = raise ? R[sid * 3 + 2] : 0;
+    double y0, y1, y2;
+    if (C.target == NFSP_MCCFR_NET_TARGET_AVG) {
+      y0 = (double)r0 / den;
+      y1 = (double)r1 / den;
+      y2 = (double)r2 / den;
+    } else {
+      const long long a0 = r0 < 0 ? -r0 : r0, a1 = r1 < 0 ? -r1 : r1, a2 = r2 < 0 ? -r2 : r2;
+      const long long m01 = a0 > a1 ? a0 : a1, m = m01 > a2 ? m01 : a2;
+      y0 = m ? (double)r0 / (double)m : 0.0;
+      y1 = m ? (double)r1 / (double)m : 0.0;
+      y2 = m ? (double)r2 / (double)m : 0.0;
+    }
+    S.t[3 * b] = (float)y0;
+    S.t[3 * b + 1] = (float)y1;
+    S.t[3 * b + 2] = raise ? (float)y2 : 0.f;
+    S.m[3 * b] = 1.f;
+    S.m[3 * b + 1] = 1.f;
+    S.m[3 * b + 2] = raise ? 1.f : 0.f;
+  }
+  __syncthreads();
+
+  if (fits) {                                        // the workgroup's: uniform
+    fit_forward(S, N);
+    fit_rows(S, N, head, loss);
+    if (tid == 0) {
+      double L = 0.0;
+      for (int b = 0; b < N; ++b) L += (double)S.lt[b];
+      A.loss[((size_t)run * 2 + seat) * 2] = L;
+    }
+    for (int s = 0; s < C.steps; ++s) {              // the run's: uniform
+#include "fit_step_body.inc"
+    }
+  }
+
+  fit_forward(S, N);
+  if (fits) {
+    fit_rows(S, N, head, loss);
+    if (tid == 0) {
+      double L = 0.0;
+      for (int b = 0; b < N; ++b) L += (double)S.lt[b];
+      A.loss[((size_t)run * 2 + seat) * 2 + 1] = L;
+    }
+    for (int e = tid; e < NP; e += FIT_WG) {
+      gw[e] = S.w[e];
+      gv[e] = S.v[e];
+    }
+  }
+  for (int b = tid; b < N; b += FIT_WG) {
+    const int c = b / 3, r = b - c * 3;
+    const int d = A.rows[seat * FIT_SEAT_ROWS + c];
+    const size_t at = ((size_t)d * 3 + r) * 3;      // < n9
+    const bool raise = A.legal[d] & 1;
+    double rp[3];
+    for (int k = 0; k < 3; ++k) {
+      const float z = S.o[3 * b + k];
+      A.z[(size_t)run * n9 + at + k] = z;
+      rp[k] = (double)z > 0.0 ? (double)z : 0.0;
+    }
+    if (!raise) rp[2] = 0.0;
+    average_row(rp, raise, A.tabs + (size_t)run * 2 * n9 + at);
   }
 }
 
@@ -865,6 +1010,7 @@ int launch_x_apply(nfsp_mccfr* h, const ExTables& T, int walked, int64_t t) {
   A.tabs = h->tabs;
   A.sw = h->sw;
   A.avg2 = h->avg2;
+  A.sigma_tab = h->sigma_tab;
   A.counts = h->counts;
   A.bstate = h->bstate;
   A.btab = h->btab;
@@ -874,6 +1020,35 @@ int launch_x_apply(nfsp_mccfr* h, const ExTables& T, int walked, int64_t t) {
   A.walked = walked;
   k_mccfr_x_apply<<<dim3(nfsp_blocks(3 * (int64_t)h->ndec, 256), h->n), 256, 0, h->ctx->stream>>>(A);
   NFSP_LAUNCHED("k_mccfr_x_apply");
+  return NFSP_OK;
+}
+
+size_t net_lds(const nfsp_mccfr* h) {
+  const int nm = (std::max(h->net_nrows[0], h->net_nrows[1]) * 3 + 3) & ~3;
+  return sizeof(float) * nfsp::fit::fit_lds_floats(nm);
+}
+
+// fitseat: the seat that walked, 2 at creation; t as launch_x_apply's
+int launch_net_apply(nfsp_mccfr* h, const ExTables& T, int fitseat, int64_t t) {
+  NetApplyArgs A{};
+  A.net = (const NetDevCfg*)h->dev_net;
+  A.cfg = h->dev_cfg;
+  A.rows = h->net_rows;
+  A.obs = T.obs;
+  A.legal = T.legal;
+  A.state = h->state;
+  A.tabs = h->tabs;
+  A.z = h->net_z;
+  A.w = h->net_w;
+  A.v = h->net_v;
+  A.loss = h->net_loss;
+  A.tw = (double)(t + 1);
+  A.nrows[0] = h->net_nrows[0];
+  A.nrows[1] = h->net_nrows[1];
+  A.ndec = h->ndec;
+  A.fitseat = fitseat;
+  k_mccfr_net_apply<<<dim3(2, h->n), nfsp::fit::FIT_WG, net_lds(h), h->ctx->stream>>>(A);
+  NFSP_LAUNCHED("k_mccfr_net_apply");
   return NFSP_OK;
 }
 
@@ -1037,13 +1212,60 @@ extern "C" int nfsp_mccfr_x_cfgs_check(int game, const nfsp_mccfr_x_cfg* cfgs, i
   return nfsp_mccfr_vr_cfgs_check(game, vr.data(), n, iters);
 }
 
+extern "C" int nfsp_mccfr_net_cfgs_check(int game, const nfsp_mccfr_net_cfg* cfgs, int n, int64_t iters) {
+  NFSP_REQUIRE(cfgs, "null argument");
+  NFSP_REQUIRE(n >= 1 && n <= NFSP_MCCFR_MAX_RUNS, "n must be in 1 .. NFSP_MCCFR_MAX_RUNS");
+  NFSP_REQUIRE(iters >= 0, "iters must be >= 0");
+  NFSP_REQUIRE(game == NFSP_GAME_LEDUC || game == NFSP_GAME_KUHN, "unknown game");
+  std::vector<nfsp_mccfr_x_cfg> x(n);
+  for (int k = 0; k < n; ++k) {
+    const nfsp_mccfr_net_cfg& c = cfgs[k];
+    const auto bad = [k](const char* what) {
+      char msg[256];
+      snprintf(msg, sizeof msg, "nfsp_mccfr_net_cfg.%s (run %d)", what, k);
+      return nfsp::fail(NFSP_EINVAL, msg);
+    };
+    if (!(c.walkers >= 2 && c.walkers <= NFSP_MCCFR_MAX_WALKERS))
+      return bad("walkers must be in 2 .. NFSP_MCCFR_MAX_WALKERS");
+    if (c.walkers % 2 != 0) return bad("walkers must be even (one dealer each in turn)");
+    if (!(c.sampling >= 0 && c.sampling <= 2))
+      return bad("sampling must be 0 (external), 1 (outcome) or 2 (outcome with baselines)");
+    if (c.sampling != cfgs[0].sampling)
+      return bad("sampling differs from run 0's: one walk kernel serves a launch, so a handle has one sampling kind");
+    if (c.sampling == 0) {
+      if (!(c.epsilon == 0.0)) return bad("epsilon must be 0.0 under sampling 0 (external sampling has none)");
+    } else if (!(c.epsilon >= NFSP_MCCFR_OS_EPS_MIN && c.epsilon <= 1.0)) {      // true for a NaN
+      return bad("epsilon must be in NFSP_MCCFR_OS_EPS_MIN .. 1");
+    }
+    if (c.regret != NFSP_MCCFR_REGRET_PLAIN && c.regret != NFSP_MCCFR_REGRET_PLUS)
+      return bad("regret must be NFSP_MCCFR_REGRET_PLAIN or NFSP_MCCFR_REGRET_PLUS");
+    if (c.average != NFSP_MCCFR_AVG_UNIFORM && c.average != NFSP_MCCFR_AVG_LINEAR)
+      return bad("average must be NFSP_MCCFR_AVG_UNIFORM or NFSP_MCCFR_AVG_LINEAR");
+    if (c.target != NFSP_MCCFR_NET_TARGET_AVG && c.target != NFSP_MCCFR_NET_TARGET_ROWMAX)
+      return bad("target must be NFSP_MCCFR_NET_TARGET_AVG or NFSP_MCCFR_NET_TARGET_ROWMAX");
+    if (!(c.fit_steps >= 0 && c.fit_steps <= NFSP_MCCFR_NET_MAX_STEPS))
+      return bad("fit_steps must be in 0 .. NFSP_MCCFR_NET_MAX_STEPS");
+    if (c.loss != NFSP_FIT_MSE && c.loss != NFSP_FIT_HUBER)
+      return bad("loss must be NFSP_FIT_MSE or NFSP_FIT_HUBER (the heads are linear)");
+    if (!(std::isfinite(c.lr) && c.lr >= 0.f)) return bad("lr must be finite and >= 0");
+    if (!(c.momentum >= 0.f && c.momentum < 1.f)) return bad("momentum must be in [0, 1)");
+    if (c.reserved != 0) return bad("reserved must be 0");
+    x[k] = nfsp_mccfr_x_cfg{c.seed, c.walkers, c.sampling, c.epsilon, c.regret, c.average};
+  }
+  // the fields hold: what is left is the sampling kind's own overflow bound, which does not depend
+  // on sigma and so not on the nets
+  return nfsp_mccfr_x_cfgs_check(game, x.data(), n, iters);
+}
+
 namespace {
 
 // What every kind of handle is made of, after its checks: cfgs holds every run's seed and
 // walkers; os is null for external sampling; sampling 2 adds the baseline's tables, all 0; x (the
-// cfgs of nfsp_mccfr_x_create) adds the per-run rule, Sw and the second average, and its own apply.
+// cfgs of nfsp_mccfr_x_create) adds the per-run rule, Sw and the second average, and its own apply;
+// net (the cfgs of nfsp_mccfr_net_create, with x) adds the nets from dev_w0, their tables and their apply.
 int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os_cfg* os, int n, nfsp_mccfr** out,
-                  int sampling = -1, const nfsp_mccfr_x_cfg* x = nullptr) {
+                  int sampling = -1, const nfsp_mccfr_x_cfg* x = nullptr, const nfsp_mccfr_net_cfg* net = nullptr,
+                  const float* const* dev_w0 = nullptr) {
   const HostTables* H = nullptr;
   int rc = host_tables(ctx->game, &H);
   if (rc != NFSP_OK) return rc;
@@ -1064,6 +1286,37 @@ int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os
     NFSP_REQUIRE(T->ndec <= FRAME_MAX_ROWS, "a decision row does not fit a frame");
   } else {
     NFSP_REQUIRE(walk_lds(T->nn, T->ndec, nterm) <= 64 * 1024, "MCCFR tables exceed 64 KB of LDS");
+  }
+  // the nets: the seats' rows as nfsp_fit_tables takes them, and the initial nets to the host once,
+  // refused unless finite -- before anything is allocated or launched
+  std::vector<int32_t> rows;
+  std::vector<float> w0;
+  int nrows[2] = {0, 0};
+  if (net) {
+    using namespace nfsp::fit;
+    static_assert(nfsp::nn::H == 64, "nfsp_mccfr_net_create: hidden is 64");
+    rows.assign(2 * FIT_SEAT_ROWS, 0);
+    for (int d = 0; d < T->ndec; ++d) {
+      const int s = H->legal[d] >> 1;
+      NFSP_REQUIRE(s <= 1 && nrows[s] < FIT_SEAT_ROWS,
+                   "nfsp_mccfr_net_create: the seat has more rows than the kernel holds");
+      rows[s * FIT_SEAT_ROWS + nrows[s]++] = d;
+    }
+    const int nm = (std::max(nrows[0], nrows[1]) * 3 + 3) & ~3;
+    NFSP_REQUIRE(sizeof(float) * fit_lds_floats(nm) <= (size_t)EX_MAX_LDS,
+                 "nfsp_mccfr_net_create: the rows do not fit in LDS");
+    w0.resize((size_t)n * 2 * NP);
+    for (int k = 0; k < 2 * n; ++k)
+      NFSP_HIP(hipMemcpyAsync(w0.data() + (size_t)k * NP, dev_w0[k], sizeof(float) * NP, hipMemcpyDeviceToHost,
+                              ctx->stream));
+    NFSP_HIP(hipStreamSynchronize(ctx->stream));
+    for (size_t e = 0; e < w0.size(); ++e)
+      if (!std::isfinite(w0[e])) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "nfsp_mccfr_net_create: run %d seat %d: dev_w0 is not finite at parameter %d",
+                 (int)(e / NP / 2), (int)(e / NP % 2), (int)(e % NP));
+        return nfsp::fail(NFSP_EINVAL, msg);
+      }
   }
   nfsp_mccfr* h = new nfsp_mccfr;
   h->ctx = ctx;
@@ -1103,6 +1356,32 @@ int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os
     if (e == hipSuccess)
       e = hipMemcpyAsync(h->dev_rule, rule.data(), sizeof(int32_t) * rule.size(), hipMemcpyHostToDevice, ctx->stream);
   }
+  std::vector<NetDevCfg> ncfg;
+  if (net) {
+    h->net_cfgs.assign(net, net + n);
+    h->net_nrows[0] = nrows[0];
+    h->net_nrows[1] = nrows[1];
+    for (int k = 0; k < n; ++k)
+      ncfg.push_back(NetDevCfg{net[k].target, net[k].fit_steps, net[k].loss, net[k].lr, net[k].momentum});
+    const size_t b_net = sizeof(float) * 2 * nfsp::nn::NP * n;
+    if (e == hipSuccess) e = hipMalloc(&h->dev_net, sizeof(NetDevCfg) * n);
+    if (e == hipSuccess) e = hipMalloc(&h->net_rows, sizeof(int32_t) * rows.size());
+    if (e == hipSuccess) e = hipMalloc(&h->net_w, b_net);
+    if (e == hipSuccess) e = hipMalloc(&h->net_v, b_net);
+    if (e == hipSuccess) e = hipMalloc(&h->net_z, sizeof(float) * n9 * n);
+    if (e == hipSuccess) e = hipMalloc(&h->sigma_tab, sizeof(double) * n9 * n);
+    if (e == hipSuccess) e = hipMalloc(&h->net_loss, sizeof(double) * 4 * n);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(h->dev_net, ncfg.data(), sizeof(NetDevCfg) * n, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(h->net_rows, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->net_w, w0.data(), b_net, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->net_v, 0, b_net, ctx->stream);                    // v = 0.0
+    if (e == hipSuccess) e = hipMemsetAsync(h->net_z, 0, sizeof(float) * n9 * n, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->net_loss, 0, sizeof(double) * 4 * n, ctx->stream);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute((const void*)k_mccfr_net_apply, hipFuncAttributeMaxDynamicSharedMemorySize, EX_MAX_LDS);
+  }
   if (e == hipSuccess) e = hipMemsetAsync(h->state, 0, b_state, ctx->stream);
   if (e == hipSuccess) e = hipMemsetAsync(h->counts, 0, b_counts, ctx->stream);
   if (e == hipSuccess)
@@ -1113,8 +1392,10 @@ int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os
     (void)nfsp_mccfr_destroy(h);
     return nfsp::hip_fail(e, "nfsp_mccfr_create");
   }
-  // sigma and the average before any iteration: uniform
+  // sigma and the average before any iteration: uniform; with nets sigma is theirs, after both
+  // seats' K steps toward R = 0
   rc = x ? launch_x_apply(h, *T, 0, 0) : launch_apply(h, *T, 0);
+  if (rc == NFSP_OK && net) rc = launch_net_apply(h, *T, 2, 0);
   if (rc == NFSP_OK && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess)
     rc = nfsp::hip_fail(e, "nfsp_mccfr_create");
   if (rc != NFSP_OK) {
@@ -1185,6 +1466,69 @@ extern "C" int nfsp_mccfr_x_create(nfsp_ctx* ctx, const nfsp_mccfr_x_cfg* cfgs, 
   return rc;
 }
 
+extern "C" int nfsp_mccfr_net_create(nfsp_ctx* ctx, const nfsp_mccfr_net_cfg* cfgs, int n, const float* const* dev_w0,
+                                     nfsp_mccfr** out) {
+  NFSP_REQUIRE(cfgs && out && dev_w0, "null argument");
+  NFSP_REQUIRE(n >= 1 && n <= NFSP_MCCFR_MAX_RUNS, "n must be in 1 .. NFSP_MCCFR_MAX_RUNS");
+  NFSP_REQUIRE(ctx, "null argument");
+  int rc = nfsp_mccfr_net_cfgs_check(ctx->game, cfgs, n, 0);
+  if (rc != NFSP_OK) return rc;
+  for (int k = 0; k < 2 * n; ++k) NFSP_REQUIRE(dev_w0[k], "nfsp_mccfr_net_create: a null initial net");
+  const int sampling = cfgs[0].sampling;
+  std::vector<nfsp_mccfr_cfg> plain(n);
+  std::vector<nfsp_mccfr_os_cfg> os(n);
+  std::vector<nfsp_mccfr_vr_cfg> vr(n);
+  std::vector<nfsp_mccfr_x_cfg> x(n);
+  for (int k = 0; k < n; ++k) {
+    plain[k] = nfsp_mccfr_cfg{cfgs[k].seed, cfgs[k].walkers, 0};
+    os[k] = nfsp_mccfr_os_cfg{cfgs[k].seed, cfgs[k].walkers, 0, cfgs[k].epsilon};
+    vr[k] = nfsp_mccfr_vr_cfg{cfgs[k].seed, cfgs[k].walkers, 0, cfgs[k].epsilon};
+    x[k] = nfsp_mccfr_x_cfg{cfgs[k].seed, cfgs[k].walkers, sampling, cfgs[k].epsilon, cfgs[k].regret, cfgs[k].average};
+  }
+  rc = create_handle(ctx, plain.data(), sampling ? os.data() : nullptr, n, out, sampling, x.data(), cfgs, dev_w0);
+  if (rc == NFSP_OK && sampling == 2) (*out)->vr_cfgs = vr;
+  return rc;
+}
+
+#define NFSP_NET_HANDLE(h) \
+  NFSP_REQUIRE(!(h)->net_cfgs.empty(), "not a handle of nfsp_mccfr_net_create: the other kinds hold no nets")
+
+extern "C" int nfsp_mccfr_net_tables(nfsp_mccfr* h, int run, const double** dev_sigma, const double** dev_sigma_tab,
+                                     const float** dev_z) {
+  NFSP_REQUIRE(run >= 0, "run out of range");
+  NFSP_REQUIRE(h, "null argument");
+  NFSP_NET_HANDLE(h);
+  NFSP_REQUIRE(run < h->n, "run out of range");
+  const size_t n9 = 9 * (size_t)h->ndec;
+  if (dev_sigma) *dev_sigma = h->tabs + (size_t)run * 2 * n9;
+  if (dev_sigma_tab) *dev_sigma_tab = h->sigma_tab + (size_t)run * n9;
+  if (dev_z) *dev_z = h->net_z + (size_t)run * n9;
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_mccfr_net_weights(nfsp_mccfr* h, int run, int seat, float** dev_w, float** dev_v) {
+  NFSP_REQUIRE(run >= 0, "run out of range");
+  NFSP_REQUIRE(h, "null argument");
+  NFSP_NET_HANDLE(h);
+  NFSP_REQUIRE(run < h->n, "run out of range");
+  NFSP_REQUIRE(seat == 0 || seat == 1, "seat must be 0 or 1");
+  const size_t at = ((size_t)run * 2 + seat) * nfsp::nn::NP;
+  if (dev_w) *dev_w = h->net_w + at;
+  if (dev_v) *dev_v = h->net_v + at;
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_mccfr_net_loss(nfsp_mccfr* h, int run, double out[2][2]) {
+  NFSP_REQUIRE(run >= 0, "run out of range");
+  NFSP_REQUIRE(h && out, "null argument");
+  NFSP_NET_HANDLE(h);
+  NFSP_REQUIRE(run < h->n, "run out of range");
+  NFSP_HIP(hipMemcpyAsync(out, h->net_loss + 4 * (size_t)run, sizeof(double) * 4, hipMemcpyDeviceToHost,
+                          h->ctx->stream));
+  NFSP_HIP(hipStreamSynchronize(h->ctx->stream));
+  return NFSP_OK;
+}
+
 extern "C" int nfsp_mccfr_rule(nfsp_mccfr* h, int run, int32_t out[2]) {
   NFSP_REQUIRE(run >= 0, "run out of range");
   NFSP_REQUIRE(h && out, "null argument");
@@ -1229,6 +1573,7 @@ extern "C" int nfsp_mccfr_run(nfsp_mccfr* h, int64_t iters) {
   NFSP_REQUIRE(iters >= 0, "iters must be >= 0");
   NFSP_REQUIRE(h, "null argument");
   NFSP_REQUIRE(iters <= INT64_MAX - h->iterations, "overflow: iters too large");
+  NFSP_REQUIRE(!h->timing || iters <= NFSP_MCCFR_TIMED_ITERS, "with timing on, iters must be <= NFSP_MCCFR_TIMED_ITERS");
   int rc = h->sampling == 2   ? nfsp_mccfr_vr_cfgs_check(h->ctx->game, h->vr_cfgs.data(), h->n, h->iterations + iters)
            : h->sampling == 1 ? nfsp_mccfr_os_cfgs_check(h->ctx->game, h->os_cfgs.data(), h->n, h->iterations + iters)
                               : nfsp_mccfr_cfgs_check(h->ctx->game, h->cfgs.data(), h->n, h->iterations + iters);
@@ -1240,9 +1585,26 @@ extern "C" int nfsp_mccfr_run(nfsp_mccfr* h, int64_t iters) {
   const size_t lds = h->sampling == 2   ? vr_lds(T->nn, T->ndec)
                      : h->sampling == 1 ? os_lds(T->nn, T->ndec)
                                         : walk_lds(T->nn, T->ndec, h->nterm);
+  // with timing on: three events per half-iteration, before the walk, after it and after the applies
+  std::vector<hipEvent_t> ev;
+  struct EvFree {
+    std::vector<hipEvent_t>& v;
+    ~EvFree() {
+      for (hipEvent_t e : v) (void)hipEventDestroy(e);
+    }
+  } ev_free{ev};
+  const auto stamp = [&]() -> int {
+    if (!h->timing) return NFSP_OK;
+    hipEvent_t e;
+    NFSP_HIP(hipEventCreate(&e));
+    ev.push_back(e);
+    NFSP_HIP(hipEventRecord(e, h->ctx->stream));
+    return NFSP_OK;
+  };
   for (int64_t it = 0; it < iters; ++it) {
     for (int i = 0; i < 2; ++i) {
       const uint64_t hh = 2 * (uint64_t)h->iterations + i;
+      if ((rc = stamp()) != NFSP_OK) return rc;
       if (h->sampling == 2) {
         VrArgs A{};
         A.T = *T;
@@ -1285,17 +1647,44 @@ extern "C" int nfsp_mccfr_run(nfsp_mccfr* h, int64_t iters) {
         k_mccfr_walk<<<grid, WALK_THREADS, lds, h->ctx->stream>>>(A);
         NFSP_LAUNCHED("k_mccfr_walk");
       }
+      if ((rc = stamp()) != NFSP_OK) return rc;
       if (!h->x_cfgs.empty()) {
         rc = launch_x_apply(h, *T, 1, h->iterations);
+        if (rc == NFSP_OK && !h->net_cfgs.empty()) rc = launch_net_apply(h, *T, i, h->iterations);
       } else {
         rc = launch_apply(h, *T, 1);
         if (rc == NFSP_OK && h->sampling == 2) rc = launch_vr_apply(h);
       }
       if (rc != NFSP_OK) return rc;
+      if ((rc = stamp()) != NFSP_OK) return rc;
     }
     h->iterations += 1;
   }
   NFSP_HIP(hipStreamSynchronize(h->ctx->stream));
+  for (size_t k = 0; k + 2 < ev.size(); k += 3) {
+    float walk = 0.f, apply = 0.f;
+    NFSP_HIP(hipEventElapsedTime(&walk, ev[k], ev[k + 1]));
+    NFSP_HIP(hipEventElapsedTime(&apply, ev[k + 1], ev[k + 2]));
+    h->ms_walk += (double)walk;
+    h->ms_apply += (double)apply;
+  }
+  if (h->timing) h->timed += iters;
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_mccfr_set_timing(nfsp_mccfr* h, int enable) {
+  NFSP_REQUIRE(h, "null argument");
+  h->timing = enable != 0;
+  h->ms_walk = h->ms_apply = 0.0;
+  h->timed = 0;
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_mccfr_get_timings(nfsp_mccfr* h, double out_ms[2], int64_t* iterations) {
+  NFSP_REQUIRE(h && out_ms && iterations, "null argument");
+  out_ms[0] = h->ms_walk;
+  out_ms[1] = h->ms_apply;
+  *iterations = h->timed;
   return NFSP_OK;
 }
 
@@ -1383,6 +1772,13 @@ extern "C" int nfsp_mccfr_destroy(nfsp_mccfr* h) {
   if (h->dev_rule) (void)hipFree(h->dev_rule);
   if (h->sw) (void)hipFree(h->sw);
   if (h->avg2) (void)hipFree(h->avg2);
+  if (h->dev_net) (void)hipFree(h->dev_net);
+  if (h->net_rows) (void)hipFree(h->net_rows);
+  if (h->net_w) (void)hipFree(h->net_w);
+  if (h->net_v) (void)hipFree(h->net_v);
+  if (h->net_z) (void)hipFree(h->net_z);
+  if (h->sigma_tab) (void)hipFree(h->sigma_tab);
+  if (h->net_loss) (void)hipFree(h->net_loss);
   delete h;
   return NFSP_OK;
 }

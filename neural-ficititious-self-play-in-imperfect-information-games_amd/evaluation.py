@@ -28,7 +28,9 @@ counted in traversals and terminals visited, to set beside the engine's curves i
 ``MccfrOsSolver`` runs outcome sampling on the same handle (``nfsp_mccfr_os_*``), whose traversal
 is one sampled hand, so its cost is in the engine's own unit, and ``MccfrVrSolver`` the same
 paths with baseline-corrected values (``nfsp_mccfr_vr_*``, VR-MCCFR).  ``MccfrXSolver`` puts
-regret matching+ and linear averaging on any of the three (``nfsp_mccfr_x_*``).
+regret matching+ and linear averaging on any of the three (``nfsp_mccfr_x_*``), and
+``MccfrNetSolver`` holds the regrets in two 30-64-3 nets per run (``nfsp_mccfr_net_*``): sampled
+regression CFR on the same walks.
 
 ``MemoryTable`` is a memory counted per information set on the device (``nfsp_memory_table``,
 csrc/memtab.hip): M_SL as the tabular average strategy the AR net is a fit of, M_RL as what the
@@ -949,6 +951,126 @@ class MccfrXSolver(MccfrVrSolver):
         native.check(self.ctx.L.nfsp_mccfr_weighted(self.h, int(run), Sw.ctypes.data_as(native.P)),
                      "nfsp_mccfr_weighted")
         return Sw
+
+
+class MccfrNetSolver(MccfrXSolver):
+    """Regret nets on the MCCFR handle (``nfsp_mccfr_net_create``): sampled regression CFR whose
+    walkers read the sigma of two 30-64-3 nets per run, each fitted to its seat's rows of R after the
+    seat's half-iteration.  ``sampling`` is ``MccfrXSolver``'s; ``cfgs`` is one ``(seed, walkers,
+    epsilon, regret, average, target, fit_steps, loss, lr, momentum)`` per run -- the first five as
+    ``MccfrXSolver``'s, target ``native.MCCFR_NET_TARGET_*`` or "avg" / "rowmax", loss "mse" / "huber"
+    or ``native.FIT_*``; ``init_seeds`` is one seed per run: the nets are
+    ``glorot_net(RandomState(seed))``, seat 0's first and then seat 1's.  ``sigma_table(k)`` is the
+    sigma the walkers read ("net") or regret matching on R ("table"), ``head(k)`` the nets' heads z,
+    ``net(k, seat)`` a seat's (w, v), ``set_net`` writes them between runs, ``fit_loss(k)`` the
+    ``[seat, before / after]`` losses of the last fits, ``current(k)`` the nets' sigma as a ``Policy``
+    and ``sigma_tv(k)`` the per-seat mean total variation between the two sigma tables.  Everything
+    else is ``MccfrXSolver``'s."""
+
+    TARGETS = {"avg": native.MCCFR_NET_TARGET_AVG, "rowmax": native.MCCFR_NET_TARGET_ROWMAX}
+
+    def __init__(self, ctx, cfgs=((1, 1024, 0.0, "plain", "uniform", "avg", 32, "mse", 0.5, 0.9),), sampling=0,
+                 init_seeds=None):
+        import torch
+        _Solver.__init__(self, ctx)
+        samp = int(self.SAMPLINGS.get(sampling, sampling))
+        self.cfgs = [(int(seed) & (2**64 - 1), int(w), float(eps), int(self.REGRETS.get(reg, reg)),
+                      int(self.AVERAGES.get(avg, avg)), int(self.TARGETS.get(tgt, tgt)), int(steps),
+                      int(FIT_LOSSES.get(loss, loss)), float(lr), float(mu))
+                     for seed, w, eps, reg, avg, tgt, steps, loss, lr, mu in cfgs]
+        self.n = len(self.cfgs)
+        self.init_seeds = [int(s) for s in (range(1, self.n + 1) if init_seeds is None else init_seeds)]
+        if len(self.init_seeds) != self.n:
+            raise ValueError("MccfrNetSolver: one init seed per run")
+        nets = []
+        for s in self.init_seeds:
+            rng = np.random.RandomState(s)
+            nets += [glorot_net(rng), glorot_net(rng)]
+        w0 = torch.as_tensor(np.stack(nets) if nets else np.zeros((0, native.NP), np.float32), device="cuda")
+        arr = (native.MccfrNetCfg * max(self.n, 1))(*[native.MccfrNetCfg(c[0], c[1], samp, *c[2:], 0) for c in self.cfgs])
+        ptrs = (native.P * max(2 * self.n, 1))(*[w0[k].data_ptr() for k in range(2 * self.n)])
+        h = native.P()
+        native.check(ctx.L.nfsp_mccfr_net_create(ctx.h, arr, self.n, ptrs, C.byref(h)), "nfsp_mccfr_net_create")
+        self.h = h
+
+    def _tables(self, run):
+        sg, tab, z = native.P(), native.P(), native.P()
+        native.check(self.ctx.L.nfsp_mccfr_net_tables(self.h, int(run), C.byref(sg), C.byref(tab), C.byref(z)),
+                     "nfsp_mccfr_net_tables")
+        return sg.value, tab.value, z.value
+
+    def _view(self, addr, numel, dtype):
+        import torch
+        return native.wrap_device(addr, numel, dtype, torch.device("cuda", torch.cuda.current_device()), self)
+
+    def sigma_table(self, run: int = 0, which: str = "net") -> np.ndarray:
+        """f64 ``[ndec, 3, 3]``: the nets' sigma ("net", what the walkers read) or regret matching on R ("table")."""
+        import torch
+        if which not in ("net", "table"):
+            raise ValueError('which must be "net" or "table"')
+        addr = self._tables(run)[which == "table"]
+        return self._view(addr, self.tree.ndec * 9, torch.float64).cpu().numpy().reshape(self.tree.ndec, 3, 3).copy()
+
+    def head(self, run: int = 0) -> np.ndarray:
+        """f32 ``[ndec, 3, 3]``: the heads z of the acting seat's net at every row."""
+        import torch
+        return self._view(self._tables(run)[2], self.tree.ndec * 9, torch.float32).cpu().numpy().reshape(
+            self.tree.ndec, 3, 3).copy()
+
+    def _net(self, run, seat):
+        import torch
+        w, v = native.P(), native.P()
+        native.check(self.ctx.L.nfsp_mccfr_net_weights(self.h, int(run), int(seat), C.byref(w), C.byref(v)),
+                     "nfsp_mccfr_net_weights")
+        return self._view(w.value, native.NP, torch.float32), self._view(v.value, native.NP, torch.float32)
+
+    def net(self, run: int = 0, seat: int = 0) -> tuple:
+        """(w, v) of a seat's net, f32 ``[NP]`` each, copied to the host."""
+        w, v = self._net(run, seat)
+        return w.cpu().numpy().copy(), v.cpu().numpy().copy()
+
+    def set_net(self, run: int, seat: int, w, v=None) -> "MccfrNetSolver":
+        """Writes a seat's net (and with ``v`` its momentum state) between runs; z and sigma follow at
+        the handle's next apply."""
+        import torch
+        dw, dv = self._net(run, seat)
+        for dst, src in ((dw, w), (dv, v)):
+            if src is None:
+                continue
+            src = np.ascontiguousarray(src, np.float32)
+            if src.shape != (native.NP,):
+                raise ValueError("a net has native.NP float32 values")
+            if not np.isfinite(src).all():
+                raise ValueError("set_net: values that are not finite")
+            dst.copy_(torch.as_tensor(src, device=dst.device))
+        torch.cuda.current_stream().synchronize()
+        return self
+
+    def fit_loss(self, run: int = 0) -> np.ndarray:
+        """``[seat, 2]``: the loss of the seat's last fit before its first step and at its final weights."""
+        out = np.zeros((2, 2))
+        native.check(self.ctx.L.nfsp_mccfr_net_loss(self.h, int(run), out.ctypes.data_as(C.POINTER(native.F64))),
+                     "nfsp_mccfr_net_loss")
+        return out
+
+    def current(self, run: int = 0) -> Policy:
+        return Policy(native.POL_TABLE, None, self._tables(run)[0], self)
+
+    def sigma_tv(self, run: int = 0) -> np.ndarray:
+        """Per seat, the mean over the seat's (d, r) rows of half the L1 distance between the nets' sigma and
+        regret matching on R."""
+        tv = 0.5 * np.abs(self.sigma_table(run, "net") - self.sigma_table(run, "table")).sum(axis=2)
+        return np.array([tv[self.tree.seat == s].mean() for s in (0, 1)])
+
+
+def mccfr_timings(solver, enable=None):
+    """``nfsp_mccfr_set_timing`` / ``_get_timings`` of any MCCFR solver: with ``enable`` given turns the
+    handle's event timing on or off (and zeroes its sums); returns (ms in walks, ms in applies, iterations)."""
+    if enable is not None:
+        native.check(solver.ctx.L.nfsp_mccfr_set_timing(solver.h, int(bool(enable))), "nfsp_mccfr_set_timing")
+    ms, it = (native.F64 * 2)(), native.I64(0)
+    native.check(solver.ctx.L.nfsp_mccfr_get_timings(solver.h, ms, C.byref(it)), "nfsp_mccfr_get_timings")
+    return float(ms[0]), float(ms[1]), int(it.value)
 
 
 class CfrSolver(_Solver):

@@ -123,6 +123,15 @@ class MccfrXCfg(C.Structure):
                 ("regret", C.c_int32), ("average", C.c_int32)]
 
 
+class MccfrNetCfg(C.Structure):
+    """``nfsp_mccfr_net_cfg``: ``nfsp_mccfr_x_cfg``'s fields, then what the run's two regret nets are
+    fitted with: the target (``MCCFR_NET_TARGET_*``), the steps per fit, the loss (``FIT_MSE`` /
+    ``FIT_HUBER``), the learning rate and the momentum"""
+    _fields_ = [("seed", C.c_uint64), ("walkers", C.c_int32), ("sampling", C.c_int32), ("epsilon", C.c_double),
+                ("regret", C.c_int32), ("average", C.c_int32), ("target", C.c_int32), ("fit_steps", C.c_int32),
+                ("loss", C.c_int32), ("lr", F32), ("momentum", F32), ("reserved", C.c_int32)]
+
+
 class MemSegment(C.Structure):
     """``nfsp_mem_segment``: n packed records (SlRec 16 B / RlRec 32 B) at a device address"""
     _fields_ = [("dev_recs", P), ("n", I64)]
@@ -225,6 +234,13 @@ SIGNATURES = {
     "nfsp_mccfr_rule": (I32, [P, I32, C.POINTER(I32)]),
     "nfsp_mccfr_average_of": (I32, [P, I32, I32, C.POINTER(P)]),
     "nfsp_mccfr_weighted": (I32, [P, I32, P]),
+    "nfsp_mccfr_net_cfgs_check": (I32, [I32, C.POINTER(MccfrNetCfg), I32, I64]),
+    "nfsp_mccfr_net_create": (I32, [P, C.POINTER(MccfrNetCfg), I32, C.POINTER(P), C.POINTER(P)]),
+    "nfsp_mccfr_net_tables": (I32, [P, I32, C.POINTER(P), C.POINTER(P), C.POINTER(P)]),
+    "nfsp_mccfr_net_weights": (I32, [P, I32, I32, C.POINTER(P), C.POINTER(P)]),
+    "nfsp_mccfr_net_loss": (I32, [P, I32, C.POINTER(F64)]),
+    "nfsp_mccfr_set_timing": (I32, [P, I32]),
+    "nfsp_mccfr_get_timings": (I32, [P, C.POINTER(F64), C.POINTER(I64)]),
     "nfsp_engine_set_loss_log": (I32, [P, I32]),
     "nfsp_engine_losses": (I32, [P, P]),
     "nfsp_engine_set_timing": (I32, [P, I32]),
@@ -312,6 +328,10 @@ MCCFR_OS_EPS_MIN = 0.0625       # outcome sampling's least exploration rate (NFS
 # nfsp_mccfr_x_cfg.regret / .average (NFSP_MCCFR_REGRET_*, NFSP_MCCFR_AVG_*)
 MCCFR_REGRET_PLAIN, MCCFR_REGRET_PLUS = 0, 1
 MCCFR_AVG_UNIFORM, MCCFR_AVG_LINEAR = 0, 1
+# nfsp_mccfr_net_cfg.target (NFSP_MCCFR_NET_TARGET_*), the most steps of a fit and the most iterations timed per run call
+MCCFR_NET_TARGET_AVG, MCCFR_NET_TARGET_ROWMAX = 0, 1
+MCCFR_NET_MAX_STEPS = 4096
+MCCFR_TIMED_ITERS = 4096
 # the memories as tables (NFSP_MEM_*, NFSP_MEMTAB_*)
 MEM_SL, MEM_RL, MEM_TD, MEM_TDQ = 0, 1, 2, 3
 # what nfsp_table_rows makes of a table (NFSP_ROWS_*), and the most sweeps and tables of a call

@@ -15,6 +15,8 @@ csrc/xfp.hip): the algorithm NFSP approximates, with an exact best response and 
     python tools/solve_game.py --solver mccfr-vr --time
     python tools/solve_game.py --game leduc --solver mccfr-vr --regret plus --average both --walkers 1024 --seeds 4
     python tools/solve_game.py --solver mccfr-vr --regret plus --average linear --time --time-walkers 1024 --time-runs 4
+    python tools/solve_game.py --game leduc --solver mccfr --regret-net --net-steps 32 --net-target rowmax --seeds 4
+    python tools/solve_game.py --solver mccfr --regret-net --net-steps 200 --time
 
 eq.npz holds ``table`` [ndec, 3 ranks, 3 actions] (rows as evaluation.GameTree's; usable as
 evaluation.Policy.table), ``game``, and per checkpoint (--every, doubling by default)
@@ -47,6 +49,15 @@ k_mccfr_vr_walk), with mccfr-os's options and output columns, --time included: t
 hands, the values on the way back up corrected by a learned baseline at every decision.  Its
 corrected values are larger than one pay, so its budget is smaller: W x iterations up to
 29,142,433 on Leduc at --epsilon 0.6.
+
+--regret-net, for the three mccfr solvers: the regrets are held in two 30-64-3 nets per run, fitted to R after
+every half-iteration, and the walkers read the nets' sigma (evaluation.MccfrNetSolver, k_mccfr_net_apply):
+sampled regression CFR.  --net-steps K, --net-lr, --net-momentum, --net-target avg|rowmax, --net-loss mse|huber
+and --net-init SEED set the fit; --regret / --average apply as below (left out: plain / uniform).  The lines add
+``exploitability_current`` (the nets' sigma scored), ``sigma_tv`` (per seat, the mean total variation between
+the nets' sigma and regret matching on R) and ``fit_loss`` ([seat][before, after] of the last fits), each with
+a ``_runs`` list over the seeds.  --time then times one iteration at --time-walkers and splits it
+into ``ms_walk`` and ``ms_applies`` with HIP events.  Without the flag every output is as it was.
 
 --regret plain|plus and --average uniform|linear|both, for the three mccfr solvers: regret matching+
 and the linearly weighted average on the same walks (evaluation.MccfrXSolver, k_mccfr_x_apply; a flag
@@ -113,6 +124,42 @@ def time_mccfr(ev, nat, epsilon=None, walkers=1 << 20, repeats=5, baselines=Fals
     solver.close()
 
 
+def time_mccfr_net(ev, nat, sampling, cfg, init_seed, repeats=5, runs=1):
+    """Regret nets (--regret-net --time): best of ``repeats`` single iterations of ``runs`` runs of ``cfg``
+    (seeds cfg's .. + runs - 1) after a warm-up, and of the same iteration split by the handle's own HIP
+    events (nfsp_mccfr_set_timing) into its two walks and its applies (k_mccfr_x_apply and k_mccfr_net_apply,
+    twice each)."""
+    import torch
+    ctx = nat.Context(1, game=nat.GAME_LEDUC)
+    cfgs = [(cfg[0] + k,) + tuple(cfg[1:]) for k in range(runs)]
+    solver = ev.MccfrNetSolver(ctx, cfgs, sampling, [init_seed + k for k in range(runs)]).run(1)
+    best = None
+    for _ in range(repeats):
+        before = solver.counts(0)
+        ev.mccfr_timings(solver, True)
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        solver.run(1)
+        t1.record()
+        t1.synchronize()
+        walk, applies, _ = ev.mccfr_timings(solver)
+        after = solver.counts(0)
+        rec = {"ms": t0.elapsed_time(t1), "ms_walk": walk, "ms_applies": applies,
+               "traversals": after[0] - before[0], "terminals": after[1] - before[1]}
+        if best is None or rec["ms"] < best["ms"]:
+            best = rec
+    best.update(game="leduc", solver=("mccfr", "mccfr-os", "mccfr-vr")[sampling], regret_net=True, walkers=cfg[1],
+                repeats=repeats, regret=cfg[3], average=cfg[4], net_target=cfg[5], net_steps=cfg[6], net_loss=cfg[7],
+                net_lr=cfg[8], net_momentum=cfg[9], net_init=init_seed,
+                us_per_fit_step_upper=(1e3 * best["ms_applies"] / (2 * cfg[6]) if cfg[6] else None))
+    if sampling:
+        best.update(epsilon=cfg[2])
+    if runs != 1:
+        best.update(runs=runs)
+    print(json.dumps(best), flush=True)
+    solver.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--game", default="leduc", choices=["leduc", "kuhn"])
@@ -133,6 +180,15 @@ def main():
                     help="mccfr, mccfr-os, mccfr-vr: the average scored; both scores the two of every run")
     ap.add_argument("--time-walkers", type=int, default=1 << 20, help="--time: walkers of a run")
     ap.add_argument("--time-runs", type=int, default=1, help="--time: runs in the one handle")
+    ap.add_argument("--regret-net", action="store_true",
+                    help="mccfr, mccfr-os, mccfr-vr: hold the regrets in two 30-64-3 nets per run (sampled regression CFR)")
+    ap.add_argument("--net-steps", type=int, default=32, help="--regret-net: full-batch steps per fit, 0 .. 4096")
+    ap.add_argument("--net-lr", type=float, default=0.5, help="--regret-net: learning rate")
+    ap.add_argument("--net-momentum", type=float, default=0.9, help="--regret-net: momentum, in [0, 1)")
+    ap.add_argument("--net-target", default="avg", choices=["avg", "rowmax"], help="--regret-net: how R is scaled into targets")
+    ap.add_argument("--net-loss", default="mse", choices=["mse", "huber"], help="--regret-net: the fit's loss")
+    ap.add_argument("--net-init", type=int, default=1, metavar="SEED",
+                    help="--regret-net: run k's nets are glorot_net(RandomState(SEED + k)), seat 0's then seat 1's")
     ap.add_argument("--out", default=None, metavar="PATH")
     args = ap.parse_args()
     import __graft_entry__
@@ -145,6 +201,17 @@ def main():
             ap.error("--regret and --average are for --solver mccfr, mccfr-os and mccfr-vr")
         rule = (args.regret or "plain", "linear" if args.average == "both" else args.average or "uniform")
     both = args.average == "both"
+    net = None                                          # the fit's part of a cfg: nfsp_mccfr_net_create
+    if args.regret_net:
+        if args.solver not in ("mccfr", "mccfr-os", "mccfr-vr"):
+            ap.error("--regret-net is for --solver mccfr, mccfr-os and mccfr-vr")
+        rule = rule or ("plain", "uniform")
+        net = (args.net_target, args.net_steps, args.net_loss, args.net_lr, args.net_momentum)
+    sampling = {"mccfr": 0, "mccfr-os": 1, "mccfr-vr": 2}.get(args.solver)
+    if args.time and net is not None:
+        eps = args.epsilon if sampling else 0.0
+        return time_mccfr_net(ev, nat, sampling, (1, args.time_walkers, eps) + rule + net, args.net_init,
+                              runs=args.time_runs)
     if args.time:
         if args.solver not in ("mccfr", "mccfr-os", "mccfr-vr"):
             ap.error("--time is for --solver mccfr, mccfr-os and mccfr-vr")
@@ -154,7 +221,11 @@ def main():
     xfp = args.solver == "xfp"
     outcome = args.solver in ("mccfr-os", "mccfr-vr")
     mccfr = args.solver == "mccfr" or outcome
-    if rule is not None:
+    if net is not None:
+        solver = ev.MccfrNetSolver(ctx, [(seed, args.walkers, args.epsilon if outcome else 0.0) + rule + net
+                                         for seed in range(1, args.seeds + 1)], sampling,
+                                   [args.net_init + k for k in range(args.seeds)])
+    elif rule is not None:
         solver = ev.MccfrXSolver(ctx, [(seed, args.walkers, args.epsilon if outcome else 0.0) + rule
                                        for seed in range(1, args.seeds + 1)],
                                  {"mccfr": "es", "mccfr-os": "os", "mccfr-vr": "vr"}[args.solver])
@@ -198,6 +269,14 @@ def main():
             rec.update(hands=counts[0][0], epsilon=args.epsilon)
         if rule is not None:
             rec.update(regret=rule[0], average=args.average or "uniform")
+        if net is not None:
+            cur = ev.evaluate_batch(ctx, [(c, c) for c in (solver.current(k) for k in range(solver.n))])
+            tv = [solver.sigma_tv(k).tolist() for k in range(solver.n)]
+            rec.update(regret_net=True, net_target=net[0], net_steps=net[1], net_loss=net[2], net_lr=net[3],
+                       net_momentum=net[4], net_init=args.net_init, exploitability_current=cur[0]["exploitability"],
+                       exploitability_current_runs=[x["exploitability"] for x in cur], sigma_tv=tv[0], sigma_tv_runs=tv,
+                       fit_loss=solver.fit_loss(0).tolist(),
+                       fit_loss_runs=[solver.fit_loss(k).tolist() for k in range(solver.n)])
         if both:
             uni = ev.evaluate_batch(ctx, [(a, a) for a in (solver.average(k, "uniform") for k in range(solver.n))])
             rec.update(exploitability_runs_uniform=[x["exploitability"] for x in uni],
