@@ -1084,6 +1084,15 @@ int nfsp_mccfr_net_create(nfsp_ctx* ctx, const nfsp_mccfr_net_cfg* cfgs /*[n]*/,
  * This and the two calls below are refused for a handle not made by nfsp_mccfr_net_create. */
 int nfsp_mccfr_net_tables(nfsp_mccfr* h, int run, const double** dev_sigma, const double** dev_sigma_tab,
                           const float** dev_z);
+/* nfsp_mccfr_net_create with nets of hidden width `hidden` (one of 16, 32, 64, 128; one width per
+ * handle): dev_w0[2 k + seat] is NP(hidden) f32 (nfsp_net_params), nfsp_mccfr_net_weights hands
+ * out NP(hidden) floats, the fit is nfsp_fit_tables_h's at that width, and everything else of the
+ * handle is unchanged.  hidden 64 is nfsp_mccfr_net_create, bit for bit.  A width that is not
+ * built, or whose rows do not fit in LDS for the game, is NFSP_EINVAL (nfsp_fit_width_check). */
+int nfsp_mccfr_net_create_h(nfsp_ctx* ctx, int hidden, const nfsp_mccfr_net_cfg* cfgs /*[n]*/, int n,
+                            const float* const* dev_w0 /*[n][2]*/, nfsp_mccfr** out);
+/* The nets' hidden width: 64 for a handle of nfsp_mccfr_net_create.  Refused for the other kinds. */
+int nfsp_mccfr_net_hidden(nfsp_mccfr* h, int* out);
 /* A seat's net and momentum state, NP f32 each on the device: may be read, and written between
  * runs (on the ctx stream, or synchronised with it).  Either of the two may be NULL. */
 int nfsp_mccfr_net_weights(nfsp_mccfr* h, int run, int seat, float** dev_w, float** dev_v);
@@ -1191,6 +1200,13 @@ int nfsp_group_td_tables(nfsp_group* g, int64_t* dev_out /*[R][ndec][3][3][3]*/,
  * host loops beyond.  Synchronises the ctx stream. */
 int nfsp_head_tables(nfsp_ctx* ctx, int game, const float* const* dev_w, const int* act, int n,
                      float* dev_out /*[n][ndec][3][3]*/);
+/* The same for n packed nets of hidden width `hidden` (16, 32, 64 or 128; NP(hidden) f32 each): per
+ * hidden unit the set bits' W1 entries ascending from +0, plus b1, ReLU; the units ascending into
+ * the three head sums, plus b2, then the activation.  That is fwd_lds' order, so at 64 the ReLU
+ * and linear heads have nfsp_head_tables' bits.  A plain kernel: one workgroup per net, the net in
+ * LDS in packed order, one observation per lane. */
+int nfsp_head_tables_h(nfsp_ctx* ctx, int game, int hidden, const float* const* dev_w, const int* act, int n,
+                       float* dev_out /*[n][ndec][3][3]*/);
 
 /* ---- tables that act (csrc/act_table.hip; csrc/rollout.hip k_rollout_t, k_rollout_gt) ----
  * Any of an engine's four (agent, role) slots can be acted by a table over nfsp_tree_export's
@@ -1337,7 +1353,8 @@ int nfsp_group_tabular_q(nfsp_group* g, int sweeps, const float* dev_fill, float
  * state, table and weights to the host once and checks, before anything is launched: every value
  * finite (a target as float too), the seat's weights >= 0 with a positive sum, CE targets >= 0, no
  * two jobs sharing dev_w / dev_v memory.  A violation is NFSP_EINVAL, nfsp_last_error names the
- * job and the row, and nothing was changed.  The hidden width is 64.  One workgroup per job, all
+ * job and the row, and nothing was changed.  The hidden width is 64 (nfsp_fit_tables_h: 16, 32,
+ * 64 or 128, see below).  One workgroup per job, all
  * `steps` inside the launch, the net, v, the rows and the workspace in LDS; at most
  * NFSP_FIT_MAX_JOBS jobs per launch, the host loops beyond.  Synchronises the ctx stream. */
 #define NFSP_FIT_CE 0      /* softmax head only */
@@ -1356,6 +1373,24 @@ typedef struct {
 int nfsp_fit_jobs_check(const nfsp_fit_job* jobs, int n, int64_t steps);   /* host only, no device */
 int nfsp_fit_tables(nfsp_ctx* ctx, int game, const nfsp_fit_job* jobs, int n, int64_t steps,
                     double* host_loss /*[n][2] or NULL*/);
+/* The hidden width as a parameter.  A packed net of width H is W1[30][H] | b1[H] | W2[H][3] | b2[3]:
+ * NP(H) = 34 H + 3 floats at the offsets 0, 30 H, 31 H, 34 H.  Built: H = 16, 32, 64, 128, each its
+ * own instantiation of the step above, operation for operation with H free (one thread owns one
+ * parameter: 3 H + 3 <= 512 threads for W2 and b2).  128 is the widest whose job fits a
+ * workgroup's LDS on Leduc: 4 (2 NPP + nm (16 + H)) bytes, NPP = NP rounded up to 4 and nm = 3 x
+ * the larger seat's rows rounded up to 4 (Leduc 196: 29,472 / 46,368 / 80,160 / 147,744 B).
+ * nfsp_net_params: *np = NP(hidden); another width is NFSP_EINVAL, and nfsp_last_error lists the
+ *   widths built.  Host only.
+ * nfsp_fit_width_check: the dynamic LDS a job of `game` needs at that width into *lds_bytes (may
+ *   be NULL); a width whose rows do not fit is NFSP_EINVAL naming the bytes and the bound, a width
+ *   that is not built as nfsp_net_params refuses it.  Host only.
+ * nfsp_fit_tables_h: nfsp_fit_tables with every job's dev_w / dev_v holding NP(hidden) floats (the
+ *   overlap and finiteness checks use that length).  hidden 64 is nfsp_fit_tables: same kernel,
+ *   same bits. */
+int nfsp_net_params(int hidden, int64_t* np);
+int nfsp_fit_width_check(int game, int hidden, int64_t* lds_bytes);
+int nfsp_fit_tables_h(nfsp_ctx* ctx, int game, int hidden, const nfsp_fit_job* jobs, int n, int64_t steps,
+                      double* host_loss /*[n][2] or NULL*/);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,14 @@
 // The body of the step loop is fit_step_body.inc, included where the loop stands: as a function it
 // cost k_fit_tables a scalar register (78 for 77), and that kernel's code is to stay as it was.
 //
+// The hidden width H is a parameter of the step: a packed net is W1[30][H] | b1[H] | W2[H][3] | b2[3],
+// NP(H) = 34 H + 3 floats at the offsets 0, 30 H, 31 H, 34 H (Width<H>).  The two kernels above are
+// the width-64 ones, written against nn::H and the constants below as before; every other supported
+// width (FIT_WIDTHS) is an instantiation of k_fit_tables_w<H> / k_mccfr_net_apply_w<H>, the same
+// kernel text (fit_tables_kernel.inc, mccfr_net_apply_kernel.inc) under FIT_WIDTH_NAMES(H).  128
+// is the largest width whose carve fits one workgroup's LDS on Leduc (147,744 B); FIT_WG >= 3 H + 3
+// holds up to it.
+//
 // Per step, f32 with fp contract off, every gradient from the weights before the step:
 //   z1[b][j]  = (sum over the SET bits i of obs[b], ascending, of W1[i][j]) + b1[j]
 //               -- the bits of sgd_step's 30-input sum for finite weights: x is 0 or 1, and adding
@@ -40,13 +48,42 @@ constexpr int ZS = H + 1;                     // z1's row stride: breaks the 64-
 constexpr int NPP = (NP + 3) & ~3;            // keeps every carve offset a multiple of 16 bytes
 static_assert(FIT_WG >= H * NA + NA, "one W2 / b2 entry per thread");
 
+// the layout of a packed net of width HH; Width<nn::H> is nn's
+template <int HH>
+struct Width {
+  static constexpr int H = HH, NP = OBS * HH + HH + HH * NA + NA;
+  static constexpr int OW1 = 0, OB1 = OBS * HH, OW2 = OB1 + HH, OB2 = OW2 + HH * NA;
+  static constexpr int ZS = HH + 1, NPP = (NP + 3) & ~3;
+  static_assert(FIT_WG >= HH * NA + NA, "one W2 / b2 entry per thread");
+};
+static_assert(Width<nn::H>::NP == nn::NP && Width<nn::H>::OB2 == nn::OB2 && Width<nn::H>::NPP == NPP, "Width<64> is nn's");
+
+// The names the shared kernel text and fit_step_body.inc use, for width HH, inside a kernel
+// instantiated per width; the width-64 kernels see nn's and this header's instead.
+#define FIT_WIDTH_NAMES(HH)                                                                                   \
+  constexpr int H = nfsp::fit::Width<HH>::H, NP = nfsp::fit::Width<HH>::NP, OW1 = nfsp::fit::Width<HH>::OW1,   \
+                OB1 = nfsp::fit::Width<HH>::OB1, OW2 = nfsp::fit::Width<HH>::OW2, OB2 = nfsp::fit::Width<HH>::OB2, \
+                ZS = nfsp::fit::Width<HH>::ZS;                                                                \
+  (void)OW1; (void)OB1
+
+// the supported widths, and whether `hidden` is one
+constexpr int FIT_WIDTHS[4] = {16, 32, 64, 128};
+inline bool fit_width_ok(int hidden) { return hidden == 16 || hidden == 32 || hidden == 64 || hidden == 128; }
+inline size_t fit_np(int hidden) { return (size_t)(OBS + 1 + NA) * hidden + NA; }
+#define NFSP_FIT_WIDTHS_TEXT "16, 32, 64 and 128"
+
 // LDS carve, in floats, for at most nm (a multiple of 4) rows
 struct FitLds {
   float *w, *v, *t, *m, *wh, *o, *dz, *lt, *z;
   uint32_t* x;
 };
 __host__ __device__ inline size_t fit_lds_floats(int nm) { return 2 * (size_t)NPP + (size_t)nm * (3 + 4 * NA + ZS); }
+inline size_t fit_lds_floats_h(int hidden, int nm) {
+  return 2 * ((fit_np(hidden) + 3) & ~(size_t)3) + (size_t)nm * (3 + 4 * NA + hidden + 1);
+}
+template <int HH = nn::H>
 __device__ inline FitLds fit_carve(char* raw, int nm) {
+  constexpr int NPP = Width<HH>::NPP;
   FitLds S;
   S.w = (float*)raw;
   S.v = S.w + NPP;
@@ -62,8 +99,11 @@ __device__ inline FitLds fit_carve(char* raw, int nm) {
 }
 
 // z1 and the raw head sums of every row from the weights in LDS; ends behind a barrier
+template <int HH = nn::H>
 __device__ inline void fit_forward(const FitLds& S, int N) {
 #pragma clang fp contract(off)
+  constexpr int H = Width<HH>::H, OW1 = Width<HH>::OW1, OB1 = Width<HH>::OB1, OW2 = Width<HH>::OW2,
+                OB2 = Width<HH>::OB2, ZS = Width<HH>::ZS;
   const int tid = threadIdx.x;
   for (int e = tid; e < N * H; e += FIT_WG) {
     const int b = e / H, j = e - b * H;

@@ -1,8 +1,9 @@
 // The body of one full-batch step (fit_step.h states it), included inside the step loop of
 // k_fit_tables and k_mccfr_net_apply.  In scope where it is included: FitLds S; int N, the net's
 // row count; int tid = threadIdx.x; int head, loss; float lr, mu -- all but tid uniform over the
-// workgroup.  Every loop runs to N; ends behind a barrier.
-  fit_forward(S, N);
+// workgroup; and the width's names H, ZS, OW2, OB2 (nn's and fit_step.h's at 64, FIT_WIDTH_NAMES
+// elsewhere).  Every loop runs to N; ends behind a barrier.
+  fit_forward<H>(S, N);
   fit_rows(S, N, head, loss);
   float g2 = 0.f;
   int w2i = -1;

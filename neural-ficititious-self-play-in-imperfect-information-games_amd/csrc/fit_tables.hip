@@ -5,7 +5,9 @@
 // nets only ever see sampled minibatches (agent/agent.py:209-264).
 //
 // The step itself (the carve, the forward, the rows, the gradients and the update) is fit_step.h's,
-// shared with k_mccfr_net_apply (mccfr.hip).
+// shared with k_mccfr_net_apply (mccfr.hip).  nfsp_fit_tables_h takes the hidden width: 64 is
+// k_fit_tables, 16, 32 and 128 are k_fit_tables_w<H>, the same kernel text (fit_tables_kernel.inc)
+// with the width's layout.
 //
 // Barriers: the step loop runs to A.steps and every loop inside a phase to the job's row count,
 // both uniform over the workgroup; the two single-thread regions (the loss sums) lie outside the
@@ -46,57 +48,27 @@ struct FitArgs {
 };
 
 __global__ void __launch_bounds__(FIT_WG) k_fit_tables(FitArgs A) {
-#pragma clang fp contract(off)
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  const FitDevJob J = A.jobs[blockIdx.x];
-  const int tid = threadIdx.x;
-  const int N = A.nrows[J.seat] * 3;
-  const int nmax = (A.nrows[0] > A.nrows[1] ? A.nrows[0] : A.nrows[1]) * 3;
-  const FitLds S = fit_carve(smem_raw, (nmax + 3) & ~3);
-  const float lr = J.lr, mu = J.mu;
-  const int head = J.head, loss = J.loss;
+#include "fit_tables_kernel.inc"
+}
 
-  for (int e = tid; e < NP; e += FIT_WG) {
-    S.w[e] = J.w[e];
-    S.v[e] = J.v ? J.v[e] : 0.f;
+// the same text at another width: one instantiation per entry of FIT_WIDTHS but 64
+template <int HH>
+__global__ void __launch_bounds__(FIT_WG) k_fit_tables_w(FitArgs A) {
+  FIT_WIDTH_NAMES(HH);
+  {
+#include "fit_tables_kernel.inc"
   }
-  for (int b = tid; b < N; b += FIT_WG) {
-    const int c = b / 3, r = b - c * 3;
-    const int d = A.rows[J.seat * FIT_SEAT_ROWS + c];
-    const int sid = d * 3 + r;
-    const bool raise = A.legal[d] & 1;
-    S.x[b] = A.obs[sid];
-    S.wh[b] = (float)((J.weight ? J.weight[sid] : 1.0) / J.wsum);
-    for (int k = 0; k < 3; ++k) {
-      S.t[3 * b + k] = (float)J.target[sid * 3 + k];
-      S.m[3 * b + k] = J.mask ? (J.mask[sid * 3 + k] ? 1.f : 0.f) : (k < 2 || raise ? 1.f : 0.f);
-    }
-  }
-  __syncthreads();
+}
 
-  fit_forward(S, N);
-  fit_rows(S, N, J.head, J.loss);
-  if (tid == 0) {
-    double L = 0.0;
-    for (int b = 0; b < N; ++b) L += (double)S.lt[b];
-    A.loss[2 * blockIdx.x] = L;
+using FitKernel = void (*)(FitArgs);
+FitKernel fit_kernel(int hidden) {
+  switch (hidden) {
+    case 16: return k_fit_tables_w<16>;
+    case 32: return k_fit_tables_w<32>;
+    case 64: return k_fit_tables;
+    case 128: return k_fit_tables_w<128>;
   }
-
-  for (int64_t s = 0; s < A.steps; ++s) {          // the launch's: uniform
-#include "fit_step_body.inc"
-  }
-
-  fit_forward(S, N);
-  fit_rows(S, N, J.head, J.loss);
-  if (tid == 0) {
-    double L = 0.0;
-    for (int b = 0; b < N; ++b) L += (double)S.lt[b];
-    A.loss[2 * blockIdx.x + 1] = L;
-  }
-  for (int e = tid; e < NP; e += FIT_WG) {
-    J.w[e] = S.w[e];
-    if (J.v) J.v[e] = S.v[e];
-  }
+  return nullptr;
 }
 
 std::string job_name(int k) { return "nfsp_fit job " + std::to_string(k); }
@@ -138,13 +110,51 @@ extern "C" int nfsp_fit_jobs_check(const nfsp_fit_job* jobs, int n, int64_t step
   return NFSP_OK;
 }
 
-extern "C" int nfsp_fit_tables(nfsp_ctx* ctx, int game, const nfsp_fit_job* jobs, int n, int64_t steps,
-                               double* host_loss) {
+extern "C" int nfsp_net_params(int hidden, int64_t* np) {
+  NFSP_REQUIRE(np, "null argument");
+  if (!fit_width_ok(hidden))
+    return nfsp::fail(NFSP_EINVAL, "hidden is " + std::to_string(hidden) + ": the widths built are " NFSP_FIT_WIDTHS_TEXT);
+  *np = (int64_t)fit_np(hidden);
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_fit_width_check(int game, int hidden, int64_t* lds_bytes) {
+  const nfsp::ex::HostTables* HT = nullptr;
+  int rc = nfsp::ex::host_tables(game, &HT);
+  if (rc != NFSP_OK) return rc;
+  NFSP_REQUIRE(hidden >= 1 && hidden <= 65536, "hidden is not a width: the widths built are " NFSP_FIT_WIDTHS_TEXT);
+  int nrows[2] = {0, 0};
+  for (uint8_t l : HT->legal) {
+    NFSP_REQUIRE((l >> 1) <= 1, "nfsp_fit_width_check: a row of a third seat");
+    ++nrows[l >> 1];
+  }
+  const int nm = (std::max(nrows[0], nrows[1]) * 3 + 3) & ~3;
+  const size_t lds = sizeof(float) * fit_lds_floats_h(hidden, nm);
+  if (lds > (size_t)nfsp::ex::EX_MAX_LDS)
+    return nfsp::fail(NFSP_EINVAL, "hidden " + std::to_string(hidden) + ": a job's rows need " + std::to_string(lds) +
+                                       " bytes of LDS, more than the " + std::to_string(nfsp::ex::EX_MAX_LDS) +
+                                       " a workgroup may take");
+  int64_t np = 0;
+  rc = nfsp_net_params(hidden, &np);              // a width that would fit, but is not built
+  if (rc != NFSP_OK) return rc;
+  if (lds_bytes) *lds_bytes = (int64_t)lds;
+  return NFSP_OK;
+}
+
+namespace {
+
+// nfsp_fit_tables (hidden 64: k_fit_tables itself) and nfsp_fit_tables_h
+int fit_tables_run(nfsp_ctx* ctx, int game, int hidden, const nfsp_fit_job* jobs, int n, int64_t steps,
+                   double* host_loss) {
   NFSP_REQUIRE(ctx, "null argument");
   int rc = nfsp_fit_jobs_check(jobs, n, steps);
   if (rc != NFSP_OK) return rc;
   NFSP_REQUIRE(game == ctx->game, "nfsp_fit_tables: game is not the ctx's");
-  static_assert(H == 64, "nfsp_fit_tables: hidden is 64");
+  int64_t lds_need = 0;
+  rc = nfsp_fit_width_check(game, hidden, &lds_need);
+  if (rc != NFSP_OK) return rc;
+  const int NP = (int)fit_np(hidden);             // the width's, not nn's, from here on
+  const FitKernel kernel = fit_kernel(hidden);
   const nfsp::ex::HostTables* HT = nullptr;
   rc = nfsp::ex::host_tables(game, &HT);
   if (rc != NFSP_OK) return rc;
@@ -157,8 +167,8 @@ extern "C" int nfsp_fit_tables(nfsp_ctx* ctx, int game, const nfsp_fit_job* jobs
     rows[s * FIT_SEAT_ROWS + nrows[s]++] = d;
   }
   const int nm = (std::max(nrows[0], nrows[1]) * 3 + 3) & ~3;
-  const size_t lds = sizeof(float) * fit_lds_floats(nm);
-  NFSP_REQUIRE(lds <= (size_t)nfsp::ex::EX_MAX_LDS, "nfsp_fit_tables: the rows do not fit in LDS");
+  const size_t lds = sizeof(float) * fit_lds_floats_h(hidden, nm);
+  NFSP_REQUIRE(lds <= (size_t)nfsp::ex::EX_MAX_LDS && lds == (size_t)lds_need, "nfsp_fit_tables: the rows do not fit in LDS");
   hipStream_t st = ctx->stream;
   if (n == 0) {
     NFSP_HIP(hipStreamSynchronize(st));
@@ -236,7 +246,7 @@ extern "C" int nfsp_fit_tables(nfsp_ctx* ctx, int game, const nfsp_fit_job* jobs
   NFSP_HIP(hipMalloc((void**)&buf.p, b_jobs + b_loss + b_rows));
   NFSP_HIP(hipMemcpyAsync(buf.p, dj.data(), b_jobs, hipMemcpyHostToDevice, st));
   NFSP_HIP(hipMemcpyAsync(buf.p + b_jobs + b_loss, rows.data(), b_rows, hipMemcpyHostToDevice, st));
-  NFSP_HIP(hipFuncSetAttribute((const void*)k_fit_tables, hipFuncAttributeMaxDynamicSharedMemorySize,
+  NFSP_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                nfsp::ex::EX_MAX_LDS));
   for (int k0 = 0; k0 < n; k0 += NFSP_FIT_MAX_JOBS) {
     FitArgs A{};
@@ -248,7 +258,7 @@ extern "C" int nfsp_fit_tables(nfsp_ctx* ctx, int game, const nfsp_fit_job* jobs
     A.steps = steps;
     A.nrows[0] = nrows[0];
     A.nrows[1] = nrows[1];
-    k_fit_tables<<<std::min(n - k0, NFSP_FIT_MAX_JOBS), FIT_WG, lds, st>>>(A);
+    kernel<<<std::min(n - k0, NFSP_FIT_MAX_JOBS), FIT_WG, lds, st>>>(A);
     NFSP_LAUNCHED("k_fit_tables");
   }
   std::vector<double> loss(2 * (size_t)n);
@@ -256,4 +266,16 @@ extern "C" int nfsp_fit_tables(nfsp_ctx* ctx, int game, const nfsp_fit_job* jobs
   NFSP_HIP(hipStreamSynchronize(st));
   if (host_loss) std::copy(loss.begin(), loss.end(), host_loss);
   return NFSP_OK;
+}
+
+}  // namespace
+
+extern "C" int nfsp_fit_tables(nfsp_ctx* ctx, int game, const nfsp_fit_job* jobs, int n, int64_t steps,
+                               double* host_loss) {
+  return fit_tables_run(ctx, game, nfsp::nn::H, jobs, n, steps, host_loss);
+}
+
+extern "C" int nfsp_fit_tables_h(nfsp_ctx* ctx, int game, int hidden, const nfsp_fit_job* jobs, int n, int64_t steps,
+                                 double* host_loss) {
+  return fit_tables_run(ctx, game, hidden, jobs, n, steps, host_loss);
 }

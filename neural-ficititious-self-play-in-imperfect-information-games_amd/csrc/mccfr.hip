@@ -44,7 +44,9 @@
 // Regret nets (nfsp_mccfr_net_*, the same handle, any of the three walks) add after it
 //   k_mccfr_net_apply  grid (2 seats, n runs), 512 lanes, one workgroup per (run, seat) with the
 //                  seat's 30-64-3 net, its momentum state and the seat's rows in LDS as
-//                  k_fit_tables holds them (fit_step.h).  The workgroup of the seat that walked
+//                  k_fit_tables holds them (fit_step.h).  A handle of nfsp_mccfr_net_create_h with
+//                  another width H launches k_mccfr_net_apply_w<H>: the same kernel text
+//                  (mccfr_net_apply_kernel.inc) at that width, one width per handle.  The workgroup of the seat that walked
 //                  turns R into targets and runs the run's K full-batch steps; every workgroup
 //                  then takes one forward and writes the heads z and the sigma the next walk
 //                  reads for its seat's rows.  k_mccfr_x_apply's regret matching on R goes to a
@@ -84,6 +86,7 @@ struct nfsp_mccfr {
   void* dev_net = nullptr;                // that kind: per run target, K, loss, lr, momentum (NetDevCfg)
   int32_t* net_rows = nullptr;            // that kind: [2][FIT_SEAT_ROWS], a seat's decision rows, ascending
   int net_nrows[2] = {0, 0};
+  int net_hidden = nfsp::nn::H;           // that kind: the nets' width, one per handle (fit_step.h FIT_WIDTHS)
   float* net_w = nullptr;                 // that kind: per run and seat the net, NP f32
   float* net_v = nullptr;                 // that kind: per run and seat its momentum state
   float* net_z = nullptr;                 // that kind: per run the heads, [ndec][3][3]
@@ -843,101 +846,29 @@ struct NetApplyArgs {
 // uniform over the workgroup; the two single-thread regions (the loss sums) lie outside the step
 // loop.
 __global__ void __launch_bounds__(nfsp::fit::FIT_WG) k_mccfr_net_apply(NetApplyArgs A) {
-#pragma clang fp contract(off)
-  using namespace nfsp::fit;
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  const int seat = blockIdx.x, run = blockIdx.y;
-  const int tid = threadIdx.x;
-  const bool fits = A.fitseat == 2 || A.fitseat == seat;
-  const NetDevCfg C = A.net[run];
-  const int N = A.nrows[seat] * 3;
-  const int nmax = (A.nrows[0] > A.nrows[1] ? A.nrows[0] : A.nrows[1]) * 3;
-  const FitLds S = fit_carve(smem_raw, (nmax + 3) & ~3);
-  const float lr = C.lr, mu = C.mu;
-  const int head = NFSP_ACT_LINEAR, loss = C.loss;
-  const size_t n9 = (size_t)A.ndec * 9;
-  float* gw = A.w + ((size_t)run * 2 + seat) * NP;
-  float* gv = A.v + ((size_t)run * 2 + seat) * NP;
-  const long long* R = A.state + (size_t)run * 4 * n9;
-  const double den = ((double)A.cfg[run].walkers * Q) * A.tw;
-  const float what = (float)(1.0 / (double)N);
+#include "mccfr_net_apply_kernel.inc"
+}
 
-  for (int e = tid; e < NP; e += FIT_WG) {
-    S.w[e] = gw[e];
-    S.v[e] = gv[e];
-  }
-  for (int b = tid; b < N; b += FIT_WG) {
-    const int c = b / 3, r = b - c * 3;
-    const int d = A.rows[seat * FIT_SEAT_ROWS + c];
-    const int sid = d * 3 + r;
-    const bool raise = A.legal[d] & 1;
-    S.x[b] = A.obs[sid];
-    S.wh[b] = what;
-    const long long r0 = R[sid * 3], r1 = R[sid * 3 + 1], r2 = raise ? R[sid * 3 + 2] : 0;
-    double y0, y1, y2;
-    if (C.target == NFSP_MCCFR_NET_TARGET_AVG) {
-      y0 = (double)r0 / den;
-      y1 = (double)r1 / den;
-      y2 = (double)r2 / den;
-    } else {
-      const long long a0 = r0 < 0 ? -r0 : r0, a1 = r1 < 0 ? -r1 : r1, a2 = r2 < 0 ? -r2 : r2;
-      const long long m01 = a0 > a1 ? a0 : a1, m = m01 > a2 ? m01 : a2;
-      y0 = m ? (double)r0 / (double)m : 0.0;
-      y1 = m ? (double)r1 / (double)m : 0.0;
-      y2 = m ? (double)r2 / (double)m : 0.0;
-    }
-    S.t[3 * b] = (float)y0;
-    S.t[3 * b + 1] = (float)y1;
-    S.t[3 * b + 2] = raise ? (float)y2 : 0.f;
-    S.m[3 * b] = 1.f;
-    S.m[3 * b + 1] = 1.f;
-    S.m[3 * b + 2] = raise ? 1.f : 0.f;
-  }
-  __syncthreads();
-
-  if (fits) {                                        // the workgroup's: uniform
-    fit_forward(S, N);
-    fit_rows(S, N, head, loss);
-    if (tid == 0) {
-      double L = 0.0;
-      for (int b = 0; b < N; ++b) L += (double)S.lt[b];
-      A.loss[((size_t)run * 2 + seat) * 2] = L;
-    }
-    for (int s = 0; s < C.steps; ++s) {              // the run's: uniform
-#include "fit_step_body.inc"
-    }
-  }
-
-  fit_forward(S, N);
-  if (fits) {
-    fit_rows(S, N, head, loss);
-    if (tid == 0) {
-      double L = 0.0;
-      for (int b = 0; b < N; ++b) L += (double)S.lt[b];
-      A.loss[((size_t)run * 2 + seat) * 2 + 1] = L;
-    }
-    for (int e = tid; e < NP; e += FIT_WG) {
-      gw[e] = S.w[e];
-      gv[e] = S.v[e];
-    }
-  }
-  for (int b = tid; b < N; b += FIT_WG) {
-    const int c = b / 3, r = b - c * 3;
-    const int d = A.rows[seat * FIT_SEAT_ROWS + c];
-    const size_t at = ((size_t)d * 3 + r) * 3;      // < n9
-    const bool raise = A.legal[d] & 1;
-    double rp[3];
-    for (int k = 0; k < 3; ++k) {
-      const float z = S.o[3 * b + k];
-      A.z[(size_t)run * n9 + at + k] = z;
-      rp[k] = (double)z > 0.0 ? (double)z : 0.0;
-    }
-    if (!raise) rp[2] = 0.0;
-    average_row(rp, raise, A.tabs + (size_t)run * 2 * n9 + at);
+// the same text at another width: one instantiation per entry of fit::FIT_WIDTHS but 64
+template <int HH>
+__global__ void __launch_bounds__(nfsp::fit::FIT_WG) k_mccfr_net_apply_w(NetApplyArgs A) {
+  FIT_WIDTH_NAMES(HH);
+  {
+#include "mccfr_net_apply_kernel.inc"
   }
 }
 
-// seat i's decisions on the longest path below n
+using NetApplyKernel = void (*)(NetApplyArgs);
+NetApplyKernel net_apply_kernel(int hidden) {
+  switch (hidden) {
+    case 16: return k_mccfr_net_apply_w<16>;
+    case 32: return k_mccfr_net_apply_w<32>;
+    case 64: return k_mccfr_net_apply;
+    case 128: return k_mccfr_net_apply_w<128>;
+  }
+  return nullptr;
+}
+
 int frames_below(const HostTables& H, int n, int i) {
   if (n < 0) return 0;
   const DevNode& N = H.nodes[n];
@@ -1025,7 +956,7 @@ int launch_x_apply(nfsp_mccfr* h, const ExTables& T, int walked, int64_t t) {
 
 size_t net_lds(const nfsp_mccfr* h) {
   const int nm = (std::max(h->net_nrows[0], h->net_nrows[1]) * 3 + 3) & ~3;
-  return sizeof(float) * nfsp::fit::fit_lds_floats(nm);
+  return sizeof(float) * nfsp::fit::fit_lds_floats_h(h->net_hidden, nm);
 }
 
 // fitseat: the seat that walked, 2 at creation; t as launch_x_apply's
@@ -1047,7 +978,7 @@ int launch_net_apply(nfsp_mccfr* h, const ExTables& T, int fitseat, int64_t t) {
   A.nrows[1] = h->net_nrows[1];
   A.ndec = h->ndec;
   A.fitseat = fitseat;
-  k_mccfr_net_apply<<<dim3(2, h->n), nfsp::fit::FIT_WG, net_lds(h), h->ctx->stream>>>(A);
+  net_apply_kernel(h->net_hidden)<<<dim3(2, h->n), nfsp::fit::FIT_WG, net_lds(h), h->ctx->stream>>>(A);
   NFSP_LAUNCHED("k_mccfr_net_apply");
   return NFSP_OK;
 }
@@ -1265,7 +1196,7 @@ namespace {
 // net (the cfgs of nfsp_mccfr_net_create, with x) adds the nets from dev_w0, their tables and their apply.
 int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os_cfg* os, int n, nfsp_mccfr** out,
                   int sampling = -1, const nfsp_mccfr_x_cfg* x = nullptr, const nfsp_mccfr_net_cfg* net = nullptr,
-                  const float* const* dev_w0 = nullptr) {
+                  const float* const* dev_w0 = nullptr, int hidden = nfsp::nn::H) {
   const HostTables* H = nullptr;
   int rc = host_tables(ctx->game, &H);
   if (rc != NFSP_OK) return rc;
@@ -1294,7 +1225,10 @@ int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os
   int nrows[2] = {0, 0};
   if (net) {
     using namespace nfsp::fit;
-    static_assert(nfsp::nn::H == 64, "nfsp_mccfr_net_create: hidden is 64");
+    int64_t lds_need = 0;
+    rc = nfsp_fit_width_check(ctx->game, hidden, &lds_need);
+    if (rc != NFSP_OK) return rc;
+    const size_t NP = fit_np(hidden);               // the width's, not nn's
     rows.assign(2 * FIT_SEAT_ROWS, 0);
     for (int d = 0; d < T->ndec; ++d) {
       const int s = H->legal[d] >> 1;
@@ -1303,7 +1237,7 @@ int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os
       rows[s * FIT_SEAT_ROWS + nrows[s]++] = d;
     }
     const int nm = (std::max(nrows[0], nrows[1]) * 3 + 3) & ~3;
-    NFSP_REQUIRE(sizeof(float) * fit_lds_floats(nm) <= (size_t)EX_MAX_LDS,
+    NFSP_REQUIRE(sizeof(float) * fit_lds_floats_h(hidden, nm) == (size_t)lds_need && lds_need <= EX_MAX_LDS,
                  "nfsp_mccfr_net_create: the rows do not fit in LDS");
     w0.resize((size_t)n * 2 * NP);
     for (int k = 0; k < 2 * n; ++k)
@@ -1361,9 +1295,10 @@ int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os
     h->net_cfgs.assign(net, net + n);
     h->net_nrows[0] = nrows[0];
     h->net_nrows[1] = nrows[1];
+    h->net_hidden = hidden;
     for (int k = 0; k < n; ++k)
       ncfg.push_back(NetDevCfg{net[k].target, net[k].fit_steps, net[k].loss, net[k].lr, net[k].momentum});
-    const size_t b_net = sizeof(float) * 2 * nfsp::nn::NP * n;
+    const size_t b_net = sizeof(float) * 2 * nfsp::fit::fit_np(hidden) * n;
     if (e == hipSuccess) e = hipMalloc(&h->dev_net, sizeof(NetDevCfg) * n);
     if (e == hipSuccess) e = hipMalloc(&h->net_rows, sizeof(int32_t) * rows.size());
     if (e == hipSuccess) e = hipMalloc(&h->net_w, b_net);
@@ -1380,7 +1315,8 @@ int create_handle(nfsp_ctx* ctx, const nfsp_mccfr_cfg* cfgs, const nfsp_mccfr_os
     if (e == hipSuccess) e = hipMemsetAsync(h->net_z, 0, sizeof(float) * n9 * n, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(h->net_loss, 0, sizeof(double) * 4 * n, ctx->stream);
     if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)k_mccfr_net_apply, hipFuncAttributeMaxDynamicSharedMemorySize, EX_MAX_LDS);
+      e = hipFuncSetAttribute((const void*)net_apply_kernel(hidden), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              EX_MAX_LDS);
   }
   if (e == hipSuccess) e = hipMemsetAsync(h->state, 0, b_state, ctx->stream);
   if (e == hipSuccess) e = hipMemsetAsync(h->counts, 0, b_counts, ctx->stream);
@@ -1468,10 +1404,17 @@ extern "C" int nfsp_mccfr_x_create(nfsp_ctx* ctx, const nfsp_mccfr_x_cfg* cfgs, 
 
 extern "C" int nfsp_mccfr_net_create(nfsp_ctx* ctx, const nfsp_mccfr_net_cfg* cfgs, int n, const float* const* dev_w0,
                                      nfsp_mccfr** out) {
+  return nfsp_mccfr_net_create_h(ctx, nfsp::nn::H, cfgs, n, dev_w0, out);
+}
+
+extern "C" int nfsp_mccfr_net_create_h(nfsp_ctx* ctx, int hidden, const nfsp_mccfr_net_cfg* cfgs, int n,
+                                       const float* const* dev_w0, nfsp_mccfr** out) {
   NFSP_REQUIRE(cfgs && out && dev_w0, "null argument");
   NFSP_REQUIRE(n >= 1 && n <= NFSP_MCCFR_MAX_RUNS, "n must be in 1 .. NFSP_MCCFR_MAX_RUNS");
   NFSP_REQUIRE(ctx, "null argument");
   int rc = nfsp_mccfr_net_cfgs_check(ctx->game, cfgs, n, 0);
+  if (rc != NFSP_OK) return rc;
+  rc = nfsp_fit_width_check(ctx->game, hidden, nullptr);
   if (rc != NFSP_OK) return rc;
   for (int k = 0; k < 2 * n; ++k) NFSP_REQUIRE(dev_w0[k], "nfsp_mccfr_net_create: a null initial net");
   const int sampling = cfgs[0].sampling;
@@ -1485,7 +1428,7 @@ extern "C" int nfsp_mccfr_net_create(nfsp_ctx* ctx, const nfsp_mccfr_net_cfg* cf
     vr[k] = nfsp_mccfr_vr_cfg{cfgs[k].seed, cfgs[k].walkers, 0, cfgs[k].epsilon};
     x[k] = nfsp_mccfr_x_cfg{cfgs[k].seed, cfgs[k].walkers, sampling, cfgs[k].epsilon, cfgs[k].regret, cfgs[k].average};
   }
-  rc = create_handle(ctx, plain.data(), sampling ? os.data() : nullptr, n, out, sampling, x.data(), cfgs, dev_w0);
+  rc = create_handle(ctx, plain.data(), sampling ? os.data() : nullptr, n, out, sampling, x.data(), cfgs, dev_w0, hidden);
   if (rc == NFSP_OK && sampling == 2) (*out)->vr_cfgs = vr;
   return rc;
 }
@@ -1512,9 +1455,16 @@ extern "C" int nfsp_mccfr_net_weights(nfsp_mccfr* h, int run, int seat, float** 
   NFSP_NET_HANDLE(h);
   NFSP_REQUIRE(run < h->n, "run out of range");
   NFSP_REQUIRE(seat == 0 || seat == 1, "seat must be 0 or 1");
-  const size_t at = ((size_t)run * 2 + seat) * nfsp::nn::NP;
+  const size_t at = ((size_t)run * 2 + seat) * nfsp::fit::fit_np(h->net_hidden);
   if (dev_w) *dev_w = h->net_w + at;
   if (dev_v) *dev_v = h->net_v + at;
+  return NFSP_OK;
+}
+
+extern "C" int nfsp_mccfr_net_hidden(nfsp_mccfr* h, int* out) {
+  NFSP_REQUIRE(h && out, "null argument");
+  NFSP_NET_HANDLE(h);
+  *out = h->net_hidden;
   return NFSP_OK;
 }
 

@@ -236,9 +236,9 @@ def _fit_weights(ctx, pol, weights, tree):
     return np.asarray(weights, np.float64).reshape(tree.ndec, 3)
 
 
-def _init_pairs(init, n):
+def _init_pairs(init, n, hidden=64):
     """``init`` of a distillation as n pairs of packed nets: a seed (seat 0's net, then seat 1's,
-    Glorot, from one stream), a pair of nets, or a list of either."""
+    Glorot of width ``hidden``, from one stream), a pair of nets of that width, or a list of either."""
     items = list(init) if isinstance(init, (list, tuple)) and not (len(init) == 2 and np.ndim(init[0]) == 1) else [init]
     if len(items) == 1:
         items = items * n
@@ -248,13 +248,16 @@ def _init_pairs(init, n):
     for it in items:
         if np.ndim(it) == 0:
             rng = np.random.RandomState(int(it))
-            out.append((ev.glorot_net(rng), ev.glorot_net(rng)))
+            out.append((ev.glorot_net(rng, hidden), ev.glorot_net(rng, hidden)))
         else:
             out.append((np.asarray(it[0], np.float32), np.asarray(it[1], np.float32)))
+            for w in out[-1]:
+                if ev.net_width(w) != hidden:
+                    raise ValueError(f"an init net of width {ev.net_width(w)} where hidden is {hidden}")
     return out
 
 
-def _variants(lr, momentum, init):
+def _variants(lr, momentum, init, hidden=64):
     ls = list(lr) if isinstance(lr, (list, tuple)) else [lr]
     ms = list(momentum) if isinstance(momentum, (list, tuple)) else [momentum]
     n = max(len(ls), len(ms), len(init) if isinstance(init, list) else 1)
@@ -262,7 +265,7 @@ def _variants(lr, momentum, init):
     if len(ls) != n or len(ms) != n:
         raise ValueError("lr, momentum and init lists must have one length")
     many = any(isinstance(x, (list, tuple)) for x in (lr, momentum)) or isinstance(init, list)
-    return ls, ms, _init_pairs(init, n), many
+    return ls, ms, _init_pairs(init, n, hidden), many
 
 
 def q_targets(ctx, policy, tree=None):
@@ -277,8 +280,10 @@ def q_targets(ctx, policy, tree=None):
     return qx, reach, (beta, q, reach)
 
 
-def distill_policy(ctx, table, weights="visit", steps: int = 2000, lr=0.5, momentum=0.9, init=0, tree=None):
-    """The approximation floor of the AR net: two 30-64-3 softmax nets, one per seat, fitted to
+def distill_policy(ctx, table, weights="visit", steps: int = 2000, lr=0.5, momentum=0.9, init=0, tree=None,
+                   hidden: int = 64):
+    """The approximation floor of the AR net: two 30-H-3 softmax nets (``hidden``: 16, 32, 64 or
+    128; scored through ``evaluation.net_policy`` where it is not 64), one per seat, fitted to
     ``table`` (a ``Policy`` or ``[ndec, 3, 3]``; as executed) by ``evaluation.fit_tables`` with
     cross-entropy.  ``weights``: "visit" (``evaluation.visit_weights`` of the table against itself:
     fitted where it is played), "uniform", or ``[ndec, 3]``.  ``init``: a seed for Glorot nets, or
@@ -293,14 +298,19 @@ def distill_policy(ctx, table, weights="visit", steps: int = 2000, lr=0.5, momen
     tree = tree or ev.GameTree.of(ctx.game)
     pol, tab = _as_policy(ctx, table, tree)
     wt = _fit_weights(ctx, pol, weights, tree)
-    ls, ms, inits, many = _variants(lr, momentum, init)
+    native.net_params(hidden)
+    ls, ms, inits, many = _variants(lr, momentum, init, hidden)
     jobs = [ev.FitJob(inits[k][s], tab, s, native.ACT_SOFTMAX, "ce", ls[k], ms[k], wt)
             for k in range(len(ls)) for s in (0, 1)]
     losses = ev.fit_tables(ctx, jobs, steps, tree)
     pairs = [(pol, pol)]
     for k in range(len(ls)):
         for mode in (0, 1):
-            pairs.append((ev.Policy.ar(jobs[2 * k].w, mode), ev.Policy.ar(jobs[2 * k + 1].w, mode)))
+            if hidden == 64:
+                pairs.append((ev.Policy.ar(jobs[2 * k].w, mode), ev.Policy.ar(jobs[2 * k + 1].w, mode)))
+            else:
+                kind = native.POL_AR_ARGMAX if mode else native.POL_AR_SOFTMAX
+                pairs.append((ev.net_policy(ctx, jobs[2 * k].w, kind, tree), ev.net_policy(ctx, jobs[2 * k + 1].w, kind, tree)))
     res = ev.evaluate_batch(ctx, pairs)
     w = np.ones((tree.ndec, 3)) if wt is None else wt
     ent = []
@@ -316,8 +326,9 @@ def distill_policy(ctx, table, weights="visit", steps: int = 2000, lr=0.5, momen
 
 
 def distill_q(ctx, policy, linear: bool = False, loss: str = "mse", steps: int = 2000, lr=0.05, momentum=0.9,
-              init=0, tree=None):
-    """The approximation floor of the Q net: two 30-64-3 nets, one per seat, with the ReLU head
+              init=0, tree=None, hidden: int = 64):
+    """The approximation floor of the Q net: two 30-H-3 nets (``hidden`` as ``distill_policy``'s), one
+    per seat, with the ReLU head
     (the reference's) or the ``linear`` one, fitted to the exact action values against ``policy``
     -- qx = q / reach of ``best_response(values=True)`` -- with weight ``reach`` and the legal
     actions as the mask, by "mse" or "huber".  Returns ``{"nets", "losses" [2, 2], "reports":
@@ -328,13 +339,18 @@ def distill_q(ctx, policy, linear: bool = False, loss: str = "mse", steps: int =
     pol, _ = _as_policy(ctx, policy, tree)
     qx, reach, (beta, q, _) = q_targets(ctx, pol, tree)
     head = native.ACT_LINEAR if linear else native.ACT_RELU
-    ls, ms, inits, many = _variants(lr, momentum, init)
+    native.net_params(hidden)
+    ls, ms, inits, many = _variants(lr, momentum, init, hidden)
     jobs = [ev.FitJob(inits[k][s], qx, s, head, loss, ls[k], ms[k], reach) for k in range(len(ls)) for s in (0, 1)]
     losses = ev.fit_tables(ctx, jobs, steps, tree)
     heads = ev.head_tables(ctx, [j.w for j in jobs], [head] * len(jobs), tree).cpu().numpy()
     pairs = []
+    kind = native.POL_BR_GREEDY_LINEAR if linear else native.POL_BR_GREEDY
+
+    def greedy(w):
+        return ev.Policy.br(w, linear) if hidden == 64 else ev.net_policy(ctx, w, kind, tree)
     for k in range(len(ls)):
-        pairs += [(ev.Policy.br(jobs[2 * k].w, linear), pol), (pol, ev.Policy.br(jobs[2 * k + 1].w, linear))]
+        pairs += [(greedy(jobs[2 * k].w), pol), (pol, greedy(jobs[2 * k + 1].w))]
     res = ev.evaluate_batch(ctx, pairs)
     none = np.zeros((tree.ndec, 3, 3, 3), np.int64)
     out = []
@@ -350,14 +366,18 @@ def distill_q(ctx, policy, linear: bool = False, loss: str = "mse", steps: int =
     return out if many else out[0]
 
 
-def warm_start(engines, policy, q="exact", steps: int = 2000, lr=(0.5, 0.05), momentum=0.9, weights="visit") -> list:
+def warm_start(engines, policy, q="exact", steps: int = 2000, lr=(0.5, 0.05), momentum=0.9, weights="visit",
+               hidden: int = 64) -> list:
     """``SelfPlayEngine.warm_start`` of every engine (one ctx, one game), all of their jobs -- up to
     four per engine -- in ONE ``fit_tables`` call: the AR nets fitted in place to ``policy`` as
     ``distill_policy`` fits them, from the nets as they are; with ``q`` the BR nets to the action
     values (``q_targets`` against ``policy`` for "exact", or an array ``[ndec, 3, 3]``) with weight
     ``reach``, the head and loss the engine's quirks train, then copied to the target nets.
-    ``lr``: one rate or (AR, BR)."""
+    ``lr``: one rate or (AR, BR).  ``hidden`` must be 64: the engine's nets are 64 wide."""
     import torch
+    if int(hidden) != 64:
+        raise ValueError(f"warm_start: hidden is {hidden}, but the engine is 64 wide: its nets, chains and rollout "
+                         "are built for 30-64-3 only")
     e0 = engines[0]
     ctx = e0.ctx
     tree = ev.GameTree.of(ctx.game)

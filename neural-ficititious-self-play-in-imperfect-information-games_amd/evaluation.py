@@ -29,8 +29,8 @@ counted in traversals and terminals visited, to set beside the engine's curves i
 is one sampled hand, so its cost is in the engine's own unit, and ``MccfrVrSolver`` the same
 paths with baseline-corrected values (``nfsp_mccfr_vr_*``, VR-MCCFR).  ``MccfrXSolver`` puts
 regret matching+ and linear averaging on any of the three (``nfsp_mccfr_x_*``), and
-``MccfrNetSolver`` holds the regrets in two 30-64-3 nets per run (``nfsp_mccfr_net_*``): sampled
-regression CFR on the same walks.
+``MccfrNetSolver`` holds the regrets in two 30-H-3 nets per run (``nfsp_mccfr_net_*``; H is 64, or
+16, 32 or 128 through ``hidden`` / ``init_nets``): sampled regression CFR on the same walks.
 
 ``MemoryTable`` is a memory counted per information set on the device (``nfsp_memory_table``,
 csrc/memtab.hip): M_SL as the tabular average strategy the AR net is a fit of, M_RL as what the
@@ -44,7 +44,10 @@ the truth, and what the net makes of its data.
 
 ``fit_tables`` (``nfsp_fit_tables``, csrc/fit_tables.hip) goes the other way: ``FitJob``s put a
 table into a packed net by weighted full-batch gradient descent on the device, and
-``visit_weights`` gives the exact visit distribution to weight them with.
+``visit_weights`` gives the exact visit distribution to weight them with.  The fit, ``head_tables``
+and the regret nets take packed nets of hidden width 16, 32, 64 or 128 (``net_width`` reads it from
+a net's length); ``net_policy`` turns a net of any of them into the ``Policy.table`` it executes,
+which is how ``evaluate`` and ``best_response`` score a width the evaluators' net kinds (64) lack.
 
 Nothing here knows an engine: what needs both an engine and this module is ``diagnostics``.
 """
@@ -506,22 +509,90 @@ def table_rows(ctx, stat: int, tabs, fill=None, prev=None, tree: GameTree | None
     return out, c[0] if one else c
 
 
-def head_tables(ctx, nets, acts, tree: GameTree | None = None):
+def net_width(w) -> int:
+    """The hidden width of a packed net (array or tensor), from its length 34 H + 3; a length that
+    is no built width's (``native.FIT_WIDTHS``) is refused.  A device address carries no length: 64."""
+    if isinstance(w, int):
+        return 64
+    n = int(w.numel() if hasattr(w, "numel") else np.asarray(w).size)
+    for h in native.FIT_WIDTHS:
+        if n == native.net_params(h):
+            return h
+    raise ValueError(f"a packed net has 34 H + 3 values for H in {native.FIT_WIDTHS}, got {n}")
+
+
+def _one_width(nets, what: str, hidden=None) -> int:
+    """the one width of ``nets`` (``hidden`` for device addresses, 64 without it); mixed widths are refused"""
+    ws = {int(hidden) if isinstance(w, int) and hidden is not None else net_width(w) for w in nets}
+    if hidden is not None:
+        ws.add(int(hidden))
+    if len(ws) > 1:
+        raise ValueError(f"{what}: nets of widths {sorted(ws)} in one call; one width per call")
+    h = ws.pop() if ws else 64
+    native.net_params(h)
+    return h
+
+
+def head_tables(ctx, nets, acts, tree: GameTree | None = None, hidden=None):
     """``nfsp_head_tables``: the raw head outputs of packed nets (arrays, tensors or device
     addresses) at every row and rank, a float32 device tensor ``[n, ndec, 3, 3]`` -- for a BR net
     the Q values it holds, with the bits the rollout acts on.  ``acts[k]``: ``native.ACT_RELU``,
-    ``ACT_LINEAR`` or ``ACT_SOFTMAX``.  All three outputs are there, an illegal raise's too."""
+    ``ACT_LINEAR`` or ``ACT_SOFTMAX``.  All three outputs are there, an illegal raise's too.
+    The width is the nets' (``net_width``; ``hidden`` for device addresses), one per call: other
+    than 64, or with ``hidden`` given, the call is ``nfsp_head_tables_h``'s plain kernel."""
     import torch
     tree = tree or GameTree.of(ctx.game)
     n = len(nets)
     if len(acts) != n:
         raise ValueError("one act per net")
-    keep = [Policy._dev(w, torch.float32, native.NP) for w in nets]
+    H = _one_width(nets, "head_tables", hidden)
+    keep = [Policy._dev(w, torch.float32, native.net_params(H)) for w in nets]
     ptrs = (native.P * max(n, 1))(*[t.data_ptr() if p is None else p for t, p in keep])
     act = (native.I32 * max(n, 1))(*[int(a) for a in acts])
     out = torch.empty((n, tree.ndec, 3, 3), dtype=torch.float32, device="cuda")
-    native.check(ctx.L.nfsp_head_tables(ctx.h, tree.game, ptrs, act, n, native.P(out.data_ptr())), "nfsp_head_tables")
+    if H == 64 and hidden is None:
+        native.check(ctx.L.nfsp_head_tables(ctx.h, tree.game, ptrs, act, n, native.P(out.data_ptr())), "nfsp_head_tables")
+    else:
+        native.check(ctx.L.nfsp_head_tables_h(ctx.h, tree.game, H, ptrs, act, n, native.P(out.data_ptr())),
+                     "nfsp_head_tables_h")
     return out
+
+
+_KIND_ACT = {native.POL_AR_SOFTMAX: native.ACT_SOFTMAX, native.POL_AR_ARGMAX: native.ACT_SOFTMAX,
+             native.POL_BR_GREEDY: native.ACT_RELU, native.POL_BR_GREEDY_LINEAR: native.ACT_LINEAR}
+
+
+def heads_table(heads, legal, kind: int) -> np.ndarray:
+    """Heads ``[ndec, 3, 3]`` (softmax rows for the AR kinds, ReLU / linear Q values for the BR
+    kinds) as the float64 table a net of that ``native.POL_*`` kind executes: softmax rows pass
+    through, the other kinds are one-hot at the first maximum (an all-zero head folds); a raise
+    where ``legal[d]`` is false goes to call."""
+    if kind not in _KIND_ACT:
+        raise ValueError("heads_table: kind must be one of the four net kinds (native.POL_*)")
+    y = np.asarray(heads, np.float32).astype(np.float64).reshape(-1, 3, 3)
+    legal = np.asarray(legal, bool).reshape(-1)
+    if len(legal) != len(y):
+        raise ValueError("heads_table: one legal flag per decision row")
+    if kind != native.POL_AR_SOFTMAX:
+        y = np.eye(3)[np.argmax(y, axis=2)]        # numpy's argmax: the first maximum
+    out = y.copy()
+    il = ~legal
+    out[il, :, 1] = y[il, :, 1] + y[il, :, 2]
+    out[il, :, 2] = 0.0
+    return out
+
+
+def net_policy(ctx, w, kind: int = native.POL_AR_SOFTMAX, tree: GameTree | None = None) -> "Policy":
+    """A packed net of any built width as the ``Policy.table`` it executes under ``kind``
+    (``native.POL_AR_SOFTMAX``, ``POL_AR_ARGMAX``, ``POL_BR_GREEDY``, ``POL_BR_GREEDY_LINEAR``):
+    ``head_tables`` at the net's width, then ``heads_table``.  What ``evaluate``, ``best_response``
+    and the solvers score a net of width other than 64 through; the evaluators' own net kinds are
+    64 wide."""
+    tree = tree or GameTree.of(ctx.game)
+    if kind not in _KIND_ACT:
+        raise ValueError("net_policy: kind must be one of the four net kinds (native.POL_*)")
+    z = head_tables(ctx, [w], [_KIND_ACT[kind]], tree, hidden=net_width(w))[0].cpu().numpy()
+    return Policy.table(heads_table(z, tree.legal, kind))
 
 
 def act_rows(table):
@@ -559,12 +630,13 @@ class FitJob:
     ``ACT_LINEAR`` with "mse" or "huber".  ``weight``: float64 ``[ndec, 3]`` >= 0 per information
     set (None: 1); ``mask``: ``[ndec, 3, 3]``, nonzero where an entry has a target (None: the legal
     actions; not with "ce"); ``v``: the momentum state, float32 like ``w`` (None: zero at the
-    call's start, dropped at its end).  Every input is an array, a device tensor or a device
+    call's start, dropped at its end).  The hidden width is ``w``'s (``net_width``; ``hidden`` where
+    ``w`` is a device address, 64 without it) and is kept as ``.hidden``.  Every input is an array, a device tensor or a device
     address, in the style of ``Policy``; ``w`` and ``v`` are updated in place where they are device
     tensors or addresses, and ``self.w`` / ``self.v`` are the device tensors otherwise."""
 
     def __init__(self, w, target, seat: int, head: int, loss, lr: float, momentum: float = 0.0, weight=None,
-                 mask=None, v=None):
+                 mask=None, v=None, hidden=None):
         import torch
 
         def dev(x, dtype, numel=None):
@@ -572,8 +644,9 @@ class FitJob:
                 return None, None
             t, p = Policy._dev(x, dtype, numel)
             return t, int(t.data_ptr() if p is None else p)
-        self.w, self._w = dev(w, torch.float32, native.NP)
-        self.v, self._v = dev(v, torch.float32, native.NP)
+        self.hidden = _one_width([w] + ([] if v is None else [v]), "FitJob (w and v)", hidden)
+        self.w, self._w = dev(w, torch.float32, native.net_params(self.hidden))
+        self.v, self._v = dev(v, torch.float32, native.net_params(self.hidden))
         self.target, self._t = dev(target, torch.float64)
         self.weight, self._wt = dev(weight, torch.float64)
         self.mask, self._m = dev(mask, torch.uint8)
@@ -589,7 +662,8 @@ class FitJob:
 def fit_tables(ctx, jobs, steps: int, tree: GameTree | None = None) -> np.ndarray:
     """``nfsp_fit_tables``: every job's net takes ``steps`` full-batch steps on its seat's rows, one
     workgroup per job (64 per launch), deterministic: a job's result depends on the job alone, and
-    ``steps`` split over calls with ``v`` carried gives the bits of one call.  Returns the
+    ``steps`` split over calls with ``v`` carried gives the bits of one call.  All jobs of a call
+    have one hidden width (16, 32, 64 or 128: ``nfsp_fit_tables_h`` where it is not 64).  Returns the
     weighted losses ``[n, 2]``: at the weights before step 1 and at the final weights."""
     tree = tree or GameTree.of(ctx.game)
     for k, j in enumerate(jobs):
@@ -598,10 +672,17 @@ def fit_tables(ctx, jobs, steps: int, tree: GameTree | None = None) -> np.ndarra
             if t is not None and t.numel() != numel:
                 raise ValueError(f"fit_tables: job {k}: {name} has {t.numel()} values, expected {numel}")
     n = len(jobs)
+    widths = sorted({j.hidden for j in jobs})
+    if len(widths) > 1:
+        raise ValueError(f"fit_tables: jobs of widths {widths} in one call; one width per call")
     arr = (native.FitJob * max(n, 1))(*[j.spec() for j in jobs])
     out = np.zeros((n, 2))
-    native.check(ctx.L.nfsp_fit_tables(ctx.h, tree.game, arr, n, int(steps), out.ctypes.data_as(native.P)),
-                 "nfsp_fit_tables")
+    if widths in ([], [64]):
+        native.check(ctx.L.nfsp_fit_tables(ctx.h, tree.game, arr, n, int(steps), out.ctypes.data_as(native.P)),
+                     "nfsp_fit_tables")
+    else:
+        native.check(ctx.L.nfsp_fit_tables_h(ctx.h, tree.game, widths[0], arr, n, int(steps),
+                                             out.ctypes.data_as(native.P)), "nfsp_fit_tables_h")
     return out
 
 
@@ -960,7 +1041,9 @@ class MccfrNetSolver(MccfrXSolver):
     epsilon, regret, average, target, fit_steps, loss, lr, momentum)`` per run -- the first five as
     ``MccfrXSolver``'s, target ``native.MCCFR_NET_TARGET_*`` or "avg" / "rowmax", loss "mse" / "huber"
     or ``native.FIT_*``; ``init_seeds`` is one seed per run: the nets are
-    ``glorot_net(RandomState(seed))``, seat 0's first and then seat 1's.  ``sigma_table(k)`` is the
+    ``glorot_net(RandomState(seed), hidden)``, seat 0's first and then seat 1's -- or ``init_nets``,
+    two packed nets per run, whose common width (``net_width``) is the handle's
+    (``nfsp_mccfr_net_create_h``; one width per handle, 16, 32, 64 or 128, read back as ``.hidden``).  ``sigma_table(k)`` is the
     sigma the walkers read ("net") or regret matching on R ("table"), ``head(k)`` the nets' heads z,
     ``net(k, seat)`` a seat's (w, v), ``set_net`` writes them between runs, ``fit_loss(k)`` the
     ``[seat, before / after]`` losses of the last fits, ``current(k)`` the nets' sigma as a ``Policy``
@@ -970,7 +1053,7 @@ class MccfrNetSolver(MccfrXSolver):
     TARGETS = {"avg": native.MCCFR_NET_TARGET_AVG, "rowmax": native.MCCFR_NET_TARGET_ROWMAX}
 
     def __init__(self, ctx, cfgs=((1, 1024, 0.0, "plain", "uniform", "avg", 32, "mse", 0.5, 0.9),), sampling=0,
-                 init_seeds=None):
+                 init_seeds=None, hidden: int = 64, init_nets=None):
         import torch
         _Solver.__init__(self, ctx)
         samp = int(self.SAMPLINGS.get(sampling, sampling))
@@ -983,15 +1066,34 @@ class MccfrNetSolver(MccfrXSolver):
         if len(self.init_seeds) != self.n:
             raise ValueError("MccfrNetSolver: one init seed per run")
         nets = []
-        for s in self.init_seeds:
-            rng = np.random.RandomState(s)
-            nets += [glorot_net(rng), glorot_net(rng)]
-        w0 = torch.as_tensor(np.stack(nets) if nets else np.zeros((0, native.NP), np.float32), device="cuda")
+        if init_nets is not None:
+            nets = [np.ascontiguousarray(w, np.float32).reshape(-1) for w in init_nets]
+            if len(nets) != 2 * self.n:
+                raise ValueError("MccfrNetSolver: init_nets holds two nets per run, seat 0's first")
+            hidden = _one_width(nets, "MccfrNetSolver")
+        else:
+            native.net_params(int(hidden))
+            for s in self.init_seeds:
+                rng = np.random.RandomState(s)
+                nets += [glorot_net(rng, int(hidden)), glorot_net(rng, int(hidden))]
+        self._np = native.net_params(int(hidden))
+        w0 = torch.as_tensor(np.stack(nets) if nets else np.zeros((0, self._np), np.float32), device="cuda")
         arr = (native.MccfrNetCfg * max(self.n, 1))(*[native.MccfrNetCfg(c[0], c[1], samp, *c[2:], 0) for c in self.cfgs])
         ptrs = (native.P * max(2 * self.n, 1))(*[w0[k].data_ptr() for k in range(2 * self.n)])
         h = native.P()
-        native.check(ctx.L.nfsp_mccfr_net_create(ctx.h, arr, self.n, ptrs, C.byref(h)), "nfsp_mccfr_net_create")
+        if init_nets is None and int(hidden) == 64:
+            native.check(ctx.L.nfsp_mccfr_net_create(ctx.h, arr, self.n, ptrs, C.byref(h)), "nfsp_mccfr_net_create")
+        else:
+            native.check(ctx.L.nfsp_mccfr_net_create_h(ctx.h, int(hidden), arr, self.n, ptrs, C.byref(h)),
+                         "nfsp_mccfr_net_create_h")
         self.h = h
+
+    @property
+    def hidden(self) -> int:
+        """the nets' hidden width (``nfsp_mccfr_net_hidden``)"""
+        out = native.I32()
+        native.check(self.ctx.L.nfsp_mccfr_net_hidden(self.h, C.byref(out)), "nfsp_mccfr_net_hidden")
+        return int(out.value)
 
     def _tables(self, run):
         sg, tab, z = native.P(), native.P(), native.P()
@@ -1022,7 +1124,7 @@ class MccfrNetSolver(MccfrXSolver):
         w, v = native.P(), native.P()
         native.check(self.ctx.L.nfsp_mccfr_net_weights(self.h, int(run), int(seat), C.byref(w), C.byref(v)),
                      "nfsp_mccfr_net_weights")
-        return self._view(w.value, native.NP, torch.float32), self._view(v.value, native.NP, torch.float32)
+        return self._view(w.value, self._np, torch.float32), self._view(v.value, self._np, torch.float32)
 
     def net(self, run: int = 0, seat: int = 0) -> tuple:
         """(w, v) of a seat's net, f32 ``[NP]`` each, copied to the host."""
@@ -1038,8 +1140,8 @@ class MccfrNetSolver(MccfrXSolver):
             if src is None:
                 continue
             src = np.ascontiguousarray(src, np.float32)
-            if src.shape != (native.NP,):
-                raise ValueError("a net has native.NP float32 values")
+            if src.shape != (self._np,):
+                raise ValueError(f"a net of this handle has {self._np} float32 values")
             if not np.isfinite(src).all():
                 raise ValueError("set_net: values that are not finite")
             dst.copy_(torch.as_tensor(src, device=dst.device))

@@ -27,6 +27,16 @@ TEXTBOOK_MSE_DECAY = TEXTBOOK_MSE & ~EXT_EPS_CONST      # epsilon / iteration, a
 
 NP = 30 * 64 + 64 + 64 * 3 + 3      # floats of a packed net: W1 | b1 | W2 | b2 (include/nfsp.h)
 NET_AR, NET_BR, NET_TARGET = 0, 1, 2
+# the hidden widths the fits off the engine are built for (nfsp_net_params); the engine's is 64
+FIT_WIDTHS = (16, 32, 64, 128)
+
+
+def net_params(hidden: int) -> int:
+    """floats of a packed net of that width: 34 H + 3 (nfsp_net_params' rule, without the library)"""
+    if hidden not in FIT_WIDTHS:
+        raise ValueError(f"hidden is {hidden}: the widths built are {FIT_WIDTHS}")
+    return 34 * hidden + 3
+
 
 P = C.c_void_p
 I32, I64, U32, U64, F32, F64 = C.c_int, C.c_int64, C.c_uint, C.c_uint64, C.c_float, C.c_double
@@ -239,6 +249,8 @@ SIGNATURES = {
     "nfsp_mccfr_net_tables": (I32, [P, I32, C.POINTER(P), C.POINTER(P), C.POINTER(P)]),
     "nfsp_mccfr_net_weights": (I32, [P, I32, I32, C.POINTER(P), C.POINTER(P)]),
     "nfsp_mccfr_net_loss": (I32, [P, I32, C.POINTER(F64)]),
+    "nfsp_mccfr_net_create_h": (I32, [P, I32, C.POINTER(MccfrNetCfg), I32, C.POINTER(P), C.POINTER(P)]),
+    "nfsp_mccfr_net_hidden": (I32, [P, C.POINTER(I32)]),
     "nfsp_mccfr_set_timing": (I32, [P, I32]),
     "nfsp_mccfr_get_timings": (I32, [P, C.POINTER(F64), C.POINTER(I64)]),
     "nfsp_engine_set_loss_log": (I32, [P, I32]),
@@ -292,6 +304,7 @@ SIGNATURES = {
     "nfsp_engine_td_table": (I32, [P, P, C.POINTER(MemtabInfo)]),
     "nfsp_group_td_tables": (I32, [P, P, C.POINTER(MemtabInfo)]),
     "nfsp_head_tables": (I32, [P, I32, PP, C.POINTER(I32), I32, P]),
+    "nfsp_head_tables_h": (I32, [P, I32, I32, PP, C.POINTER(I32), I32, P]),
     # tables that act: a slot's net (agent/agent.py:124-151's predict calls) replaced by a lookup
     "nfsp_engine_set_act_table": (I32, [P, I32, I32, P]),
     "nfsp_engine_get_act_table": (I32, [P, I32, I32, PP, C.POINTER(I64)]),
@@ -304,6 +317,10 @@ SIGNATURES = {
     # nets fitted to tables: weighted full-batch descent, one workgroup per job
     "nfsp_fit_jobs_check": (I32, [C.POINTER(FitJob), I32, I64]),
     "nfsp_fit_tables": (I32, [P, I32, C.POINTER(FitJob), I32, I64, P]),
+    # the same at hidden widths 16, 32, 64, 128
+    "nfsp_net_params": (I32, [I32, C.POINTER(I64)]),
+    "nfsp_fit_width_check": (I32, [I32, I32, C.POINTER(I64)]),
+    "nfsp_fit_tables_h": (I32, [P, I32, I32, C.POINTER(FitJob), I32, I64, P]),
 }
 # int (*nfsp_exchange_fn)(void* user, float* dev_sum, int64_t n)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, P, P, I64)

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""The capacity table of the 30-64-3 nets ("Nets fitted to tables"): what the AR
+"""The capacity table of the 30-H-3 nets ("Nets fitted to tables"; H = 64 unless
+--hidden says otherwise): what the AR
 net and the Q heads reach when they are fitted to exact tables with exact weights, full batch, on
 the device (nfsp_fit_tables) -- the approximation floors under NFSP's sampled, minibatch fits.
 
@@ -17,6 +18,10 @@ the device (nfsp_fit_tables) -- the approximation floors under NFSP's sampled, m
 * --time: microseconds per step of k_fit_tables for 1 and 64 jobs (HIP events, best of 5 after a
   warm-up, the difference of a long and a short call so that the call's fixed cost drops out), and
   the same rows through nfsp_mlp_fit in <= 64-row minibatches (unweighted: a time comparison only).
+
+* --hidden 16,32,64,128: every table above once per hidden width (nfsp_fit_tables_h; the nets of a
+  width other than 64 are scored through evaluation.net_policy), a "hidden" column in every row;
+  with --time the step times per width too.
 
 JSON goes to profiles/distill/ (--out).
 """
@@ -46,7 +51,8 @@ def event_ms(torch, fn, reps=5):
     return best
 
 
-def step_times(pkg, torch, ctx, tree, short=1000, long=5000):
+def fit_step_times(pkg, torch, ctx, tree, hidden=64, short=1000, long=5000):
+    """us per step of the fit kernel of that width for 1 and 64 jobs: the difference of two calls"""
     import numpy as np
     ev, nat = pkg.evaluation, pkg.native
     rng = np.random.RandomState(0)
@@ -54,13 +60,22 @@ def step_times(pkg, torch, ctx, tree, short=1000, long=5000):
     out = {}
     for n in (1, 64):
         def call(steps, n=n):
-            jobs = [ev.FitJob(ev.glorot_net(np.random.RandomState(k)), table, k & 1, nat.ACT_SOFTMAX, "ce", 0.1, 0.9)
-                    for k in range(n)]
+            jobs = [ev.FitJob(ev.glorot_net(np.random.RandomState(k), hidden), table, k & 1, nat.ACT_SOFTMAX, "ce", 0.1,
+                              0.9) for k in range(n)]
             return lambda: ev.fit_tables(ctx, jobs, steps, tree)
         t0, t1 = event_ms(torch, call(short)), event_ms(torch, call(long))
         out[f"fit_tables_us_per_step_{n}"] = 1e3 * (t1 - t0) / (long - short)
         out[f"fit_tables_call_ms_{n}_jobs_{short}_steps"] = t0
     out["ratio_64_over_1"] = out["fit_tables_us_per_step_64"] / out["fit_tables_us_per_step_1"]
+    return out
+
+
+def step_times(pkg, torch, ctx, tree, short=1000, long=5000):
+    import numpy as np
+    ev, nat = pkg.evaluation, pkg.native
+    rng = np.random.RandomState(0)
+    table = tree.remap(rng.dirichlet(np.ones(3), size=(tree.ndec, 3)))
+    out = fit_step_times(pkg, torch, ctx, tree, 64, short, long)
     # the parent's own path: one net through nfsp_mlp_fit, the seat's rows in <= 64-row minibatches
     d = np.nonzero(tree.seat == 0)[0]
     rows = len(d) * 3
@@ -99,6 +114,7 @@ def main():
     ap.add_argument("--q-loss", default="mse", choices=["mse", "huber"])
     ap.add_argument("--checkpoint", default=None, metavar="PATH")
     ap.add_argument("--time", action="store_true")
+    ap.add_argument("--hidden", default="64", help="hidden widths, comma separated: 16, 32, 64, 128")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import numpy as np
@@ -108,8 +124,11 @@ def main():
     nat, ev, dg = pkg.native, pkg.evaluation, pkg.diagnostics
     game = nat.GAME_KUHN if args.game == "kuhn" else nat.GAME_LEDUC
     steps = [int(x) for x in args.steps.split(",")]
+    widths = [int(x) for x in args.hidden.split(",")]
+    for h in widths:
+        nat.net_params(h)
     seeds = list(range(1, args.inits + 1))
-    out = {"game": args.game, "momentum": args.momentum, "weights": args.weights, "policy": [], "q": []}
+    out = {"game": args.game, "momentum": args.momentum, "weights": args.weights, "hidden": widths, "policy": [], "q": []}
 
     def grid(lrs):
         return [lr for lr in lrs for _ in seeds], [s for _ in lrs for s in seeds]
@@ -129,21 +148,21 @@ def main():
         target, weights = solver.average(), args.weights
         out["target"] = f"CFR+ average, {args.iters} iterations"
     lrs, sd = grid(floats(args.lr))
-    for n in steps:
-        res = dg.distill_policy(ctx, target, weights, n, lrs, args.momentum, sd, tree)
+    for hidden, n in [(h, n) for h in widths for n in steps]:
+        res = dg.distill_policy(ctx, target, weights, n, lrs, args.momentum, sd, tree, hidden)
         out["table_exploitability"] = res[0]["scores"]["table"]
         for lr, seed, r in zip(lrs, sd, res):
-            row = {"steps": n, "lr": lr, "seed": seed, "softmax": r["scores"]["softmax"], "argmax": r["scores"]["argmax"],
+            row = {"hidden": hidden, "steps": n, "lr": lr, "seed": seed, "softmax": r["scores"]["softmax"], "argmax": r["scores"]["argmax"],
                    "loss_minus_entropy": [float(r["losses"][s, 1] - r["entropy"][s]) for s in (0, 1)]}
             out["policy"].append(row)
             print(json.dumps(row), flush=True)
     if args.q and not args.checkpoint:
         lrs, sd = grid(floats(args.q_lr))
-        for linear in (False, True):
+        for hidden, linear in [(h, lin) for h in widths for lin in (False, True)]:
             for n in steps:
-                res = dg.distill_q(ctx, target, linear, args.q_loss, n, lrs, args.momentum, sd, tree)
+                res = dg.distill_q(ctx, target, linear, args.q_loss, n, lrs, args.momentum, sd, tree, hidden)
                 for lr, seed, r in zip(lrs, sd, res):
-                    row = {"head": "linear" if linear else "relu", "loss": args.q_loss, "steps": n, "lr": lr, "seed": seed,
+                    row = {"hidden": hidden, "head": "linear" if linear else "relu", "loss": args.q_loss, "steps": n, "lr": lr, "seed": seed,
                            "q_rmse_exact": [x["q_rmse_exact"] for x in r["reports"]],
                            "greedy_mismatch_share": [x["greedy_mismatch_share"] for x in r["reports"]],
                            "relu_blind_share": [x["relu_blind_share"] for x in r["reports"]],
@@ -153,6 +172,10 @@ def main():
     if args.time:
         out["time"] = step_times(pkg, torch, ctx, tree)
         print(json.dumps(out["time"]), flush=True)
+        for h in widths:
+            if h != 64:
+                out[f"time_hidden_{h}"] = fit_step_times(pkg, torch, ctx, tree, h)
+                print(json.dumps({"hidden": h, **out[f"time_hidden_{h}"]}), flush=True)
     path = args.out or os.path.join(REPO, "profiles", "distill", f"capacity_{args.game}.json")
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "w") as f:

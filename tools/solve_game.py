@@ -50,7 +50,8 @@ hands, the values on the way back up corrected by a learned baseline at every de
 corrected values are larger than one pay, so its budget is smaller: W x iterations up to
 29,142,433 on Leduc at --epsilon 0.6.
 
---regret-net, for the three mccfr solvers: the regrets are held in two 30-64-3 nets per run, fitted to R after
+--regret-net, for the three mccfr solvers: the regrets are held in two 30-H-3 nets per run (--net-hidden 16, 32,
+64 or 128; 64 without it), fitted to R after
 every half-iteration, and the walkers read the nets' sigma (evaluation.MccfrNetSolver, k_mccfr_net_apply):
 sampled regression CFR.  --net-steps K, --net-lr, --net-momentum, --net-target avg|rowmax, --net-loss mse|huber
 and --net-init SEED set the fit; --regret / --average apply as below (left out: plain / uniform).  The lines add
@@ -124,7 +125,7 @@ def time_mccfr(ev, nat, epsilon=None, walkers=1 << 20, repeats=5, baselines=Fals
     solver.close()
 
 
-def time_mccfr_net(ev, nat, sampling, cfg, init_seed, repeats=5, runs=1):
+def time_mccfr_net(ev, nat, sampling, cfg, init_seed, repeats=5, runs=1, hidden=64):
     """Regret nets (--regret-net --time): best of ``repeats`` single iterations of ``runs`` runs of ``cfg``
     (seeds cfg's .. + runs - 1) after a warm-up, and of the same iteration split by the handle's own HIP
     events (nfsp_mccfr_set_timing) into its two walks and its applies (k_mccfr_x_apply and k_mccfr_net_apply,
@@ -132,7 +133,7 @@ def time_mccfr_net(ev, nat, sampling, cfg, init_seed, repeats=5, runs=1):
     import torch
     ctx = nat.Context(1, game=nat.GAME_LEDUC)
     cfgs = [(cfg[0] + k,) + tuple(cfg[1:]) for k in range(runs)]
-    solver = ev.MccfrNetSolver(ctx, cfgs, sampling, [init_seed + k for k in range(runs)]).run(1)
+    solver = ev.MccfrNetSolver(ctx, cfgs, sampling, [init_seed + k for k in range(runs)], hidden=hidden).run(1)
     best = None
     for _ in range(repeats):
         before = solver.counts(0)
@@ -150,7 +151,7 @@ def time_mccfr_net(ev, nat, sampling, cfg, init_seed, repeats=5, runs=1):
             best = rec
     best.update(game="leduc", solver=("mccfr", "mccfr-os", "mccfr-vr")[sampling], regret_net=True, walkers=cfg[1],
                 repeats=repeats, regret=cfg[3], average=cfg[4], net_target=cfg[5], net_steps=cfg[6], net_loss=cfg[7],
-                net_lr=cfg[8], net_momentum=cfg[9], net_init=init_seed,
+                net_lr=cfg[8], net_momentum=cfg[9], net_init=init_seed, net_hidden=hidden,
                 us_per_fit_step_upper=(1e3 * best["ms_applies"] / (2 * cfg[6]) if cfg[6] else None))
     if sampling:
         best.update(epsilon=cfg[2])
@@ -189,6 +190,8 @@ def main():
     ap.add_argument("--net-loss", default="mse", choices=["mse", "huber"], help="--regret-net: the fit's loss")
     ap.add_argument("--net-init", type=int, default=1, metavar="SEED",
                     help="--regret-net: run k's nets are glorot_net(RandomState(SEED + k)), seat 0's then seat 1's")
+    ap.add_argument("--net-hidden", type=int, default=64, choices=[16, 32, 64, 128],
+                    help="--regret-net: the nets' hidden width, one per handle")
     ap.add_argument("--out", default=None, metavar="PATH")
     args = ap.parse_args()
     import __graft_entry__
@@ -211,7 +214,7 @@ def main():
     if args.time and net is not None:
         eps = args.epsilon if sampling else 0.0
         return time_mccfr_net(ev, nat, sampling, (1, args.time_walkers, eps) + rule + net, args.net_init,
-                              runs=args.time_runs)
+                              runs=args.time_runs, hidden=args.net_hidden)
     if args.time:
         if args.solver not in ("mccfr", "mccfr-os", "mccfr-vr"):
             ap.error("--time is for --solver mccfr, mccfr-os and mccfr-vr")
@@ -224,7 +227,7 @@ def main():
     if net is not None:
         solver = ev.MccfrNetSolver(ctx, [(seed, args.walkers, args.epsilon if outcome else 0.0) + rule + net
                                          for seed in range(1, args.seeds + 1)], sampling,
-                                   [args.net_init + k for k in range(args.seeds)])
+                                   [args.net_init + k for k in range(args.seeds)], hidden=args.net_hidden)
     elif rule is not None:
         solver = ev.MccfrXSolver(ctx, [(seed, args.walkers, args.epsilon if outcome else 0.0) + rule
                                        for seed in range(1, args.seeds + 1)],
@@ -273,7 +276,7 @@ def main():
             cur = ev.evaluate_batch(ctx, [(c, c) for c in (solver.current(k) for k in range(solver.n))])
             tv = [solver.sigma_tv(k).tolist() for k in range(solver.n)]
             rec.update(regret_net=True, net_target=net[0], net_steps=net[1], net_loss=net[2], net_lr=net[3],
-                       net_momentum=net[4], net_init=args.net_init, exploitability_current=cur[0]["exploitability"],
+                       net_momentum=net[4], net_init=args.net_init, net_hidden=solver.hidden, exploitability_current=cur[0]["exploitability"],
                        exploitability_current_runs=[x["exploitability"] for x in cur], sigma_tv=tv[0], sigma_tv_runs=tv,
                        fit_loss=solver.fit_loss(0).tolist(),
                        fit_loss_runs=[solver.fit_loss(k).tolist() for k in range(solver.n)])
