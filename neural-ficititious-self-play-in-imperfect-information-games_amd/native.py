@@ -458,7 +458,12 @@ class Context(Handle):
         self.h = h
         self.n = int(n_envs)
         self.game = int(game)
-        check(L.nfsp_set_stream(h, stream_handle()), "nfsp_set_stream")
+        self.set_stream()
+
+    def set_stream(self):
+        """Rebind the ctx -- and every engine, group and solver on it -- to torch's current stream
+        (``nfsp_set_stream``).  Nothing orders the new stream after the one it leaves: the caller does."""
+        check(self.L.nfsp_set_stream(self.h, stream_handle()), "nfsp_set_stream")
 
     def call(self, name, *args):
         check(getattr(self.L, name)(self.h, *args), name)
